@@ -25,7 +25,15 @@ This file is the CONTRACT: arguments, the two timed regions, the JSON line, the 
 line carries beside that (target_512, progressive, host_load, batch_raymarch, halo_loopback, config4, self-checks) is
 bench_extras.py; the timing helpers both share are bench_common.py.
 
+A plain run measures the headline only: at N = 1 a short probe (every pipeline's fill and march timed for PROBE_STEPS steps)
+picks the pipeline that is fastest end to end, and only that one is timed, K steps of fill and K steps of march;
+at N > 1 the fill step and the march.  --full adds everything else as before: K steps of every pipeline (the fastest of them
+is `pipeline`), the interleaved and double-buffered variants, the per-launch distributions, the N > 1 kernel-alone roofline
+region, where the run was measured (rocm-smi), bench_extras.py and the CPU baseline.  --dump-outputs DIR writes what the
+timed path computed in its last step (dump_outputs).
+
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -101,7 +109,45 @@ def parse_args():
     ap.add_argument("--no-config4", action="store_true", help="N>1: skip the cube-geometry block (BASELINE config 4)")
     ap.add_argument("--config4-side", type=int, default=512,
                     help="N>1: voxels per rank of the cube-geometry block are side^3 (8 x 512^3 = config 4's 1024^3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: every pipeline for K steps, the variants, per-launch "
+                         "statistics, the extras (bench_extras.py), the CPU baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of an array above DUMP_ARRAY_BYTES)")
     return ap.parse_args()
+
+
+PROBE_STEPS = 100
+
+
+def pick_pipeline(cands, warmup, torch, device):
+    """Plain runs, N = 1: which pipeline is fastest end to end, from a short probe instead of K steps of each: every
+    pipeline's fill and march timed the way --full times them (pre-warm, warm-up, one region each), for PROBE_STEPS steps.
+    cands: name -> (fill, march).  Returns (name, {name: probe ms per step})."""
+    ms = {name: sum(region(fn, PROBE_STEPS, warmup, torch, None, 1, device)[0] for fn in (fill, march))
+          for name, (fill, march) in cands.items()}
+    return min(ms, key=ms.get), {k: round(v, 4) for k, v in ms.items()}
+
+
+DUMP_ARRAY_BYTES = 16 << 20  # per array: the three arrays written stay under 64 MB in all
+DUMP_SAMPLE = 1 << 20  # records of an array above that
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, arrays, torch):
+    """--dump-outputs DIR: every device tensor of `arrays` as DIR/<name>.npy, float32.  An array above DUMP_ARRAY_BYTES is
+    written as DUMP_SAMPLE of its records (rows of the last axis: a voxel's four channels, a pixel's RGBA) at the flat record
+    indices numpy.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False), sorted: the same records for the same
+    shape in every run and every build, so that two builds can be compared file for file."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() * t.element_size() > DUMP_ARRAY_BYTES:
+            rec = t.reshape(-1, t.shape[-1])
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rec.shape[0], DUMP_SAMPLE, replace=False))
+            t = rec[torch.from_numpy(idx).to(rec.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.detach().cpu().numpy().astype(np.float32, copy=False))
 
 
 
@@ -254,7 +300,7 @@ def contract_line(line, full_path):
     `full_path` and to stderr."""
     c = _pick(line, "metric", "value", "unit", "value_rays", "unit_rays", "n_gpus", "steps", "warmup", "ms_per_step",
               "ms_per_step_fill", "ms_per_step_raymarch", "ms_per_step_median", "ms_per_step_p95", "higher_is_better", "scaling",
-              "vs_baseline", "dtype")
+              "vs_baseline", "dtype", "full_run")
     c["data"] = "synthetic"
     cfg = line["config"]
     c["config"] = {"workload": cfg["workload"], "grid": cfg["grid_global"], "image": cfg["image"],
@@ -522,11 +568,35 @@ def run(redirect):
         #   fused: sdfv_fill_grid_commit (36 B/voxel)  -> sdfv_raymarch_ex (desc.dist) over the compact distance volume it wrote
         # Each half is timed in its own region of exactly K steps (voxels and rays are different units); the textures
         # the march reads are the ones the timed fill wrote.  value / value_rays / ms_per_step all come from ONE
-        # pipeline: the one that is faster end to end.
+        # pipeline: the one that is faster end to end (--full: K steps of every pipeline; a plain run: the probe's pick alone).
         rp = pkg.default_render_params(grid)
         cam0 = pkg.camera_look_at(aspect=W / H)  # the reference default camera (scene/mod.rs:82-95)
         rgba = torch.empty((1, H, W, 4), dtype=torch.float32, device=device)
         dist_vol = torch.empty((side, side, side), dtype=torch.float32, device=device)
+        # third pipeline (round 4): the fused fill writes the march's y-INTERLEAVED volume itself (SDFV_PASS_VOLUME_INTERLEAVED: a
+        # step-1 virgin pass = the dense kernel, textures + that volume, 36 B/voxel) and the march gathers from it -- what
+        # SDFViewer does for grids beyond the last-level cache; no commit pass between the two
+        wanted = [p for p in ("plain", "fused", "fused_ilv") if args.pipeline in ("both", p) and (p != "fused_ilv" or side % 2 == 0)]
+        ILV_FLAGS = pkg._capi.PASS_VIRGIN_GRID | pkg._capi.PASS_VOLUME_INTERLEAVED
+        ilv_vol = torch.empty((side, side, side), dtype=torch.float32, device=device) if "fused_ilv" in wanted else None
+
+        def fill_ilv():
+            pkg.fill_grid_pass(prm, grid, 1, owned0, owned1, dist=ilv_vol, flags=ILV_FLAGS)
+
+        def march_ilv():
+            pkg.raymarch(rp, owned0, owned1, cam0, W, H, out=rgba, ilv=ilv_vol)
+
+        pipelines = {"plain": (lambda: pkg.fill_grid(prm, grid, owned0, owned1),
+                               lambda: pkg.raymarch(rp, owned0, owned1, cam0, W, H, out=rgba)),
+                     "fused": (lambda: pkg.fill_grid(prm, grid, owned0, owned1, dist=dist_vol),
+                               lambda: pkg.raymarch(rp, owned0, owned1, cam0, W, H, out=rgba, dist=dist_vol)),
+                     "fused_ilv": (fill_ilv, march_ilv)}
+        probe = None
+        if args.full or len(wanted) == 1:
+            timed = wanted
+        else:
+            picked, probe = pick_pipeline({p: pipelines[p] for p in wanted}, Wm, torch, device)
+            timed = [picked]
 
         def both(fill_kw, march_kw):
             def step():
@@ -537,41 +607,26 @@ def run(redirect):
         INF = float("inf")
         fill_plain_ms = fill_plain_ev = march_tex0_ms = march_tex0_ev = inter_plain_ms = INF
         fill_fused_ms = fill_fused_ev = march_dist_ms = march_dist_ev = inter_fused_ms = INF
-        if args.pipeline in ("both", "plain"):
-            fill_plain_ms, fill_plain_ev = region(lambda: pkg.fill_grid(prm, grid, owned0, owned1), K, Wm, torch, dist, 1, device)
-            march_tex0_ms, march_tex0_ev = region(lambda: pkg.raymarch(rp, owned0, owned1, cam0, W, H, out=rgba), K, Wm,
-                                                  torch, dist, 1, device)
-            inter_plain_ms = both({}, {})
-        if args.pipeline in ("both", "fused"):
-            fill_fused_ms, fill_fused_ev = region(lambda: pkg.fill_grid(prm, grid, owned0, owned1, dist=dist_vol), K, Wm,
-                                                  torch, dist, 1, device)
-            march_dist_ms, march_dist_ev = region(lambda: pkg.raymarch(rp, owned0, owned1, cam0, W, H, out=rgba, dist=dist_vol),
-                                                  K, Wm, torch, dist, 1, device)
-            inter_fused_ms = both({"dist": dist_vol}, {"dist": dist_vol})
-        # third pipeline (round 4): the fused fill writes the march's y-INTERLEAVED volume itself (SDFV_PASS_VOLUME_INTERLEAVED: a
-        # step-1 virgin pass = the dense kernel, textures + that volume, 36 B/voxel) and the march gathers from it -- what
-        # SDFViewer does for grids beyond the last-level cache; no commit pass between the two
+        if "plain" in timed:
+            fill_plain_ms, fill_plain_ev = region(pipelines["plain"][0], K, Wm, torch, dist, 1, device)
+            march_tex0_ms, march_tex0_ev = region(pipelines["plain"][1], K, Wm, torch, dist, 1, device)
+            inter_plain_ms = both({}, {}) if args.full else INF
+        if "fused" in timed:
+            fill_fused_ms, fill_fused_ev = region(pipelines["fused"][0], K, Wm, torch, dist, 1, device)
+            march_dist_ms, march_dist_ev = region(pipelines["fused"][1], K, Wm, torch, dist, 1, device)
+            inter_fused_ms = both({"dist": dist_vol}, {"dist": dist_vol}) if args.full else INF
         fill_ilv_ms = fill_ilv_ev = march_ilv_ms = march_ilv_ev = inter_ilv_ms = INF
-        ILV_FLAGS = pkg._capi.PASS_VIRGIN_GRID | pkg._capi.PASS_VOLUME_INTERLEAVED
-        if args.pipeline in ("both", "fused_ilv") and side % 2 == 0:
-            ilv_vol = torch.empty((side, side, side), dtype=torch.float32, device=device)
-
-            def fill_ilv():
-                pkg.fill_grid_pass(prm, grid, 1, owned0, owned1, dist=ilv_vol, flags=ILV_FLAGS)
-
-            def march_ilv():
-                pkg.raymarch(rp, owned0, owned1, cam0, W, H, out=rgba, ilv=ilv_vol)
-
+        if "fused_ilv" in timed:
             fill_ilv_ms, fill_ilv_ev = region(fill_ilv, K, Wm, torch, dist, 1, device)
             march_ilv_ms, march_ilv_ev = region(march_ilv, K, Wm, torch, dist, 1, device)
-            inter_ilv_ms = region(lambda: (fill_ilv(), march_ilv()), K, Wm, torch, dist, 1, device)[0]
+            inter_ilv_ms = region(lambda: (fill_ilv(), march_ilv()), K, Wm, torch, dist, 1, device)[0] if args.full else INF
         # The fused pipeline software-pipelined over TWO sets of buffers and two streams: the march of step k (latency-bound on
         # a few long waves, most of the machine idle) runs beside the fill of step k + 1 (HBM-store-bound) -- what the
         # reference's own frame loop does on one thread in turns (scene/mod.rs:166-200: fill passes and the render of the
         # state so far alternate within a frame).  Every step still fills a whole grid and marches a whole frame over the grid
         # ITS fill wrote; nothing is skipped.  Reported beside the sequential pipelines, never as `value`.
         overlapped = None
-        if args.pipeline in ("both", "fused") and not args.no_overlapped:
+        if args.full and args.pipeline in ("both", "fused") and not args.no_overlapped:
             b0, b1 = torch.empty_like(owned0), torch.empty_like(owned1)
             bd = torch.empty_like(dist_vol)
             sets = [(owned0, owned1, dist_vol), (b0, b1, bd)]
@@ -602,7 +657,7 @@ def run(redirect):
             del b0, b1, bd
         # the separate device-side commit (what a caller pays who filled without the volume and wants it afterwards)
         commit_ms = INF
-        if args.pipeline == "both":
+        if args.full and args.pipeline == "both":
             commit_ms = region(lambda: pkg.commit_distance(grid, owned0, dist=dist_vol), aux_steps, 1, torch, dist, 1, device)[0]
         pipes = {
             "plain": {"fill": "sdfv_fill_grid (32 B/voxel)", "march": "sdfv_raymarch over tex0.r",
@@ -638,17 +693,11 @@ def run(redirect):
             fill_ms, march_ms, kern_ms, march_ev, bpv = fill_plain_ms, march_tex0_ms, fill_plain_ev, march_tex0_ev, 32
         fill_mvox = voxels_per_rank / fill_ms / 1e3
         march_mrays = W * H / march_ms / 1e3
-        # the distribution behind the two means (SURVEY 8d asks for the median): launches timed one by one
-        if chosen == "fused_ilv":
-            st_fill = per_step_stats(fill_ilv, args.per_step_samples, torch)
-            st_march = per_step_stats(march_ilv, args.per_step_samples, torch)
-        elif chosen == "fused":
-            st_fill = per_step_stats(lambda: pkg.fill_grid(prm, grid, owned0, owned1, dist=dist_vol), args.per_step_samples, torch)
-            st_march = per_step_stats(lambda: pkg.raymarch(rp, owned0, owned1, cam0, W, H, out=rgba, dist=dist_vol),
-                                      args.per_step_samples, torch)
-        else:
-            st_fill = per_step_stats(lambda: pkg.fill_grid(prm, grid, owned0, owned1), args.per_step_samples, torch)
-            st_march = per_step_stats(lambda: pkg.raymarch(rp, owned0, owned1, cam0, W, H, out=rgba), args.per_step_samples, torch)
+        # the distribution behind the two means (SURVEY 8d asks for the median): launches timed one by one (--full)
+        st_fill = st_march = None
+        if args.full:
+            st_fill = per_step_stats(pipelines[chosen][0], args.per_step_samples, torch)
+            st_march = per_step_stats(pipelines[chosen][1], args.per_step_samples, torch)
         if st_fill and st_march:
             out["ms_per_step_median"] = round(st_fill["median"] + st_march["median"], 4)
             out["ms_per_step_p95"] = round(st_fill["p95"] + st_march["p95"], 4)
@@ -659,9 +708,13 @@ def run(redirect):
                                "note": "ms_per_step_median / _p95 = fill + raymarch of `pipeline`, each launch between its own "
                                        "pair of HIP events; value / ms_per_step stay the K-step means of the contract"}
         out["pipeline"] = chosen
-        out["pipeline_plain"] = pipes["plain"] if args.pipeline in ("both", "plain") else None
-        out["pipeline_fused"] = pipes["fused"] if args.pipeline in ("both", "fused") else None
-        out["pipeline_fused_ilv"] = pipes["fused_ilv"] if (args.pipeline in ("both", "fused_ilv") and side % 2 == 0) else None
+        out["pipeline_plain"] = pipes["plain"] if "plain" in timed else None
+        out["pipeline_fused"] = pipes["fused"] if "fused" in timed else None
+        out["pipeline_fused_ilv"] = pipes["fused_ilv"] if "fused_ilv" in timed else None
+        out["pipeline_probe"] = None if probe is None else {
+            "ms_per_step": probe, "steps": PROBE_STEPS,
+            "note": "plain run: the probe that picked `pipeline` (fill + march of every pipeline, PROBE_STEPS steps each, timed "
+                    "like the regions of --full); only `pipeline` was then timed for K steps (--full times every pipeline)"}
         out["pipeline_note"] = ("three consistent pipelines over the same buffers (plain; fused = + the distance volume; fused_ilv = + the "
                                 "y-interleaved volume instead); value, value_rays, ms_per_step and "
                                 "roofline all come from `pipeline` (the faster one end to end); *_interleaved = K steps "
@@ -692,12 +745,14 @@ def run(redirect):
         own_dist = slab_dist[slab.ghost_lo:slab.ghost_lo + (slab.z_end - slab.z_begin)]
         filler, transport = make_filler(gdims, slab, slab_dist)
         fill_ms, _ = region(filler.step, K, Wm, torch, dist, world, device)
-        # dominant kernel alone (a step = boundary work + exchange + fill), HIP events on the launch stream
-        _, kern_ms = region(lambda: pkg.fill_grid(prm, grid, owned0, owned1, dist=own_dist), K, 1, torch, dist, world, device)
         fill_mvox = total_voxels / fill_ms / 1e3
-        out["roofline"] = fill_roofline(kern_ms, voxels_per_rank, 36, load_traffic(args.workload + "_fused"))
-        out["roofline"]["traffic_stale"] = traffic_stale(args.workload + "_fused")
-        out["fill_step_fraction_of_plain_fill"] = round(kern_ms / fill_ms, 3)
+        out["roofline"] = out["fill_step_fraction_of_plain_fill"] = None
+        if args.full:
+            # dominant kernel alone (a step = boundary work + exchange + fill), HIP events on the launch stream
+            _, kern_ms = region(lambda: pkg.fill_grid(prm, grid, owned0, owned1, dist=own_dist), K, 1, torch, dist, world, device)
+            out["roofline"] = fill_roofline(kern_ms, voxels_per_rank, 36, load_traffic(args.workload + "_fused"))
+            out["roofline"]["traffic_stale"] = traffic_stale(args.workload + "_fused")
+            out["fill_step_fraction_of_plain_fill"] = round(kern_ms / fill_ms, 3)
         # raymarch: one camera per rank over a replica of the N = 1 grid, filled by the same fused fill
         rgrid = pkg.make_grid((side, side, side))
         r0, r1 = pkg.alloc_textures(rgrid, device=device)
@@ -711,10 +766,12 @@ def run(redirect):
                                     torch, dist, world, device)
         march_mrays = W * H * world / march_ms / 1e3
         # the distribution behind the two means, like the N = 1 line: every rank times its launches one by one (the step
-        # contains the exchange, so all ranks make the same calls), MAX over ranks of median and p95
-        STAGE("per-step statistics of the fill step and the march")
-        st_fill = per_step_stats(filler.step, min(args.per_step_samples, 20), torch, warm=2)
-        st_march = per_step_stats(lambda: pkg.raymarch(rp, r0, r1, my_cams, W, H, out=rgba, dist=dist_vol), min(args.per_step_samples, 20), torch, warm=2)
+        # contains the exchange, so all ranks make the same calls), MAX over ranks of median and p95 (--full)
+        st_fill = st_march = None
+        if args.full:
+            STAGE("per-step statistics of the fill step and the march")
+            st_fill = per_step_stats(filler.step, min(args.per_step_samples, 20), torch, warm=2)
+            st_march = per_step_stats(lambda: pkg.raymarch(rp, r0, r1, my_cams, W, H, out=rgba, dist=dist_vol), min(args.per_step_samples, 20), torch, warm=2)
         if st_fill and st_march:
             t = torch.tensor([st_fill["median"], st_fill["p95"], st_march["median"], st_march["p95"]], dtype=torch.float64, device=cdev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -732,7 +789,8 @@ def run(redirect):
         # what RCCL itself says about the library communicator the step ran on (None under the torch transport)
         comm = getattr(filler, "comm", None)
         out["rccl_ranks"] = None if comm is None else comm.rccl_ranks[1]
-        out["roofline"]["rccl_ranks"] = out["rccl_ranks"]  # (the driver's record keeps nested objects whole)
+        if out["roofline"] is not None:
+            out["roofline"]["rccl_ranks"] = out["rccl_ranks"]  # (the driver's record keeps nested objects whole)
         out["rccl_rank_of_rank0"] = None if comm is None else comm.rccl_ranks[0]
         out["torch_world_size"] = dist.get_world_size()
 
@@ -772,22 +830,27 @@ def run(redirect):
     line.update(out)
     line["raymarch_kernel_ms"] = round(march_ev, 4)
     line["incomplete"] = None  # True only when the watchdog had to print the line for an extra that hung
-    line["box"] = box_stamp(torch, device)
+    line["full_run"] = args.full  # False: the headline alone; --full measures everything below
+    line["box"] = box_stamp(torch, device) if args.full else None
     line["build_id"] = running_build_id()  # sdfv_build_id(): which kernel sources the timed library was built from
     for key in ("batch_raymarch", "target_512", "progressive", "host_load", "ingest", "halo_loopback", "config4"):
         line[key] = None
-    PARTIAL["line"], PARTIAL["since"] = line, time.monotonic()
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results: the textures the fill wrote (this rank's slab at N > 1) and the march's frames
+        dump_outputs(args.dump_outputs, {"tex0": owned0, "tex1": owned1, "rgba": rgba}, torch)
 
-    # ---------------- everything beside the contract (bench_extras.py): never `value`, never fatal ----------------
-    import bench_extras
-    ctx = SimpleNamespace(args=args, pkg=pkg, par=par, torch=torch, dist=dist, world=world, rank=rank, device=device, cdev=cdev,
-                          multi=multi, loopback=loopback, backend=backend, transport=transport, filler=filler, slab=slab,
-                          grid=grid, gdims=gdims, side=side, W=W, H=H, K=K, prm=prm, rp=rp, r0=r0, r1=r1, owned0=owned0,
-                          owned1=owned1, dist_vol=dist_vol, slab_dist=slab_dist if multi else None, line=line)
-    bench_extras.run_extras(ctx)
-    PARTIAL["since"] = None  # the extras are done (the CPU baseline below only uses this process's host cores)
+    # ---------------- everything beside the contract (bench_extras.py, --full): never `value`, never fatal ----------------
+    if args.full:
+        PARTIAL["line"], PARTIAL["since"] = line, time.monotonic()
+        import bench_extras
+        ctx = SimpleNamespace(args=args, pkg=pkg, par=par, torch=torch, dist=dist, world=world, rank=rank, device=device, cdev=cdev,
+                              multi=multi, loopback=loopback, backend=backend, transport=transport, filler=filler, slab=slab,
+                              grid=grid, gdims=gdims, side=side, W=W, H=H, K=K, prm=prm, rp=rp, r0=r0, r1=r1, owned0=owned0,
+                              owned1=owned1, dist_vol=dist_vol, slab_dist=slab_dist if multi else None, line=line)
+        bench_extras.run_extras(ctx)
+        PARTIAL["since"] = None  # the extras are done (the CPU baseline below only uses this process's host cores)
     if rank == 0:
-        if not args.no_cpu_baseline and not multi:  # rank 0, N = 1 only
+        if args.full and not args.no_cpu_baseline and not multi:  # rank 0, N = 1 only
             line["cpu_baseline"] = cpu_baseline(wl, args.cpu_baseline_seconds)
         emit(line, redirect)
     if multi:

@@ -46,6 +46,27 @@ def test_contract_line_of_a_full_record(bench, record):
         assert d["cpu_baseline"]["kind"] == "port" and "sample" in d["cpu_baseline"] and d["cpu_baseline"]["all_cores"]["cores"] >= 1
 
 
+def test_dump_outputs_writes_float32_and_a_fixed_sample_of_a_large_array(bench, tmp_path):
+    """--dump-outputs: an array up to DUMP_ARRAY_BYTES is written whole; a larger one as DUMP_SAMPLE whole records (last axis)
+    at the sorted indices DUMP_SEED draws -- the same file from every run -- and the files stay under 64 MB in all."""
+    import numpy as np
+    import torch
+    small = torch.arange(8 * 8 * 4, dtype=torch.float32).reshape(1, 8, 8, 4)
+    big = torch.arange(1030 * 1024 * 4, dtype=torch.float32).reshape(1030, 1024, 4)  # 16.1 MiB, every value exact in f32
+    assert big.numel() * 4 > bench.DUMP_ARRAY_BYTES >= small.numel() * 4
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / f"d{k}"), {"small": small, "big": big}, torch)
+    s = np.load(tmp_path / "d0" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (1, 8, 8, 4) and np.array_equal(s, small.numpy())
+    b = np.load(tmp_path / "d0" / "big.npy")
+    assert b.dtype == np.float32 and b.shape == (bench.DUMP_SAMPLE, 4)
+    rec = (b[:, 0] / 4).astype(np.int64)
+    want = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(1030 * 1024, bench.DUMP_SAMPLE, replace=False))
+    assert np.array_equal(rec, want) and np.array_equal(b, big.reshape(-1, 4).numpy()[want])
+    assert np.array_equal(b, np.load(tmp_path / "d1" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "d0" / f) for f in os.listdir(tmp_path / "d0")) < 64e6
+
+
 def test_contract_line_stays_short_and_strict_whatever_the_record_holds(bench):
     full = json.loads(open(os.path.join(ROOT, "profiles", "r04_final_bench_256.json")).read())
     # a record that grew: forty more progressive cases per size, prose everywhere, numbers that are not JSON

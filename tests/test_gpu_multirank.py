@@ -52,7 +52,7 @@ def test_bench_weak_scaling_path_two_ranks_one_gpu(world, geometry, tmp_path):
     env = dict(os.environ, SDFV_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     port = 29600 + world + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full",
            "--gpus", str(world), "--steps", "2", "--warmup", "1", "--workload", "64", "--no-cpu-baseline",
            "--config4-side", "32", "--prewarm-ms", "5", "--per-step-samples", "4",
            "--weak-geometry", geometry]
@@ -93,7 +93,7 @@ def test_bench_weak_scaling_path_two_ranks_one_gpu(world, geometry, tmp_path):
 def test_bench_line_carries_the_whole_contract(tmp_path):
     """Every key the driver's contract names is in bench.py's short JSON line (N = 1, tiny workload): under 4 KB, strict JSON,
     the last line of stdout; everything else the run measured is in the full record it names."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "64",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--workload", "64",
            "--cpu-baseline-seconds", "1", "--prewarm-ms", "5"]
     c, d, out = run_bench(cmd, None, tmp_path, timeout=600)
     for key in ("cpu_baseline", "ms_per_step_median", "ms_per_step_p95", "roofline_raymarch", "host_load", "progressive", "box"):
@@ -142,6 +142,43 @@ def test_bench_line_carries_the_whole_contract(tmp_path):
     assert d["progressive"]["64"]["virgin_load_2_passes"]["ms"] > 0
 
 
+def test_plain_bench_run_times_the_headline_alone_and_dumps_its_outputs(tmp_path, pkg, oracle):
+    """A plain run (no --full): the probe's pick is the one pipeline timed, for exactly --steps steps, and nothing beside the
+    headline is measured.  --dump-outputs writes the last timed step's textures and frame: the same words in two runs, the
+    textures those of the oracle's 64^3 fill, the frame within the RGBA tolerance of the oracle's march."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        where = tmp_path / f"dump{k}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--workload", "64",
+               "--prewarm-ms", "5", "--dump-outputs", str(where)]
+        c, d, out = run_bench(cmd, None, tmp_path, timeout=600)
+        assert c["steps"] == 7 and c["warmup"] == 2 and c["full_run"] is False and c["dtype"] == "f32" and c["higher_is_better"] is True
+        assert abs(c["ms_per_step"] - c["ms_per_step_fill"] - c["ms_per_step_raymarch"]) < 1e-3 and c["value"] > 0
+        probe = d["pipeline_probe"]["ms_per_step"]
+        assert sorted(probe) == ["fused", "fused_ilv", "plain"] and d["pipeline"] == min(probe, key=probe.get)
+        for name in ("plain", "fused", "fused_ilv"):  # only the picked pipeline was timed
+            assert (d["pipeline_" + name] is not None) == (name == d["pipeline"]), name
+        assert abs(d["pipeline_" + d["pipeline"]]["ms_per_step"] - d["ms_per_step"]) < 1e-3
+        assert d["roofline"]["frac"] > 0 and d["roofline_raymarch"]["avg_launch_ms"] > 0
+        assert "cpu_baseline" not in d and "per_step" not in d and d["pipeline_overlapped"] is None and d["box"] is None
+        assert all(d[key] is None for key in ("target_512", "progressive", "host_load", "ingest", "batch_raymarch", "halo_loopback"))
+        arrays = {name: np.load(where / f"{name}.npy") for name in ("tex0", "tex1", "rgba")}
+        assert sorted(os.listdir(where)) == ["rgba.npy", "tex0.npy", "tex1.npy"]
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert arrays["tex0"].shape == arrays["tex1"].shape == (64, 64, 64, 4) and arrays["rgba"].shape == (1, 512, 512, 4)
+        dumps.append(arrays)
+    for name in ("tex0", "tex1", "rgba"):
+        assert np.array_equal(dumps[0][name].view(np.uint32), dumps[1][name].view(np.uint32)), name
+    r0, r1 = oracle.fill_dense(oracle.default_params(), (64, 64, 64), threads=4)
+    assert np.array_equal(dumps[0]["tex0"].view(np.uint32), r0.view(np.uint32))
+    assert np.array_equal(dumps[0]["tex1"].view(np.uint32), r1.view(np.uint32))
+    rp = oracle.copy_struct(oracle.RenderParams, pkg.default_render_params(pkg.make_grid((64, 64, 64))))
+    cam = oracle.copy_struct(oracle.Camera, pkg.camera_look_at(aspect=1.0))
+    want, _ = oracle.raymarch(rp, r0, r1, cam, 512, 512, threads=4, want_aux=False)
+    assert float(np.abs(dumps[0]["rgba"][0] - want).max()) <= 1e-4
+
+
 def test_bench_multi_gpu_path_over_rccl_in_loopback(tmp_path):
     """The N > 1 path under the backend the driver uses (nccl = RCCL), as far as one GPU can take it: world size 1 with
     SDFV_BENCH_FORCE_MULTI=1 -- torch's RCCL process group AND the library's own RCCL communicator in one process, the rank
@@ -149,7 +186,7 @@ def test_bench_multi_gpu_path_over_rccl_in_loopback(tmp_path):
     self-checks on device tensors.  (Two ranks on one device are refused by RCCL: test below.)"""
     env = dict(os.environ, SDFV_BENCH_FORCE_MULTI="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29700 + os.getpid() % 200),
                WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "64",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "64",
            "--no-cpu-baseline", "--config4-side", "32", "--prewarm-ms", "5"]
     c, d, out = run_bench(cmd, env, tmp_path, timeout=600)
     assert c["loopback"] is True and c["rccl_ranks"] == 1 and c["roofline"]["rccl_ranks"] == 1 and c["halo_transport"] == "sdfv_slab_fill_step"
@@ -238,7 +275,7 @@ def test_watchdog_prints_the_measured_line_when_an_extra_hangs(tmp_path):
     batch ...) must not lose them.  SDFV_BENCH_EXTRAS_S = 0.01 makes the watchdog fire inside the first extra: the process
     exits 0 and its one JSON line carries value / value_rays / ms_per_step / roofline plus a "watchdog" note naming the stage."""
     env = dict(os.environ, SDFV_BENCH_EXTRAS_S="0.01")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "64",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--workload", "64",
            "--no-cpu-baseline", "--prewarm-ms", "5", "--per-step-samples", "2"]
     c, d, out = run_bench(cmd, env, tmp_path, timeout=600)
     assert c["value"] > 0 and c["value_rays"] > 0 and c["incomplete"] is True and "watchdog" in c and "WATCHDOG" in out.stderr

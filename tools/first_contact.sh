@@ -24,7 +24,7 @@ run() {  # name, ranks, bench arguments...
     PORT=$((PORT + 1))
     echo "[first_contact] $name: $ranks ranks: bench.py $*" >&2
     SDFV_BENCH_FULL_JSON=$OUT/${name}_full.json timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $ranks \
-        --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus $ranks --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err
+        --master-addr 127.0.0.1 --master-port $PORT bench.py --full --gpus $ranks --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err
     local rc=$?
     tail -n 1 $OUT/$name.json
     if [ $rc -ne 0 ] || ! tail -n 1 $OUT/$name.json | python -c 'import json,sys; d=json.loads(sys.stdin.readline()); ok = d.get("sharded_fill_verified") is True and not d.get("incomplete"); sys.exit(0 if ok else 1)'; then

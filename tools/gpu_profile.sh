@@ -13,7 +13,7 @@ mkdir -p $OUT
 # --pipeline: ONE kernel variant per kernel name (plain 32 B/voxel fill + tex0 march, or fused 36 B/voxel fill + distance-
 # volume march), so that per-kernel averages belong to one variant; --no-batch: no 64-camera batch, 512^3 block or
 # loopback probe
-CMD="python bench.py --steps 10 --warmup 2 --workload $WL --pipeline $PIPE --no-cpu-baseline --no-batch --no-overlapped"
+CMD="python bench.py --full --steps 10 --warmup 2 --workload $WL --pipeline $PIPE --no-cpu-baseline --no-batch --no-overlapped"
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace --output-format csv -- $CMD > $OUT/trace.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_LDS -d $OUT/pmc_sq -o pmc --output-format csv -- $CMD > $OUT/pmc_sq.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE GRBM_GUI_ACTIVE -d $OUT/pmc_wr -o pmc --output-format csv -- $CMD > $OUT/pmc_wr.log 2>&1

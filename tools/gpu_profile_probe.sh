@@ -1,5 +1,6 @@
 #!/bin/bash
-# The run the bench LINE describes, under the profiler: default bench.py options (all three pipelines), kernel trace + stats;
+# The run the bench LINE describes, under the profiler: a plain bench.py run (the probe over all three pipelines, then the one it
+# picks), kernel trace + stats;
 # tools/kernel_trace_avg.py lists the launches per (kernel, grid size).  usage: tools/gpu_profile_probe.sh <tag> [workload]
 TAG=${1:-probe}
 WL=${2:-256}

@@ -8,8 +8,8 @@ cd $GRAFT_REPO_ROOT
 D=gpurun_out/${R}final
 mkdir -p $D
 (rocm-smi --showclocks --showuniqueid 2>&1 | grep -i "sclk\|mclk\|fclk\|unique") > $D/box_before.txt
-SDFV_BENCH_FULL_JSON=$D/bench256_full.json python bench.py > $D/bench256.json 2> $D/bench256.err
-SDFV_BENCH_FULL_JSON=$D/bench512_full.json python bench.py --workload 512 > $D/bench512.json 2> $D/bench512.err
+SDFV_BENCH_FULL_JSON=$D/bench256_full.json python bench.py --full > $D/bench256.json 2> $D/bench256.err
+SDFV_BENCH_FULL_JSON=$D/bench512_full.json python bench.py --full --workload 512 > $D/bench512.json 2> $D/bench512.err
 for spec in "${R}_256_ilv 256 fused_ilv" "${R}_256_plain 256 plain" "${R}_256_fused 256 fused" "${R}_512_ilv 512 fused_ilv" "${R}_512_plain 512 plain" "${R}_512_fused 512 fused"; do
   bash tools/gpu_profile.sh $spec > /dev/null 2>&1
 done
@@ -36,6 +36,6 @@ python tools/pass_loads_ab.py 256 512 > $D/${R}_pass_loads_ab.json 2> $D/pass_lo
 gcc -std=c11 -O2 -ffp-contract=off -fPIC -shared -fvisibility=hidden -Iinclude tests/c/gyroid_provider.c -o /tmp/libgyroid_provider.so -lm
 { python tools/source_hash.py --stamp; for t in 1 4 16 32; do ./sdf-viewer_amd/sdf-viewer-host-bench --ingest /tmp/libgyroid_provider.so --side 384 --threads $t 2>&1 | grep -v Using; done; } > $D/${R}_ingest_bench.txt 2>&1
 SDFV_BENCH_FORCE_MULTI=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29655 SDFV_BENCH_FULL_JSON=$D/bench_rccl_loopback_256_full.json \
-  python bench.py --gpus 1 --no-cpu-baseline > $D/bench_rccl_loopback_256.json 2> $D/loopback.err
+  python bench.py --full --gpus 1 --no-cpu-baseline > $D/bench_rccl_loopback_256.json 2> $D/loopback.err
 (rocm-smi --showclocks --showuniqueid 2>&1 | grep -i "sclk\|mclk\|fclk\|unique") > $D/box_after.txt
 tail -3 $D/full_workload_parity.txt
