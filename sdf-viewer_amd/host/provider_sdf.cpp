@@ -43,6 +43,14 @@ template <typename F>
 void resolve(void* handle, const char* symbol, F& out) {
     out = reinterpret_cast<F>(dlsym(handle, symbol));
 }
+// An optional export: dlsym(handle, ...) searches the library's whole dependency tree, and these names are generic (init, name,
+// normal, ...).  A symbol counts only if it lies in the same object as the library's `sample`; one found in a dependency is absent.
+template <typename F>
+void resolve_own(void* handle, const char* symbol, const void* own_base, F& out) {
+    resolve(handle, symbol, out);
+    Dl_info info;
+    if (out && !(dladdr(reinterpret_cast<void*>(out), &info) != 0 && info.dli_fbase == own_base)) out = nullptr;
+}
 std::string pl_string(const PointerLength& p) {
     return p.ptr ? std::string(static_cast<const char*>(p.ptr), p.len_bytes) : std::string();
 }
@@ -63,24 +71,26 @@ std::shared_ptr<ProviderSDF> ProviderSDF::load(const std::string& path, std::str
         if (error) *error = std::string("SDF provider '") + path + "' does not export " + (lib->f_bounding_box ? "sample" : "bounding_box");
         return nullptr;
     }
-    resolve(h, "bounding_box_free", lib->f_bounding_box_free);
-    resolve(h, "sample_free", lib->f_sample_free);
-    resolve(h, "children", lib->f_children);
-    resolve(h, "children_free", lib->f_children_free);
-    resolve(h, "name", lib->f_name);
-    resolve(h, "name_free", lib->f_name_free);
-    resolve(h, "parameters", lib->f_parameters);
-    resolve(h, "parameters_free", lib->f_parameters_free);
-    resolve(h, "set_parameter", lib->f_set_parameter);
-    resolve(h, "set_parameter_free", lib->f_set_parameter_free);
-    resolve(h, "changed", lib->f_changed);
-    resolve(h, "changed_free", lib->f_changed_free);
-    resolve(h, "normal", lib->f_normal);
-    resolve(h, "normal_free", lib->f_normal_free);
-    resolve(h, "sample_concurrency", lib->f_sample_concurrency);
-    resolve(h, "sample_batch", lib->f_sample_batch);
+    Dl_info own;
+    const void* base = dladdr(reinterpret_cast<void*>(lib->f_sample), &own) != 0 ? own.dli_fbase : nullptr;
+    resolve_own(h, "bounding_box_free", base, lib->f_bounding_box_free);
+    resolve_own(h, "sample_free", base, lib->f_sample_free);
+    resolve_own(h, "children", base, lib->f_children);
+    resolve_own(h, "children_free", base, lib->f_children_free);
+    resolve_own(h, "name", base, lib->f_name);
+    resolve_own(h, "name_free", base, lib->f_name_free);
+    resolve_own(h, "parameters", base, lib->f_parameters);
+    resolve_own(h, "parameters_free", base, lib->f_parameters_free);
+    resolve_own(h, "set_parameter", base, lib->f_set_parameter);
+    resolve_own(h, "set_parameter_free", base, lib->f_set_parameter_free);
+    resolve_own(h, "changed", base, lib->f_changed);
+    resolve_own(h, "changed_free", base, lib->f_changed_free);
+    resolve_own(h, "normal", base, lib->f_normal);
+    resolve_own(h, "normal_free", base, lib->f_normal_free);
+    resolve_own(h, "sample_concurrency", base, lib->f_sample_concurrency);
+    resolve_own(h, "sample_batch", base, lib->f_sample_batch);
     void (*f_init)(void) = nullptr;
-    resolve(h, "init", f_init);  // "Call init() to initialize the module (optional)", native.rs:51-56
+    resolve_own(h, "init", base, f_init);  // "Call init() to initialize the module (optional)", native.rs:51-56
     if (f_init) f_init();
     return std::shared_ptr<ProviderSDF>(new ProviderSDF(std::move(lib), 0));  // the root SDF is id 0 (native.rs:78)
 }

@@ -109,8 +109,12 @@ class SDFViewer {
     // launch).  ANY other SDFSurface (a ProviderSDF, an application's own class): the ingest path -- sample() runs on the
     // host, on sample_concurrency() threads, run after run of the LoadingManager's order until the budget is spent (at least
     // one voxel, like the reference); the raw 28-byte samples go to the device through pinned double buffers and
-    // sdfv_pack_samples does update()'s packing there.  update_required is decided on a host mirror of tex0.r.  (sample() is
-    // the caller's code: an exception it throws on a worker thread ends the process, as a panic ends the reference's loop.)
+    // sdfv_pack_samples does update()'s packing there.  update_required is decided on a host mirror of tex0.r.  The budget
+    // holds to within one gather of samples (2048 sample() calls on one thread) whatever sample() costs: runs are sized for
+    // the worst cost seen, and the workers stop at the first gather boundary past the deadline.  (sample() is the caller's
+    // code: an exception it throws on the calling thread propagates out of update() once the run's workers have stopped --
+    // that run is dropped and a later call samples it again; one thrown on a worker thread ends the process, as a panic ends
+    // the reference's loop.)
     size_t update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time);
     // Ingest path knobs: host threads (0 = what the SDF allows, at most the machine's), records per transfer buffer (0 = 16 Ki
     // per thread, between 64 Ki and 4 Mi: a run must outlast the fork/join of its workers by far; 32 B of pinned memory each).

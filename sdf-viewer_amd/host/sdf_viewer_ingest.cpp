@@ -11,14 +11,20 @@
 //     volume when the device path has written the grid in between) -- never the device textures;
 //   - a finished run is copied to the device (async, the viewer's stream) and sdfv_pack_samples packs it into tex0 / tex1 /
 //     the distance volume while the workers sample the next run into the other buffer;
-//   - the time budget is honoured between runs: the first run is one voxel per worker ("performs at least one update"),
-//     every further run is sized from the measured rate to end within half of what is left.
+//   - the time budget: the first run is one voxel per worker ("performs at least one update"), every further run is sized to
+//     end within half of what is left even if every voxel of it needs a sample (at the largest per-sample cost seen for this
+//     SDF), and the workers check the deadline once per gather (kGather samples): a worker stops at the first gather boundary
+//     past it and the run is cut to its longest complete prefix.  A call therefore ends within the budget plus one gather
+//     (plus the time of one fork/join and one ship), whatever the cost per sample and however it varies over the grid.
 // The set of voxels visited by a call is a prefix of the LoadingManager's remaining order, and the return value counts
-// them, exactly as in the reference.
+// them, exactly as in the reference.  A sample() that throws on the calling thread leaves nothing behind that the device did
+// not receive: the exception propagates once the run's workers have stopped, the LoadingManager is not advanced past what
+// was shipped, and the host mirror is rebuilt from the device by the next call.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cstring>
+#include <exception>
 #include <thread>
 #include <vector>
 
@@ -31,6 +37,10 @@ namespace {
 
 // f32::clamp(0.0, 1.0) of scene/sdf/mod.rs:196 (a NaN stays a NaN), the same three lines the device packs with
 inline float clamp01_rust(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
+
+// The voxels update_required lets through are gathered kGather at a time and sampled with ONE sample_batch call; the workers
+// look at the clock once per gather.
+constexpr size_t kGather = 2048;
 
 }  // namespace
 
@@ -48,6 +58,9 @@ struct SDFViewer::Ingest {
     int next = 0;
     std::vector<float> mirror;     // tex0.r of every voxel, texture order
     std::vector<float> coords[3];  // the voxels' coordinates per axis (scene/sdf/mod.rs:179-182)
+    std::vector<float> journal;    // changed-box runs: the mirror entry each record overwrote (a run cut short restores them)
+    const SDFSurface* cost_sdf = nullptr;  // the SDF record_cost was measured on
+    double record_cost = 0.0;      // ... its largest cost per sample on one thread (s), from runs of >= kGather samples per worker
     WorkerPool pool;
 
     ~Ingest() { release(); }
@@ -175,16 +188,24 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
     float* dist_dev = dist_synced_ ? material.dist->f32() : nullptr;
     const bool has_box = changed_box.has_value();
     const BoundingBox box = has_box ? *changed_box : BoundingBox{};
+    if (has_box) in.journal.resize(in.capacity);  // (a run without a box only samples voxels whose mirror entry is AIR)
+    if (in.cost_sdf != &sdf) {
+        in.cost_sdf = &sdf;
+        in.record_cost = 0.0;
+    }
+    const auto deadline = max_delta_time < std::chrono::hours(24 * 365) ? start_time + max_delta_time
+                                                                        : std::chrono::steady_clock::time_point::max();
 
     // A run that has been sampled into its buffer.
     struct Run {
         Ingest::Buffer* b = nullptr;
         size_t n = 0;
         unsigned workers = 0;
-        std::vector<size_t> counts;
+        std::vector<size_t> counts;   // records per worker
+        std::vector<size_t> visited;  // voxels per worker: its whole stretch, or up to the gather after which it met the deadline
     };
     Run runs[2];
-    for (auto& r : runs) r.counts.resize(threads);
+    for (auto& r : runs) r.counts.resize(threads), r.visited.resize(threads);
     bool failed = false;
     // Ship a run: the workers' stretches packed back to back on the device (full adjacent stretches in one copy), one launch.
     auto ship = [&](Run& r) {
@@ -256,14 +277,14 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
             const size_t lo = n * t / workers, hi = n * (t + 1) / workers;  // this worker's stretch of the run (and of the buffer)
             sdfv_sample* out_s = b.samples + lo;
             uint32_t* out_i = b.indices + lo;
-            size_t count = 0;
+            float* out_old = has_box ? in.journal.data() + lo : nullptr;
+            size_t count = 0, end = hi;
             size_t k = c0 + lo;
             size_t kx = k % walk[0], ky = k / walk[0] % walk[1], kz = k / (walk[0] * walk[1]);
             // The voxels update_required lets through are gathered kGather at a time and sampled with ONE sample_batch call
             // (src/sdf/mod.rs:39's "Batched sampling"; for an SDF that does not override it, the loop of sample() calls it
             // stands for), straight into the pinned records.  A run lies within one pass, so no voxel is visited twice in it:
-            // the mirror may be brought up to date after the batch.
-            constexpr size_t kGather = 2048;
+            // the mirror may be brought up to date after the batch (a record that the run's cut drops is taken back below).
             Vec3 pos_buf[kGather];
             size_t m = 0;
             auto flush = [&] {
@@ -280,14 +301,22 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
                 const size_t flat = (z * H + y) * W + x;  // :177
                 const Vec3 pos{in.coords[0][x], in.coords[1][y], in.coords[2][z]};
                 // Check if the update is required: was AIR on initial load, or has changed since.  (:184-190)
-                bool update_required = in.mirror[flat] == air;
+                const float cur = in.mirror[flat];
+                bool update_required = cur == air;
                 if (has_box)
                     update_required = update_required || (pos.x >= box[0].x && pos.x <= box[1].x && pos.y >= box[0].y &&
                                                           pos.y <= box[1].y && pos.z >= box[0].z && pos.z <= box[1].z);
                 if (update_required) {
                     pos_buf[m] = pos;
                     out_i[count + m] = (uint32_t)flat;
-                    if (++m == kGather) flush();
+                    if (has_box) out_old[count + m] = cur;
+                    if (++m == kGather) {
+                        flush();
+                        if (std::chrono::steady_clock::now() >= deadline) {  // (the budget is spent: the rest of the stretch waits)
+                            end = i + 1;
+                            break;
+                        }
+                    }
                 }
                 if (++kx == walk[0]) {
                     kx = 0;
@@ -299,20 +328,56 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
             }
             flush();
             run.counts[t] = count;
+            run.visited[t] = end - lo;
         };
-        if (workers > 1) in.pool.run(workers, sample_stretch);
-        else sample_stretch(0);
+        try {
+            if (workers > 1) in.pool.run(workers, sample_stretch);
+            else sample_stretch(0);
+        } catch (...) {
+            // sample() threw on this thread (WorkerPool::run returns only once the other workers are done): this run is not
+            // shipped and the LoadingManager stays where it is, but the mirror already holds some of its samples
+            host_mirror_valid_ = false;
+            error_ = "ingest: the SDF's sample() threw";
+            try {
+                throw;
+            } catch (const std::exception& e) {
+                error_ += std::string(": ") + e.what();
+            } catch (...) {
+            }
+            throw;
+        }
         ingest_stats.sample += std::chrono::duration<double>(std::chrono::steady_clock::now() - run_start).count();
+        // ---- the run's complete prefix: every stretch up to the first one whose worker met the deadline, and what that one visited
+        size_t visited = 0, sampled = 0, least = ~(size_t)0;
+        unsigned cut = workers;
+        for (unsigned t = 0; t < workers; ++t) {
+            sampled += run.counts[t];
+            least = std::min(least, run.counts[t]);
+            if (cut == workers) {
+                visited += run.visited[t];
+                if (run.visited[t] < n * (t + 1) / workers - n * t / workers) cut = t;
+            }
+        }
+        for (unsigned t = cut + 1; t < workers; ++t) {  // sampled beyond the prefix: neither shipped nor kept in the mirror
+            const size_t lo = n * t / workers;
+            for (size_t j = 0; j < run.counts[t]; ++j) in.mirror[b.indices[lo + j]] = has_box ? in.journal[lo + j] : air;
+            run.counts[t] = 0;
+        }
         ship(run);
         if (failed) break;
-        loading_mgr.advance(n);
+        loading_mgr.advance(visited);
         if (loading_mgr.step_size() == 0) loaded_once_ = true;
         publish_lod();
         ingest_stats.runs += 1;
-        ingest_stats.visited += n;
-        // ---- the next run: sized to end within half of the budget that is left, growing by at most 8x ----
+        ingest_stats.visited += visited;
+        // ---- the next run: sized to end within half of the budget that is left even if every voxel of it needs a sample, at
+        // the largest cost per sample seen for this SDF (a cheap stretch -- skips, a cheap region -- says nothing about the
+        // next one); growing by at most 8x ----
         const auto now = std::chrono::steady_clock::now();
-        const double per_voxel = std::chrono::duration<double>(now - run_start).count() / (double)n;
+        const double took = std::chrono::duration<double>(now - run_start).count();
+        const double record_cost = sampled ? took * workers / (double)sampled : 0.0;  // one thread's time per sample, this run
+        if (least >= kGather) in.record_cost = std::max(in.record_cost, record_cost);  // (long enough to be more than overhead)
+        const double per_voxel = std::max({took / (double)visited, record_cost / threads, in.record_cost / threads});
         const double left = std::chrono::duration<double>(max_delta_time - (now - start_time)).count();
         double want = per_voxel > 0.0 ? 0.5 * left / per_voxel : (double)in.capacity;
         want = std::min(want, 8.0 * (double)n);

@@ -17,7 +17,8 @@ namespace sdfviewer {
 
 // Persistent workers.  A SESSION spans one update() call: begin() wakes the background threads (condition variable, once),
 // run(n, fn) -- any number of times -- calls fn(0) on the calling thread and fn(1) .. fn(n - 1) on background threads and
-// returns when all are done, end() parks them again.  Inside a session the workers SPIN on a generation counter between runs:
+// returns when all are done (also when fn(0) throws: the exception leaves run() after the workers have finished), end() parks
+// them again.  Inside a session the workers SPIN on a generation counter between runs:
 // a run lasts a fraction of a millisecond, and waking 63 threads through one mutex costs about as much (measured on a
 // 2 x 64-core host: 64 workers reached 25 % of their single-thread rate with a condition variable per run).
 // One caller at a time (begin / run / end are the owning viewer's, which is single-owner like everything behind the C ABI).
@@ -58,14 +59,15 @@ class WorkerPool {
         // load that told it about the run (a bystander that is slow to look may skip runs, a participant cannot: the caller waits)
         sequence_ += 1;
         generation_.store(sequence_ << 16 | n, std::memory_order_release);
-        fn(0);
-        // the caller's own share may be much shorter than the workers' (it ships while they sample): spin briefly, then SLEEP --
-        // a yielding spin still burns a CPU's worth of a cgroup quota the workers need
-        for (unsigned spins = 0; spins < 256 && pending_.load(std::memory_order_acquire) != 0; ++spins) __builtin_ia32_pause();
-        if (pending_.load(std::memory_order_acquire) != 0) {
-            std::unique_lock<std::mutex> lock(done_m_);
-            done_.wait(lock, [this] { return pending_.load(std::memory_order_acquire) == 0; });
+        // fn(0) may throw (an SDF's sample() is the caller's code): the workers run *fn_ over the caller's frame, so the
+        // exception may only leave once every one of them is done
+        try {
+            fn(0);
+        } catch (...) {
+            wait_workers();
+            throw;
         }
+        wait_workers();
     }
     // CPUs this process may actually use at once: the machine's hardware threads, cut down to the scheduler affinity mask and
     // to a cgroup CPU quota (cpu.max: a container limited to 16 CPUs' worth of time on a 256-thread host reports 256 hardware
@@ -74,6 +76,15 @@ class WorkerPool {
     static unsigned probe_usable_cpus();
 
    private:
+    // the caller's own share may be much shorter than the workers' (it ships while they sample): spin briefly, then SLEEP --
+    // a yielding spin still burns a CPU's worth of a cgroup quota the workers need
+    void wait_workers() {
+        for (unsigned spins = 0; spins < 256 && pending_.load(std::memory_order_acquire) != 0; ++spins) __builtin_ia32_pause();
+        if (pending_.load(std::memory_order_acquire) != 0) {
+            std::unique_lock<std::mutex> lock(done_m_);
+            done_.wait(lock, [this] { return pending_.load(std::memory_order_acquire) == 0; });
+        }
+    }
     void loop(unsigned id, unsigned long long seen) {
         for (;;) {
             {

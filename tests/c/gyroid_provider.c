@@ -6,6 +6,10 @@
  * gyroid_sample_raw is the same function with the oracle's callback signature (oracle/sdf_oracle.h or_sample_fn), so that
  * the oracle's update loop and the product's ingest path are fed the same samples.
  * Not the reference's code: a gyroid shell with a procedural colour, written for these tests. */
+#ifdef GYROID_COST_NS
+#define _POSIX_C_SOURCE 199309L /* clock_gettime under -std=c11 */
+#include <time.h>
+#endif
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -40,6 +44,23 @@ static void gyroid(const float p[3], int distance_only, float out[7]) {
     out[6] = p[0] > 0.25f ? 0.0f : (p[0] < -0.25f ? -1.0f : 0.6f); /* occlusion: <= 0 becomes 1 */
 }
 
+/* -DGYROID_COST_NS=<n>: the exported sample() / sample_batch() spin on the wall clock for n ns per point in the upper third of
+ * the box (p.z > 0.25) -- a provider whose cost per sample jumps mid-pass.  The values do not change, and gyroid_sample_raw (the
+ * oracle's feed) stays free of any cost. */
+#ifdef GYROID_COST_NS
+static void cost(SDFVec3 p) {
+    if (!(p.z > 0.25f)) return;
+    struct timespec t0, t;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    do {
+        clock_gettime(CLOCK_MONOTONIC, &t);
+    } while ((long long)(t.tv_sec - t0.tv_sec) * 1000000000LL + (t.tv_nsec - t0.tv_nsec) < (long long)(GYROID_COST_NS));
+}
+#define GYROID_COST(p) cost(p)
+#else
+#define GYROID_COST(p) ((void)0)
+#endif
+
 EXPORT void gyroid_sample_raw(void *user, const float p[3], int distance_only, float out[7]) {
     (void)user;
     gyroid(p, distance_only, out);
@@ -54,6 +75,7 @@ EXPORT void bounding_box_free(SDFBoundingBox *ret) { free(ret); }
 
 EXPORT SDFSample *sample(uint32_t sdf_id, SDFVec3 p, bool distance_only) {
     SDFSample *ret = (SDFSample *)calloc(1, sizeof *ret);
+    GYROID_COST(p);
     if (sdf_id == 0) {
         const float q[3] = {p.x, p.y, p.z};
         gyroid(q, distance_only, (float *)ret);
@@ -67,6 +89,7 @@ EXPORT void sample_free(SDFSample *ret) { free(ret); }
 #ifdef GYROID_BATCH
 EXPORT void sample_batch(uint32_t sdf_id, const SDFVec3 *points, size_t n, bool distance_only, SDFSample *out) {
     for (size_t i = 0; i < n; ++i) {
+        GYROID_COST(points[i]);
         if (sdf_id == 0) {
             const float q[3] = {points[i].x, points[i].y, points[i].z};
             gyroid(q, distance_only, (float *)&out[i]);
@@ -132,15 +155,20 @@ EXPORT void set_parameter_free(SDFSetParameterResult *ret) {
     free(ret);
 }
 
-/* an edit reports the lower-x part of the box once (a box that does NOT cover the grid: update_required mixes both tests) */
+/* an edit reports the lower-x part of the box once (a box that does NOT cover the grid: update_required mixes both tests);
+ * -DGYROID_EDIT_HIGH_Z: the box z in [0.25, 0.75] instead (every voxel of a pass outside it -- a skip -- comes before it) */
 EXPORT SDFChangedResult *changed(uint32_t sdf_id) {
     SDFChangedResult *ret = (SDFChangedResult *)calloc(1, sizeof *ret);
     if (sdf_id == 0 && g_changed) {
         g_changed = 0;
         ret->tag = 1;
         ret->bounds = k_bounds;
+#ifdef GYROID_EDIT_HIGH_Z
+        ret->bounds.min.z = 0.25f;
+#else
         ret->bounds.max.x = 0.1f;
         ret->bounds.min.y = -0.3f;
+#endif
     }
     return ret;
 }

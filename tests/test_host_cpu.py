@@ -429,3 +429,44 @@ def test_batched_sampling_equals_the_per_point_loop(host, gyroid_provider, gyroi
             got = sdf.sample_batch(pts, distance_only)
             assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
     assert batch.sample_batch(np.zeros((0, 3), np.float32)).shape == (0, 7)
+
+
+def test_worker_pool_run_waits_for_its_workers_when_the_caller_throws(tmp_path):
+    """WorkerPool::run (host/worker_pool.hpp) with fn(0) throwing on the calling thread -- an SDF's sample() is the caller's code:
+    the exception reaches the caller only after every background worker of the run has finished (they run over the caller's
+    frame), and the pool then serves further sessions and runs (every worker id exactly once) and shuts down cleanly."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "worker_pool_throw"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-Wall", "-Werror", "-I", os.path.join(root, "sdf-viewer_amd", "host"),
+                           os.path.join(root, "tests", "c", "worker_pool_throw.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.startswith("ok"), (r.returncode, r.stdout, r.stderr)
+
+
+def test_provider_optional_exports_never_bind_to_a_dependency(host, tmp_path):
+    """dlsym(handle, ...) searches a provider's whole dependency tree.  A provider that lacks the optional exports init / name /
+    normal / children / sample_concurrency but links a library that exports those names must still get the trait's defaults
+    (wasm/native.rs:51-56,219-281,494-500), and the dependency's init() must not run."""
+    import ctypes as C
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cflags = ["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall", "-Wextra", "-Werror",
+              "-I", os.path.join(root, "include")]
+    dep = tmp_path / "libdep_exports.so"
+    subprocess.check_call(cflags + [os.path.join(root, "tests", "c", "dep_exports.c"), "-o", str(dep)])
+    lib = tmp_path / "libbare_provider.so"
+    subprocess.check_call(cflags + [os.path.join(root, "tests", "c", "bare_provider.c"), "-o", str(lib), "-L", str(tmp_path),
+                                    "-Wl,--no-as-needed", "-ldep_exports", "-Wl,-rpath," + str(tmp_path)])
+    sdf = host.SDF.provider(lib)
+    dep_lib = C.CDLL(str(dep))                          # the instance the provider loaded (same path, already mapped)
+    assert dep_lib.dep_init_calls() == 0                # the dependency's init() was not taken for the provider's
+    assert sdf.name() == "Object"                       # name_default_impl, as for the gyroid fixture without `name`
+    assert sdf.children() == []
+    assert np.array_equal(sdf.normal([0.1, 0.2, 0.3], 0.001), np.zeros(3, np.float32))  # no `normal` export: zero (native.rs:498)
+    assert sdf.sample_concurrency() == 1                # no `sample_concurrency` export
+    assert np.array_equal(sdf.bounding_box(), np.float32([-1, -1, -1, 1, 1, 1]))
+    assert sdf.sample([0.5, 0.0, 0.0])[0] == np.float32(0.0)   # the provider's own required exports still answer
+    assert dep_lib.dep_init_calls() == 0
