@@ -355,6 +355,28 @@ int sdfv_fill_grid_pass_ex(const sdfv_demo_params *params, uint32_t sdf_id, cons
 int sdfv_pack_samples(const sdfv_grid *grid, uint64_t index_base, const uint32_t *indices, const sdfv_sample *samples, size_t n,
                       float *tex0, float *tex1, float *dist, uint32_t flags, void *stream);
 
+/* ---- device-sampled loads: SDFViewer::update for an SDF that the CALLER evaluates on the device (include/sdfviewer.h,
+ * sdfv_surface.sample_batch_device) ----
+ * The first half of the loop (scene/sdf/mod.rs:173-190) for a RUN of consecutive LoadingManager points of one pass, on the
+ * device: the points [cursor, cursor + n) of the pass with lattice spacing `step` (x fastest, then y, then z: point k is
+ * (k % nx, k / nx % ny, k / (nx * ny)) * step with n_a = ceil(dim_a / step)), their positions (idx / (dim - 1) * size + min,
+ * three separately rounded steps) and update_required (tex0.r == AIR_DIST, or the position inside changed_box).  The points
+ * that need a sample are written in LoadingManager order:
+ *   points      DEVICE, up to n x 3 floats: the positions, what the caller's sample_batch_device evaluates
+ *   indices     DEVICE, up to n uint32: their flat indices (z * H + y) * W + x, what sdfv_pack_samples stores the samples through
+ *   count       DEVICE, one uint32: how many were written (the entries beyond it are undefined)
+ *   dist        DEVICE: the grid's distance volume (equal to tex0.r everywhere, sdfv_fill_grid_commit / sdfv_commit_distance /
+ *               sdfv_pack_samples keep it so; a virgin grid needs sdfv_grid_init_unvisited first), SDFV_PASS_VOLUME_INTERLEAVED in
+ *               `flags` when it has that layout (the only flag)
+ *   changed_box HOST, 6 floats min.xyz max.xyz, or NULL
+ *   scratch     DEVICE, at least sdfv_emit_update_points_scratch_bytes(n) bytes, not shared with a call in flight
+ * The grid is a whole grid (z_begin 0, z_end D) of at most 2^32 voxels; the run lies within the pass and holds at most 2^32 - 1
+ * points.  Enqueues two launches. */
+size_t sdfv_emit_update_points_scratch_bytes(uint64_t n);
+int sdfv_emit_update_points(const sdfv_grid *grid, uint32_t step, uint64_t cursor, uint64_t n, const float *changed_box,
+                            const float *dist, uint32_t flags, float *points, uint32_t *indices, uint32_t *count, void *scratch,
+                            size_t scratch_bytes, void *stream);
+
 /* ---- batched point sampling (the "Batched sampling" TODO, src/sdf/mod.rs:39) ---- */
 /* points: DEVICE, n x 3 floats.  out: DEVICE, n x sdfv_sample.  SDFSurface::sample(p, distance_only). */
 int sdfv_sample_points(const sdfv_demo_params *params, uint32_t sdf_id, const float *points, size_t n,

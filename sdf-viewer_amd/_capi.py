@@ -102,6 +102,9 @@ PROTOTYPES = {
                                  C.c_void_p]),
     "sdfv_pack_samples": (C.c_int, [C.POINTER(Grid), C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_uint32, C.c_void_p]),
+    "sdfv_emit_update_points_scratch_bytes": (C.c_size_t, [C.c_uint64]),
+    "sdfv_emit_update_points": (C.c_int, [C.POINTER(Grid), C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_float), C.c_void_p,
+                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sdfv_fill_grid_commit": (C.c_int, [C.POINTER(DemoParams), C.c_uint32, C.POINTER(Grid), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
     "sdfv_fill_grid_pass_ex": (C.c_int, [C.POINTER(DemoParams), C.c_uint32, C.POINTER(Grid), C.c_uint32,

@@ -126,6 +126,20 @@ class SDFSurface {
     // ============ batched / device evaluation (not in the reference) ============
     // nullopt = this SDF can only be sampled point by point on the host (e.g. a wasm provider).
     virtual std::optional<DeviceSDF> device_sdf() const { return std::nullopt; }
+
+    // ============ added after the reference's trait (kept last: the slots above keep their vtable positions) ============
+    // (a C++ host that derives from SDFSurface and was compiled against a header without these must be rebuilt)
+    // Called by SDFViewer::update on its own thread once the workers of a run are done and before the run is shipped.  An SDF
+    // whose sample() can fail on a worker thread (where an exception ends the process) records the failure there and throws
+    // it here: the run is then dropped like one whose sample() threw on the calling thread.
+    virtual void check_samples() const {}
+
+    // ============ device sampling by the caller (not in the reference) ============
+    // An SDF that the application evaluates on the GPU itself: out_dev[i] = sample(points_dev[i], false) for i in [0, n), with
+    // points_dev (n x 3 floats) and out_dev (n records) in device memory, ENQUEUED on `stream` (hipStream_t) without
+    // synchronising.  SDFViewer::update then runs the reference's loop on the device (sdf_viewer_device.cpp).  A failure throws.
+    virtual bool has_device_sampler() const { return false; }
+    virtual void sample_batch_device(const float* /*points_dev*/, size_t /*n*/, sdfv_sample* /*out_dev*/, void* /*stream*/) const {}
 };
 
 // merge_bounding_boxes, defaults.rs:59-72

@@ -175,6 +175,7 @@ sdfv_grid SDFViewer::grid() const {
 
 size_t SDFViewer::update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time) {
     error_.clear();  // last_error() describes THIS call
+    visited_before_throw_ = 0;
     // Check whether the SDF self-reports updates.  (:130-141)
     bool just_changed_box = false;
     // the passes of ONE load share one SDF and one set of parameters: a different device SDF (or parameter block) than the
@@ -204,6 +205,7 @@ size_t SDFViewer::update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_tim
 
     const size_t start_iter = loading_mgr.total_iterations();
     const auto dev = sdf.device_sdf();
+    if (!dev && sdf.has_device_sampler()) return update_device(sdf, max_delta_time);  // sampled by the caller's kernel
     if (!dev) return update_host(sdf, max_delta_time);  // any `impl SDFSurface`: sampled on the host, packed on the device
     host_mirror_valid_ = false;  // (whatever runs below rewrites tex0.r on the device)
     const sdfv_grid g = grid();

@@ -115,6 +115,11 @@ class SDFViewer {
     // code: an exception it throws on the calling thread propagates out of update() once the run's workers have stopped --
     // that run is dropped and a later call samples it again; one thrown on a worker thread ends the process, as a panic ends
     // the reference's loop.)
+    // An SDF the application samples on the device itself (has_device_sampler(), no device_sdf()): the same loop with its first
+    // half on the device too -- per run, sdfv_emit_update_points writes out the points update_required lets through,
+    // sample_batch_device samples them and sdfv_pack_samples packs them; the budget is checked between runs, each timed to its
+    // end (none is left in flight) and sized as on the ingest path, for the largest cost per sample seen.  A sample_batch_device that throws: that run is dropped (nothing of it reaches the textures), the
+    // exception propagates and a later call samples the run again.
     size_t update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time);
     // Ingest path knobs: host threads (0 = what the SDF allows, at most the machine's), records per transfer buffer (0 = 16 Ki
     // per thread, between 64 Ki and 4 Mi: a run must outlast the fork/join of its workers by far; 32 B of pinned memory each).
@@ -136,6 +141,8 @@ class SDFViewer {
     float* tex1_device() const { return material.tex1->f32(); }
     int download(float* tex0_host, float* tex1_host) const;  // D2H copy of both textures (debug / GL interop)
     const char* last_error() const { return error_.c_str(); }  // of the most recent update(): "" when it went through
+    // An update() that threw: the LoadingManager iterations it had consumed (and packed) before the run that failed.
+    size_t visited_before_throw() const { return visited_before_throw_; }
 
     SDFViewerMaterial material;      // volume.material
     LoadingManager loading_mgr;
@@ -147,6 +154,11 @@ class SDFViewer {
    private:
     SDFViewer(std::array<size_t, 3> voxels, const BoundingBox& bb, size_t passes);
     size_t update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time);  // sdf_viewer_ingest.cpp
+    size_t update_device(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time);  // sdf_viewer_device.cpp
+    struct DeviceRuns;  // the device-sampled path's buffers (points, indices, samples, count, scan scratch)
+    struct DeviceRunsDeleter {
+        void operator()(DeviceRuns* p) const;
+    };
     struct Ingest;  // pinned / device transfer buffers, the host mirror of tex0.r, the worker threads
     struct IngestDeleter {
         void operator()(Ingest* p) const;
@@ -160,6 +172,9 @@ class SDFViewer {
     std::optional<DeviceSDF> load_sdf_;  // what that load samples
     bool dist_synced_ = false;  // material.dist exists and mirrors tex0.r (kept so by every fill)
     std::shared_ptr<DeviceBuffer> block_;  // owns tex0 and tex1 when they share one allocation
+    // (added last: the members above keep their offsets)
+    std::unique_ptr<DeviceRuns, DeviceRunsDeleter> device_runs_;  // created by the first update() with a device sampler
+    size_t visited_before_throw_ = 0;
 };
 
 }  // namespace sdfviewer

@@ -333,10 +333,12 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
         try {
             if (workers > 1) in.pool.run(workers, sample_stretch);
             else sample_stretch(0);
+            sdf.check_samples();
         } catch (...) {
             // sample() threw on this thread (WorkerPool::run returns only once the other workers are done): this run is not
             // shipped and the LoadingManager stays where it is, but the mirror already holds some of its samples
             host_mirror_valid_ = false;
+            visited_before_throw_ = loading_mgr.total_iterations() - start_iter;
             error_ = "ingest: the SDF's sample() threw";
             try {
                 throw;
