@@ -39,7 +39,8 @@ extern "C" {
  * sdfv_grid_init_unvisited, SDFV_OPT_EXT_SRGB_QUANT, SDFV_OPT_PASS_INDEX_LIMIT, sdfv_bands_scatter and the sdfv_comm_* collectives.
  * The descriptor is size-prefixed: further layouts / outputs are new fields, not new versions. */
 /* 5 (round 6): added sdfv_pack_samples (the device half of SDFViewer::update for host-sampled SDFs); removed
- * sdfv_tune_texture_placement / SDFV_PLACEMENT_SLACK (a probe that never beat the fixed placement in the driver's runs). */
+ * sdfv_tune_texture_placement / SDFV_PLACEMENT_SLACK (a probe that never beat the fixed placement in the driver's runs).
+ * Still 5: the SDF programs (sdfv_prog_op, sdfv_program_*) are additions only -- nothing that existed changed meaning. */
 #define SDFV_ABI_VERSION 5
 
 typedef enum sdfv_status {
@@ -376,6 +377,91 @@ size_t sdfv_emit_update_points_scratch_bytes(uint64_t n);
 int sdfv_emit_update_points(const sdfv_grid *grid, uint32_t step, uint64_t cursor, uint64_t n, const float *changed_box,
                             const float *dist, uint32_t flags, float *points, uint32_t *indices, uint32_t *count, void *scratch,
                             size_t scratch_bytes, void *stream);
+
+/* ---- SDF programs: a caller-defined CSG tree, handed over as DATA and evaluated on the device ----
+ * The reference loads arbitrary SDFs as wasm (src/sdf/wasm/); a GPU cannot run that.  A program describes a model as primitives
+ * + CSG + transforms + materials: a flat array of fixed-size instructions that a stack machine runs once per point.
+ *
+ * Machine state per point p: the current point q (= p at the start); the frame stack (saved points, at most
+ * SDFV_PROGRAM_MAX_FRAMES); the current material (starts as colour 0,0,0, metallic 0, roughness 0, occlusion 0 =
+ * SDFSample::new(d, 0), src/sdf/mod.rs:120-126; the viewer's packing applies the reference's grey / occlusion rules to it as to
+ * any sample); the value stack (at most SDFV_PROGRAM_MAX_VALUES samples = distance + material).  A valid program ends with
+ * exactly one value, the result, and no open frame.
+ *
+ * Arithmetic: IEEE f32, every step rounded on its own (nothing contracted), evaluated left to right as written:
+ * a*x + b*y + c*z + d is ((a*x + b*y) + c*z) + d.  Only + - * / sqrt |x| and compares occur, so the device, the host mirror
+ * (host/program_sdf.cpp) and any restatement agree bit for bit.  Operands are finite.  min(a, b) is `b < a ? b : a` and
+ * max(a, b) is `a < b ? b : a`: fminf / fmaxf for finite operands, with the sign of a zero result pinned.  len(x, y, z) is
+ * sqrt(x*x + y*y + z*z); q = (x, y, z); a[] are the instruction's operands, unused ones must be finite (0).
+ *
+ *   primitives: push {d, current material}
+ *     SDFV_OP_SPHERE    a = r             d = len(x, y, z) - r                                      (the demo sphere, sphere.rs:39)
+ *     SDFV_OP_CUBE      a = h             d = max(max(|x|, |y|), |z|) - h                           (the demo cube, cube.rs:81)
+ *     SDFV_OP_BOX       a = hx hy hz      e = |q| - h per axis; d = len(max(e.x, 0), max(e.y, 0), max(e.z, 0))
+ *                                             + min(max(e.x, max(e.y, e.z)), 0)
+ *     SDFV_OP_CYLINDER  a = r hh          axis z: dx = sqrt(x*x + y*y) - r, dz = |z| - hh, mx = max(dx, 0), mz = max(dz, 0);
+ *                                         d = min(max(dx, dz), 0) + sqrt(mx*mx + mz*mz)
+ *     SDFV_OP_TORUS     a = R r           u = sqrt(x*x + y*y) - R; d = sqrt(u*u + z*z) - r
+ *     SDFV_OP_PLANE     a = nx ny nz d0   d = nx*x + ny*y + nz*z + d0
+ *   frames
+ *     SDFV_OP_PUSH_AFFINE a = m[12]       save q; q'_i = m[4i]*x + m[4i+1]*y + m[4i+2]*z + m[4i+3], i = 0, 1, 2 (the caller passes
+ *                                         the INVERSE of the rigid transform that places what follows)
+ *     SDFV_OP_PUSH_SCALE  a = s inv_s     save q; q' = q * inv_s per axis (s > 0, inv_s > 0: the caller's 1 / s)
+ *     SDFV_OP_POP                         restore q (closes a PUSH_AFFINE)
+ *     SDFV_OP_POP_SCALE   a = s           restore q, then top.d = top.d * s (closes a PUSH_SCALE)
+ *   combinators: pop b, pop a, push one value
+ *     SDFV_OP_UNION                       a.d <= b.d ? a : b
+ *     SDFV_OP_INTERSECT                   a.d >= b.d ? a : b
+ *     SDFV_OP_SUBTRACT                    d = max(a.d, -b.d); material of a if |a.d| - |b.d| < 0, else of b (demo/mod.rs:58-61)
+ *     SDFV_OP_SMOOTH_UNION    a = k       h = max(k - |a.d - b.d|, 0) / k; d = min(a.d, b.d) - (h*h) * (k*0.25); material as UNION
+ *     SDFV_OP_SMOOTH_SUBTRACT a = k       nb = -b.d; h = max(k - |a.d - nb|, 0) / k; d = max(a.d, nb) + (h*h) * (k*0.25);
+ *                                         material as SUBTRACT (k > 0)
+ *   on the top value
+ *     SDFV_OP_ROUND     a = r             d = d - r
+ *     SDFV_OP_SHELL     a = t             d = |d| - t
+ *   state
+ *     SDFV_OP_MATERIAL  a = r g b metallic roughness occlusion   sets the current material
+ * distance_only != 0 returns the distance with all six material fields 0. */
+typedef struct sdfv_prog_op {
+    uint32_t op;          /* SDFV_OP_* */
+    uint32_t reserved[3]; /* 0 */
+    float    a[12];       /* operands, see the table */
+} sdfv_prog_op;           /* 64 bytes */
+enum {
+    SDFV_OP_SPHERE = 1, SDFV_OP_CUBE = 2, SDFV_OP_BOX = 3, SDFV_OP_CYLINDER = 4, SDFV_OP_TORUS = 5, SDFV_OP_PLANE = 6,
+    SDFV_OP_PUSH_AFFINE = 7, SDFV_OP_PUSH_SCALE = 8, SDFV_OP_POP = 9, SDFV_OP_POP_SCALE = 10,
+    SDFV_OP_UNION = 11, SDFV_OP_INTERSECT = 12, SDFV_OP_SUBTRACT = 13, SDFV_OP_SMOOTH_UNION = 14, SDFV_OP_SMOOTH_SUBTRACT = 15,
+    SDFV_OP_ROUND = 16, SDFV_OP_SHELL = 17, SDFV_OP_MATERIAL = 18
+};
+#define SDFV_PROGRAM_MAX_OPS    256
+#define SDFV_PROGRAM_MAX_VALUES 8
+#define SDFV_PROGRAM_MAX_FRAMES 4
+typedef struct sdfv_program sdfv_program;
+/* HOST; copies and validates `ops`; needs no device.  bb: the model's bounding box [min.xyz, max.xyz] (what a surface made from
+ * the program reports; the fill takes its box from the grid).  SDFV_ERR_INVALID_ARGUMENT with a message that names the
+ * instruction ("op 17: ...") for: an unknown opcode, a non-zero reserved word, a non-finite operand, k <= 0, s <= 0 or
+ * inv_s <= 0, a value or frame stack that under- or overflows at that instruction, a POP closing a PUSH_SCALE or a POP_SCALE
+ * closing a PUSH_AFFINE; and for n == 0, n > SDFV_PROGRAM_MAX_OPS, frames left open or a value count other than 1 at the end,
+ * a box that is not finite or has max <= min on an axis (and, like sdfv_slab_comm_create, when the host is out of memory).
+ * Stack depths are static properties of a program: the kernels never check them. */
+int  sdfv_program_create(const sdfv_prog_op *ops, size_t n, const float bb[6], sdfv_program **out);
+void sdfv_program_free(sdfv_program *p); /* NULL is fine; synchronise the streams that still use it first */
+/* the validated copy: *ops stays valid until sdfv_program_free; any of the three outputs may be NULL */
+int  sdfv_program_ops(const sdfv_program *p, const sdfv_prog_op **ops, size_t *n, float bb[6]);
+/* The device entry points below make the program's device copy on the first use per device (a synchronous copy of n * 64
+ * bytes, owned by the handle).  Without a device they return SDFV_ERR_NO_DEVICE and write nothing: like the rest of this
+ * library they have no CPU path (the host mirror, include/sdfprogram.h, is where a program is evaluated on the host).
+ * points: DEVICE, n x 3 floats.  out: DEVICE, n x sdfv_sample. */
+int  sdfv_program_sample_points(const sdfv_program *p, const float *points, size_t n, int distance_only, sdfv_sample *out,
+                                void *stream);
+/* host buffers, evaluated ON THE DEVICE (allocate, run, copy back, synchronise), like the other *_host calls */
+int  sdfv_program_sample_points_host(const sdfv_program *p, const float *points_host, size_t n, int distance_only,
+                                     sdfv_sample *out_host);
+/* sdfv_fill_grid_commit for a program: the state SDFViewer::update converges to on a fresh grid, for a whole grid or a z-slab.
+ * dist: DEVICE or NULL, the distance volume; flags: 0 or SDFV_PASS_VOLUME_INTERLEAVED (its layout: H even, 8-byte aligned).
+ * Honours SDFV_OPT_EXT_SRGB_QUANT and SDFV_OPT_FILL_NONTEMPORAL; writes tex1.a = AIR_DIST. */
+int  sdfv_program_fill_grid_commit(const sdfv_program *p, const sdfv_grid *grid, float *tex0, float *tex1, float *dist,
+                                   uint32_t flags, void *stream);
 
 /* ---- batched point sampling (the "Batched sampling" TODO, src/sdf/mod.rs:39) ---- */
 /* points: DEVICE, n x 3 floats.  out: DEVICE, n x sdfv_sample.  SDFSurface::sample(p, distance_only). */

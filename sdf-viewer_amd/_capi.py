@@ -81,6 +81,13 @@ class MarchDesc(C.Structure):
                 ("rgba8", C.c_void_p)]
 
 
+class ProgOp(C.Structure):
+    """sdfv_prog_op: one 64-byte instruction of an SDF program."""
+    _fields_ = [("op", C.c_uint32), ("reserved", C.c_uint32 * 3), ("a", C.c_float * 12)]
+
+
+assert C.sizeof(ProgOp) == 64
+
 PROTOTYPES = {
     "sdfv_raymarch_ex": (C.c_int, [C.POINTER(MarchDesc), C.c_void_p]),
     "sdfv_abi_version": (C.c_uint32, []),
@@ -168,6 +175,14 @@ PROTOTYPES = {
                                            C.c_void_p, C.c_void_p]),
     "sdfv_comm_allgather_slabs": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # SDF programs
+    "sdfv_program_create": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_void_p)]),
+    "sdfv_program_free": (None, [C.c_void_p]),
+    "sdfv_program_ops": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_float)]),
+    "sdfv_program_sample_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "sdfv_program_sample_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "sdfv_program_fill_grid_commit": (C.c_int, [C.c_void_p, C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                C.c_void_p]),
 }
 LIGHT_AMBIENT, LIGHT_DIRECTIONAL, MAX_LIGHTS = 0, 1, 4
 
@@ -204,6 +219,10 @@ OPT_TUNING_TILE_ORDER = 102
 RM_NO_FAST_INDEX, RM_NO_POW2_EXTENT, RM_NO_POW2_SIZE, RM_NO_SYMMETRIC, RM_NO_ASM_LOOP, RM_NO_INTERIOR_FETCH = 1, 2, 4, 8, 16, 32
 STEP_SIDE_BOUNDARY, STEP_UNPACKED, STEP_START_EVENT, STEP_DEFER_JOIN = 3, 4, 8, 16
 PASS_FRESH_GRID, PASS_SAME_LOAD, PASS_VIRGIN_GRID, PASS_VOLUME_INTERLEAVED, PASS_EXPECT_NOOP = 1, 2, 4, 8, 16
+# SDFV_OP_*: the opcodes of an SDF program (sdfv_prog_op.op)
+(OP_SPHERE, OP_CUBE, OP_BOX, OP_CYLINDER, OP_TORUS, OP_PLANE, OP_PUSH_AFFINE, OP_PUSH_SCALE, OP_POP, OP_POP_SCALE, OP_UNION,
+ OP_INTERSECT, OP_SUBTRACT, OP_SMOOTH_UNION, OP_SMOOTH_SUBTRACT, OP_ROUND, OP_SHELL, OP_MATERIAL) = range(1, 19)
+PROGRAM_MAX_OPS, PROGRAM_MAX_VALUES, PROGRAM_MAX_FRAMES = 256, 8, 4
 FILL_FORM = {"auto": 0, "rows": 1, "flat": 2}
 COMM_ID_BYTES = 128
 RAY_BUFFER_HEADER_BYTES = 16

@@ -4,8 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
+#include <vector>
+#include <new>
 
 #include <cmath>
 #include <cstdarg>
@@ -19,6 +23,7 @@
 #include "ingest_kernels.h"
 #include "mesh_kernels.h"
 #include "points_kernels.h"
+#include "program_kernels.h"
 #include "raymarch_kernels.h"
 
 namespace {
@@ -1460,6 +1465,221 @@ int sdfv_raymarch_host(const sdfv_render_params* rp, const float* tex0_host, con
         return rc;
     SDFV_HIP(hipMemcpy(rgba_host, dr.p, px * 16, hipMemcpyDeviceToHost));
     if (aux_host) SDFV_HIP(hipMemcpy(aux_host, da.p, px * sizeof(sdfv_march_aux), hipMemcpyDeviceToHost));
+    return SDFV_OK;
+}
+
+
+// ---- SDF programs ----
+}  // extern "C"
+
+// The handle: the validated instructions (host) and one device copy per device that has used it.
+struct sdfv_program {
+    std::vector<sdfv_prog_op> ops;
+    float bb[6];
+    std::mutex mu;
+    std::vector<std::pair<int, void*>> device_copies;  // (HIP device, n * 64 bytes)
+};
+
+namespace {
+
+const char* program_op_name(uint32_t op) {
+    static const char* const names[] = {"?", "SPHERE", "CUBE", "BOX", "CYLINDER", "TORUS", "PLANE", "PUSH_AFFINE", "PUSH_SCALE",
+                                        "POP", "POP_SCALE", "UNION", "INTERSECT", "SUBTRACT", "SMOOTH_UNION", "SMOOTH_SUBTRACT",
+                                        "ROUND", "SHELL", "MATERIAL"};
+    return op <= SDFV_OP_MATERIAL ? names[op] : "?";
+}
+
+// Everything sdfgrid.h promises sdfv_program_create rejects.  The stack depths are static: one walk decides them.
+int validate_program(const sdfv_prog_op* ops, size_t n, const float bb[6]) {
+    if (!ops || !bb) return fail(SDFV_ERR_INVALID_ARGUMENT, "ops or bb is NULL");
+    if (n == 0 || n > SDFV_PROGRAM_MAX_OPS)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "a program has 1 .. %d instructions, not %zu", SDFV_PROGRAM_MAX_OPS, n);
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(bb[i]) || !std::isfinite(bb[3 + i]) || !(bb[3 + i] > bb[i]))
+            return fail(SDFV_ERR_INVALID_ARGUMENT, "degenerate bounding box on axis %d: [%g, %g]", i, bb[i], bb[3 + i]);
+    uint32_t values = 0, frames = 0;
+    bool scale_frame[SDFV_PROGRAM_MAX_FRAMES] = {};
+    for (size_t i = 0; i < n; ++i) {
+        const sdfv_prog_op& o = ops[i];
+        if (o.op < SDFV_OP_SPHERE || o.op > SDFV_OP_MATERIAL)
+            return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu: unknown opcode %u", i, o.op);
+        const char* name = program_op_name(o.op);
+        if (o.reserved[0] | o.reserved[1] | o.reserved[2])
+            return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu (%s): reserved words must be 0", i, name);
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(o.a[k])) return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu (%s): operand %d is not finite", i, name, k);
+        uint32_t pops = 0, pushes = 0;
+        switch (o.op) {
+            case SDFV_OP_SPHERE: case SDFV_OP_CUBE: case SDFV_OP_BOX: case SDFV_OP_CYLINDER: case SDFV_OP_TORUS: case SDFV_OP_PLANE:
+                pushes = 1;
+                break;
+            case SDFV_OP_SMOOTH_UNION: case SDFV_OP_SMOOTH_SUBTRACT:
+                if (!(o.a[0] > 0.0f)) return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu (%s): k = %g must be > 0", i, name, o.a[0]);
+                pops = 2, pushes = 1;
+                break;
+            case SDFV_OP_UNION: case SDFV_OP_INTERSECT: case SDFV_OP_SUBTRACT:
+                pops = 2, pushes = 1;
+                break;
+            case SDFV_OP_ROUND: case SDFV_OP_SHELL:
+                pops = 1, pushes = 1;
+                break;
+            case SDFV_OP_PUSH_AFFINE: case SDFV_OP_PUSH_SCALE:
+                if (o.op == SDFV_OP_PUSH_SCALE && (!(o.a[0] > 0.0f) || !(o.a[1] > 0.0f)))
+                    return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu (%s): s = %g and inv_s = %g must be > 0", i, name, o.a[0], o.a[1]);
+                if (frames == SDFV_PROGRAM_MAX_FRAMES)
+                    return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu (%s): frame stack overflow (more than %d open frames)", i, name,
+                                SDFV_PROGRAM_MAX_FRAMES);
+                scale_frame[frames++] = o.op == SDFV_OP_PUSH_SCALE;
+                break;
+            case SDFV_OP_POP: case SDFV_OP_POP_SCALE: {
+                const bool scale = o.op == SDFV_OP_POP_SCALE;
+                if (scale && !(o.a[0] > 0.0f)) return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu (%s): s = %g must be > 0", i, name, o.a[0]);
+                if (frames == 0) return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu (%s): frame stack underflow (no open frame)", i, name);
+                if (scale_frame[frames - 1] != scale)
+                    return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu (%s): closes a %s", i, name, scale ? "PUSH_AFFINE" : "PUSH_SCALE");
+                --frames;
+                if (scale) pops = 1, pushes = 1;
+                break;
+            }
+            default:  // MATERIAL
+                break;
+        }
+        if (values < pops)
+            return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu (%s): value stack underflow (needs %u, has %u)", i, name, pops, values);
+        values = values - pops + pushes;
+        if (values > SDFV_PROGRAM_MAX_VALUES)
+            return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu (%s): value stack overflow (more than %d values)", i, name,
+                        SDFV_PROGRAM_MAX_VALUES);
+    }
+    if (frames != 0) return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu: the program ends with %u open frame(s)", n - 1, frames);
+    if (values != 1) return fail(SDFV_ERR_INVALID_ARGUMENT, "op %zu: the program ends with %u values, not 1", n - 1, values);
+    return SDFV_OK;
+}
+
+// The program's instructions on the current device, copied there on the first use.
+int program_device_ops(const sdfv_program* cp, const sdfv_prog_op** out) {
+    sdfv_program* p = const_cast<sdfv_program*>(cp);
+    const int dev = current_device();
+    if (dev < 0) return fail(SDFV_ERR_NO_DEVICE, "no current HIP device");
+    std::lock_guard<std::mutex> lock(p->mu);
+    for (const auto& c : p->device_copies)
+        if (c.first == dev) {
+            *out = static_cast<const sdfv_prog_op*>(c.second);
+            return SDFV_OK;
+        }
+    void* d = nullptr;
+    const size_t bytes = p->ops.size() * sizeof(sdfv_prog_op);
+    try {
+        p->device_copies.reserve(p->device_copies.size() + 1);  // (so that recording the copy below cannot fail)
+    } catch (const std::bad_alloc&) {
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "out of host memory");
+    }
+    SDFV_HIP(hipMalloc(&d, bytes));
+    const hipError_t e = hipMemcpy(d, p->ops.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return hip_fail(e, "hipMemcpy of the program");
+    }
+    p->device_copies.emplace_back(dev, d);
+    *out = static_cast<const sdfv_prog_op*>(d);
+    return SDFV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfv_program_create(const sdfv_prog_op* ops, size_t n, const float bb[6], sdfv_program** out) {
+    if (!out) return fail(SDFV_ERR_INVALID_ARGUMENT, "out is NULL");
+    *out = nullptr;
+    if (int rc = validate_program(ops, n, bb)) return rc;
+    try {  // nothing crosses the C boundary, and a copy that fails takes the half-made handle with it
+        std::unique_ptr<sdfv_program> p(new sdfv_program);
+        p->ops.assign(ops, ops + n);
+        memcpy(p->bb, bb, sizeof(p->bb));
+        *out = p.release();
+    } catch (const std::bad_alloc&) {
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "out of host memory");  // (the status sdfv_slab_comm_create reports it with)
+    }
+    return SDFV_OK;
+}
+
+void sdfv_program_free(sdfv_program* p) {
+    if (!p) return;
+    for (const auto& c : p->device_copies) (void)hipFree(c.second);
+    delete p;
+}
+
+int sdfv_program_ops(const sdfv_program* p, const sdfv_prog_op** ops, size_t* n, float bb[6]) {
+    if (!p) return fail(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if (ops) *ops = p->ops.data();
+    if (n) *n = p->ops.size();
+    if (bb) memcpy(bb, p->bb, sizeof(p->bb));
+    return SDFV_OK;
+}
+
+int sdfv_program_sample_points(const sdfv_program* p, const float* points, size_t n, int distance_only, sdfv_sample* out,
+                               void* stream) {
+    if (!p) return fail(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if (n && (!points || !out)) return fail(SDFV_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (((uintptr_t)points | (uintptr_t)out) & 3) return fail(SDFV_ERR_INVALID_ARGUMENT, "points and out must be 4-byte aligned");
+    if (int rc = need_device()) return rc;
+    if (n == 0) return SDFV_OK;
+    const sdfv_prog_op* dev_ops = nullptr;
+    if (int rc = program_device_ops(p, &dev_ops)) return rc;
+    SDFV_HIP(sdfv::launch_program_sample_points(dev_ops, (uint32_t)p->ops.size(), points, n, distance_only != 0, out,
+                                                (hipStream_t)stream));
+    return SDFV_OK;
+}
+
+int sdfv_program_sample_points_host(const sdfv_program* p, const float* points_host, size_t n, int distance_only,
+                                    sdfv_sample* out_host) {
+    if (!p) return fail(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if (n && (!points_host || !out_host)) return fail(SDFV_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (int rc = need_device()) return rc;
+    if (n == 0) return SDFV_OK;
+    return run_over_host_buffers(points_host, n * 12, out_host, n * sizeof(sdfv_sample), [&](void* in, void* out) {
+        return sdfv_program_sample_points(p, (const float*)in, n, distance_only, (sdfv_sample*)out, nullptr);
+    });
+}
+
+int sdfv_program_fill_grid_commit(const sdfv_program* p, const sdfv_grid* grid, float* tex0, float* tex1, float* dist,
+                                  uint32_t flags, void* stream) {
+    if (!p) return fail(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if (int rc = check_grid(grid)) return rc;
+    if (!tex0 || !tex1) return fail(SDFV_ERR_INVALID_ARGUMENT, "texture pointer is NULL");
+    if (flags & ~SDFV_PASS_VOLUME_INTERLEAVED) return fail(SDFV_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
+    if (flags & SDFV_PASS_VOLUME_INTERLEAVED) {
+        if (!dist) return fail(SDFV_ERR_INVALID_ARGUMENT, "SDFV_PASS_VOLUME_INTERLEAVED without a volume");
+        if ((grid->dims[1] & 1u) || ((uintptr_t)dist & 7))
+            return fail(SDFV_ERR_INVALID_ARGUMENT, "the interleaved volume pairs rows: H = %u must be even and the volume 8-byte aligned", grid->dims[1]);
+    }
+    if (int rc = check_texel_alignment(tex0, tex1)) return rc;
+    if ((uintptr_t)dist & 3) return fail(SDFV_ERR_INVALID_ARGUMENT, "dist must be 4-byte aligned");
+    if (int rc = need_device()) return rc;
+    sdfv::ProgramFillArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = program_device_ops(p, &a.ops)) return rc;
+    a.n_ops = (uint32_t)p->ops.size();
+    a.W = grid->dims[0];
+    a.H = grid->dims[1];
+    a.z_begin = grid->z_begin;
+    a.slab_d = grid->z_end - grid->z_begin;
+    for (int i = 0; i < 3; ++i) {
+        a.dm1[i] = (float)grid->dims[i] - 1.0f;            // scene/sdf/mod.rs:168
+        a.bb_size[i] = grid->bb_max[i] - grid->bb_min[i];  // scene/sdf/mod.rs:167
+        a.bb_min[i] = grid->bb_min[i];
+    }
+    a.air_dist = air_dist();
+    a.tex0 = reinterpret_cast<float4*>(tex0);
+    a.tex1 = reinterpret_cast<float4*>(tex1);
+    a.dist = dist;
+    a.dist_ilv = (flags & SDFV_PASS_VOLUME_INTERLEAVED) ? 1u : 0u;
+    a.srgb_round = g_options.ext_srgb_quant;
+    a.nontemporal = fill_launch_config(dist != nullptr).nontemporal ? 1u : 0u;
+    if ((uint64_t)a.H * a.slab_d > 0x7fffffffull || a.W > 0x7fffffffu)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "slab of %u x %u rows is too large for one launch", a.H, a.slab_d);
+    SDFV_HIP(sdfv::launch_program_fill(a, (hipStream_t)stream));
     return SDFV_OK;
 }
 

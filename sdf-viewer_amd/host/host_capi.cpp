@@ -13,6 +13,7 @@
 
 #include "loading_manager.hpp"
 #include "mesh.hpp"
+#include "program_sdf.hpp"
 #include "provider_sdf.hpp"
 #include "sdf_demo.hpp"
 #include "scene.hpp"
@@ -73,6 +74,15 @@ void* sdfvh_provider_load(const char* path, char* err, size_t err_len) {
     }
     return new std::shared_ptr<SDFSurface>(p);
 }
+// ---- ProgramSDF (same handle type): the program stays the caller's and must outlive the handle ----
+void* sdfvh_program_sdf_new(const sdfv_program* program) {
+    try {
+        return new std::shared_ptr<SDFSurface>(std::make_shared<ProgramSDF>(program));
+    } catch (...) {
+        return nullptr;
+    }
+}
+int sdfvh_sdf_has_device_sampler(void* h) { return (**static_cast<std::shared_ptr<SDFSurface>*>(h)).has_device_sampler() ? 1 : 0; }
 void sdfvh_sdf_free(void* h) { delete static_cast<std::shared_ptr<SDFSurface>*>(h); }
 static SDFSurface& S(void* h) { return **static_cast<std::shared_ptr<SDFSurface>*>(h); }
 uint32_t sdfvh_sdf_id(void* h) { return S(h).id(); }

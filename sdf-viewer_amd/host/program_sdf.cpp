@@ -1,0 +1,110 @@
+// program_sdf.cpp -- ProgramSDF and sdfv_program_as_surface (include/sdfprogram.h): SDF programs on the host.
+// Built with -ffp-contract=off like the kernels: csrc/program_eval.h then rounds every step as the device does.
+#include "program_sdf.hpp"
+
+#include <cstring>
+#include <stdexcept>
+
+#include "../../include/sdfprogram.h"
+#include "../csrc/program_eval.h"
+
+namespace sdfviewer {
+namespace {
+
+// The result of the stack machine as a record: the material index resolved against the program's own instructions.
+void evaluate(const sdfv_prog_op* ops, size_t n_ops, const float* p, bool distance_only, sdfv_sample* out) {
+    const sdfv::prog::Value v = sdfv::prog::run(ops, (uint32_t)n_ops, p[0], p[1], p[2]);
+    out->distance = v.d;
+    const bool has = !distance_only && v.m != sdfv::prog::kNoMaterial;
+    const float* a = has ? ops[v.m].a : nullptr;
+    for (int k = 0; k < 3; ++k) out->color[k] = has ? a[k] : 0.0f;
+    out->metallic = has ? a[3] : 0.0f;
+    out->roughness = has ? a[4] : 0.0f;
+    out->occlusion = has ? a[5] : 0.0f;
+}
+
+// ---- the callbacks of sdfv_program_as_surface ----
+// `user` is the program (the surface has no destructor, so it cannot own an object): every callback makes the ProgramSDF over it
+// -- a view, three words read from the handle -- and goes through the class, so that the C surface and a C++ host's ProgramSDF
+// are one code path.  Nothing crosses the C boundary: an exception becomes a non-zero status.
+template <class F>
+int through_program_sdf(void* user, F&& body) {
+    try {
+        const ProgramSDF sdf(static_cast<const sdfv_program*>(user));
+        body(sdf);
+        return 0;
+    } catch (...) {
+        return 1;
+    }
+}
+void cb_bounding_box(void* user, float out[6]) {
+    through_program_sdf(user, [&](const ProgramSDF& sdf) {
+        const BoundingBox bb = sdf.bounding_box();
+        out[0] = bb[0].x; out[1] = bb[0].y; out[2] = bb[0].z;
+        out[3] = bb[1].x; out[4] = bb[1].y; out[5] = bb[1].z;
+    });
+}
+int cb_sample_batch(void* user, const float* p, size_t n, int distance_only, sdfv_sample* out) {
+    static_assert(sizeof(Vec3) == 12, "points are handed over as 3 floats each");
+    return through_program_sdf(user, [&](const ProgramSDF& sdf) {
+        sdf.sample_batch(reinterpret_cast<const Vec3*>(p), n, distance_only != 0, reinterpret_cast<SDFSample*>(out));
+    });
+}
+int cb_sample(void* user, const float p[3], int distance_only, sdfv_sample* out) {
+    return through_program_sdf(user, [&](const ProgramSDF& sdf) {
+        const SDFSample s = sdf.sample(Vec3{p[0], p[1], p[2]}, distance_only != 0);
+        memcpy(out, &s, sizeof(s));
+    });
+}
+uint32_t cb_sample_concurrency(void* user) {
+    uint32_t n = 1;
+    through_program_sdf(user, [&](const ProgramSDF& sdf) { n = sdf.sample_concurrency(); });
+    return n;
+}
+int cb_sample_batch_device(void* user, const float* points_dev, size_t n, sdfv_sample* out_dev, void* stream) {
+    return through_program_sdf(user, [&](const ProgramSDF& sdf) { sdf.sample_batch_device(points_dev, n, out_dev, stream); });
+}
+
+}  // namespace
+
+ProgramSDF::ProgramSDF(const sdfv_program* program) : program_(program) {
+    if (sdfv_program_ops(program, &ops_, &n_ops_, bb_) != SDFV_OK) throw std::invalid_argument(sdfv_last_error());
+}
+
+BoundingBox ProgramSDF::bounding_box() const { return {Vec3{bb_[0], bb_[1], bb_[2]}, Vec3{bb_[3], bb_[4], bb_[5]}}; }
+
+SDFSample ProgramSDF::sample(Vec3 p, bool distance_only) const {
+    SDFSample out;
+    evaluate(ops_, n_ops_, &p.x, distance_only, reinterpret_cast<sdfv_sample*>(&out));
+    return out;
+}
+
+void ProgramSDF::sample_batch(const Vec3* p, size_t n, bool distance_only, SDFSample* out) const {
+    for (size_t i = 0; i < n; ++i) evaluate(ops_, n_ops_, &p[i].x, distance_only, reinterpret_cast<sdfv_sample*>(out + i));
+}
+
+bool ProgramSDF::has_device_sampler() const { return sdfv_device_count() > 0; }
+
+void ProgramSDF::sample_batch_device(const float* points_dev, size_t n, sdfv_sample* out_dev, void* stream) const {
+    if (sdfv_program_sample_points(program_, points_dev, n, 0, out_dev, stream) != SDFV_OK)
+        throw std::runtime_error(sdfv_last_error());
+}
+
+}  // namespace sdfviewer
+
+// (libsdfviewer_host.so is built with default visibility: exported there, hidden in the test and provider libraries)
+extern "C" int sdfv_program_as_surface(const sdfv_program* p, sdfv_surface* out) {
+    if (!p || !out) return SDFV_ERR_INVALID_ARGUMENT;
+    bool device = false;
+    if (sdfviewer::through_program_sdf(const_cast<sdfv_program*>(p), [&](const sdfviewer::ProgramSDF& sdf) { device = sdf.has_device_sampler(); }))
+        return SDFV_ERR_INVALID_ARGUMENT;
+    sdfv_surface s = {};
+    s.user = const_cast<sdfv_program*>(p);
+    s.bounding_box = sdfviewer::cb_bounding_box;
+    s.sample = sdfviewer::cb_sample;
+    s.sample_batch = sdfviewer::cb_sample_batch;
+    s.sample_concurrency = sdfviewer::cb_sample_concurrency;
+    s.sample_batch_device = device ? sdfviewer::cb_sample_batch_device : nullptr;
+    *out = s;
+    return SDFV_OK;
+}

@@ -1,0 +1,197 @@
+"""SDF programs (include/sdfgrid.h, "SDF programs"): a caller-defined CSG tree as data, evaluated on the device.
+
+    prog = (Program(bb=(-1, -1, -1, 1, 1, 1))
+            .material(0.8, 0.2, 0.1, roughness=0.6)
+            .push_affine(translation(0.2, 0.0, 0.0)).box(0.5, 0.3, 0.2).pop()
+            .material(0.1, 0.3, 0.9).sphere(0.45)
+            .subtract()
+            .build())
+    t0, t1 = pkg.alloc_textures(grid)
+    prog.fill_grid(grid, t0, t1)                       # the dense fill, one launch
+    records = prog.sample_points(points)               # [n, 3] CUDA tensor -> [n, 7]
+    viewer.update(prog.as_surface())                   # progressive load through sdf-viewer_amd.viewer
+
+The builder only appends instructions; sdfv_program_create validates them (build() raises SdfvError with the message that
+names the offending instruction).
+"""
+import ctypes as C
+
+from . import _capi
+from ._capi import ProgOp, SdfvError, check, lib
+
+
+def translation(tx, ty, tz):
+    """The 3 x 4 matrix PUSH_AFFINE wants for content MOVED by (tx, ty, tz): the inverse transform, row-major."""
+    return (1.0, 0.0, 0.0, -float(tx), 0.0, 1.0, 0.0, -float(ty), 0.0, 0.0, 1.0, -float(tz))
+
+
+def rigid_inverse(rotation, t):
+    """rotation: 3 x 3 row-major (orthonormal), t: translation of the content -> the inverse as PUSH_AFFINE's 12 floats:
+    q' = R^T (q - t)."""
+    r = [[float(rotation[i][j]) for j in range(3)] for i in range(3)]
+    rt = [[r[j][i] for j in range(3)] for i in range(3)]
+    out = []
+    for i in range(3):
+        out += rt[i] + [-(rt[i][0] * float(t[0]) + rt[i][1] * float(t[1]) + rt[i][2] * float(t[2]))]
+    return tuple(out)
+
+
+class Program:
+    """Builder: every method appends one instruction and returns self; build() hands the array to the library."""
+
+    def __init__(self, bb=(-1.0, -1.0, -1.0, 1.0, 1.0, 1.0)):
+        self.bb = tuple(float(x) for x in bb)
+        self.ops = []
+
+    def op(self, opcode, *operands):
+        """Any instruction by opcode (_capi.OP_*) and operands; the named methods below all come here."""
+        assert len(operands) <= 12
+        self.ops.append((int(opcode), tuple(float(x) for x in operands)))
+        return self
+
+    # primitives
+    def sphere(self, r): return self.op(_capi.OP_SPHERE, r)
+    def cube(self, h): return self.op(_capi.OP_CUBE, h)
+    def box(self, hx, hy, hz): return self.op(_capi.OP_BOX, hx, hy, hz)
+    def cylinder(self, r, half_height): return self.op(_capi.OP_CYLINDER, r, half_height)
+    def torus(self, major, minor): return self.op(_capi.OP_TORUS, major, minor)
+    def plane(self, nx, ny, nz, d): return self.op(_capi.OP_PLANE, nx, ny, nz, d)
+    # frames
+    def push_affine(self, m12): return self.op(_capi.OP_PUSH_AFFINE, *m12)
+    def pop(self): return self.op(_capi.OP_POP)
+
+    def push_scale(self, s):
+        import numpy as np
+        s = np.float32(s)
+        return self.op(_capi.OP_PUSH_SCALE, s, np.float32(1.0) / s)
+
+    def pop_scale(self, s): return self.op(_capi.OP_POP_SCALE, s)
+    # combinators
+    def union(self): return self.op(_capi.OP_UNION)
+    def intersect(self): return self.op(_capi.OP_INTERSECT)
+    def subtract(self): return self.op(_capi.OP_SUBTRACT)
+    def smooth_union(self, k): return self.op(_capi.OP_SMOOTH_UNION, k)
+    def smooth_subtract(self, k): return self.op(_capi.OP_SMOOTH_SUBTRACT, k)
+    # on the top value
+    def round(self, r): return self.op(_capi.OP_ROUND, r)
+    def shell(self, t): return self.op(_capi.OP_SHELL, t)
+
+    def material(self, r, g, b, metallic=0.0, roughness=0.0, occlusion=0.0):
+        return self.op(_capi.OP_MATERIAL, r, g, b, metallic, roughness, occlusion)
+
+    def array(self):
+        """The instructions as a ctypes array of sdfv_prog_op."""
+        arr = (ProgOp * max(len(self.ops), 1))()
+        for i, (opcode, operands) in enumerate(self.ops):
+            arr[i].op = opcode
+            for k, v in enumerate(operands):
+                arr[i].a[k] = v
+        return arr
+
+    def build(self):
+        return CompiledProgram(self.array(), len(self.ops), self.bb)
+
+
+def _rotation(axis, degrees):
+    import math
+    c, s = math.cos(math.radians(degrees)), math.sin(math.radians(degrees))
+    return [[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]] if axis == "z" else [[1.0, 0.0, 0.0], [0.0, c, -s], [0.0, s, c]]
+
+
+def example_sixteen():
+    """A 16-primitive model with frames and materials, as a Program builder (77 instructions): a plate on four pillars, a torus,
+    a tilted cube, a ring of six spheres, a bore, a rounded foot, cut by a plane.  The large program of tools/program_bench.py
+    (profiles/program_fill.json's "C") and a member of the tests' catalogue: changing it changes what those numbers mean."""
+    import math
+    s = Program((-1.0, -1.0, -1.0, 1.0, 1.0, 1.0))
+    s.material(0.7, 0.7, 0.75, 0.9, 0.3, 1.0).box(0.8, 0.8, 0.1)                                   # 1: a plate
+    for i in range(4):                                                                            # 2..5: four pillars
+        cx, cy = (-0.6 if i & 1 else 0.6), (-0.6 if i & 2 else 0.6)
+        s.material(0.6, 0.3 + 0.1 * i, 0.2, 0.1, 0.7, 1.0)
+        s.push_affine(translation(cx, cy, 0.45)).cylinder(0.08, 0.4).pop().union()
+    s.material(0.2, 0.5, 0.8, 0.0, 0.4, 1.0)
+    s.push_affine(translation(0.0, 0.0, 0.5)).torus(0.45, 0.08).pop().smooth_union(0.05)            # 6
+    s.material(0.9, 0.1, 0.1, 0.3, 0.2, 1.0)
+    s.push_affine(rigid_inverse(_rotation("z", 45.0), (0.0, 0.0, 0.3))).push_scale(0.5).cube(0.3).pop_scale(0.5).pop().union()  # 7
+    for i in range(6):                                                                            # 8..13: a ring of spheres
+        ang = math.radians(60.0 * i)
+        s.material(0.2 + 0.1 * i, 0.8 - 0.1 * i, 0.4, 0.2, 0.5, 1.0)
+        s.push_affine(translation(0.7 * math.cos(ang), 0.7 * math.sin(ang), -0.3)).sphere(0.15).pop().smooth_union(0.04)
+    s.material(0.3, 0.3, 0.3, 0.0, 0.9, 1.0)
+    s.push_affine(rigid_inverse(_rotation("x", 90.0), (0.0, 0.0, 0.0))).cylinder(0.1, 1.2).pop().subtract()  # 14: a bore
+    s.material(0.95, 0.85, 0.2, 1.0, 0.1, 1.0)
+    s.push_affine(translation(0.0, 0.0, -0.6)).box(0.3, 0.3, 0.05).round(0.02).pop().union()        # 15
+    s.plane(0.0, 0.0, -1.0, 0.95).intersect()                                                     # 16
+    return s
+
+
+class CompiledProgram:
+    """An sdfv_program handle."""
+
+    def __init__(self, ops_array, n, bb):
+        h = C.c_void_p()
+        check(lib.sdfv_program_create(C.cast(ops_array, C.c_void_p), int(n), (C.c_float * 6)(*[float(x) for x in bb]), C.byref(h)))
+        self.h = h
+        self._surface = None
+
+    def ops(self):
+        """(numpy structured copy of the validated instructions, bounding box)."""
+        import numpy as np
+        p, n, bb = C.c_void_p(), C.c_size_t(), (C.c_float * 6)()
+        check(lib.sdfv_program_ops(self.h, C.byref(p), C.byref(n), bb))
+        raw = C.string_at(p.value, n.value * 64)
+        dt = np.dtype([("op", "<u4"), ("reserved", "<u4", (3,)), ("a", "<f4", (12,))])
+        return np.frombuffer(raw, dtype=dt).copy(), tuple(bb)
+
+    def sample_points(self, points, distance_only=False, stream=None):
+        """points: [n, 3] float32 CUDA tensor -> [n, 7] records (distance, r, g, b, metallic, roughness, occlusion)."""
+        import torch
+        from . import _dev_ptr, _stream_ptr
+        n = points.shape[0]
+        out = torch.empty((n, 7), dtype=torch.float32, device=points.device)
+        check(lib.sdfv_program_sample_points(self.h, _dev_ptr(points, "points") if n else None, n, int(bool(distance_only)),
+                                             C.c_void_p(out.data_ptr()) if n else None, _stream_ptr(stream)))
+        return out
+
+    def sample_points_host(self, points, distance_only=False):
+        """points: [n, 3] float32 numpy array -> [n, 7] numpy array; evaluated on the device."""
+        import numpy as np
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        out = np.empty((pts.shape[0], 7), np.float32)
+        check(lib.sdfv_program_sample_points_host(self.h, pts.ctypes.data, pts.shape[0], int(bool(distance_only)), out.ctypes.data))
+        return out
+
+    def fill_grid(self, grid, tex0, tex1, dist=None, flags=0, stream=None):
+        """sdfv_program_fill_grid_commit; flags: _capi.PASS_VOLUME_INTERLEAVED when `dist` is the y-interleaved volume."""
+        from . import _dev_ptr, _stream_ptr
+        check(lib.sdfv_program_fill_grid_commit(self.h, C.byref(grid), _dev_ptr(tex0, "tex0"), _dev_ptr(tex1, "tex1"),
+                                                None if dist is None else _dev_ptr(dist, "dist"), int(flags), _stream_ptr(stream)))
+
+    def as_surface(self, device_route=True):
+        """A viewer.Surface over this program (sdfv_program_as_surface); device_route=False clears sample_batch_device, so
+        that the viewer samples through the host callbacks.  The surface keeps the program alive."""
+        from . import viewer
+        fn = viewer.lib.sdfv_program_as_surface
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(viewer.SurfaceStruct)]
+        s = viewer.Surface()
+        rc = fn(self.h, C.byref(s.struct))
+        if rc != 0:
+            raise SdfvError(rc, "sdfv_program_as_surface")
+        if not device_route:
+            s.struct.sample_batch_device = viewer.DEVICE_FN()
+        bb = (C.c_float * 6)()
+        s.struct.bounding_box(s.struct.user, bb)
+        s._bb = tuple(bb)
+        s._keep.append(self)
+        return s
+
+    def close(self):
+        if self.h:
+            lib.sdfv_program_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,263 @@
+"""GPU tests of SDF programs: the point sampler and the dense fill of sdfv_program_* against the numpy restatement of the header's
+table (tests/program_ref.py), the demo anchor on the device, a program loaded through the viewer against the oracle's loop, and
+the plain-C path.  Every comparison is bitwise."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import program_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def PM(pkg):
+    return importlib.import_module("sdf-viewer_amd.program")
+
+
+@pytest.fixture(scope="module")
+def V(pkg):
+    return importlib.import_module("sdf-viewer_amd.viewer")
+
+
+def same_bits(got, want, what):
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.flatnonzero(got.view(np.uint32).reshape(-1) != want.view(np.uint32).reshape(-1))
+    print(f"{what}: {bad.size} of {got.size} words differ")
+    assert bad.size == 0, (what, bad[:8], got.reshape(-1)[bad[:8]], want.reshape(-1)[bad[:8]])
+
+
+def voxel_positions(dims, bb_min, bb_max):
+    """idx / (dim - 1) * size + min, three roundings (scene/sdf/mod.rs:179-182), x fastest: [D * H * W, 3]"""
+    axes = []
+    for a in range(3):
+        i = np.arange(dims[a], dtype=np.float32)
+        axes.append(((i / (np.float32(dims[a]) - np.float32(1))) * (np.float32(bb_max[a]) - np.float32(bb_min[a]))) + np.float32(bb_min[a]))
+    zz, yy, xx = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.stack([xx, yy, zz], axis=-1).reshape(-1, 3).astype(np.float32)
+
+
+def interleave(vol):
+    """texture-order volume [D, H, W] -> the y-interleaved layout (entry ((row >> 1) * W + x) * 2 + (row & 1))"""
+    D, H, W = vol.shape
+    rows = vol.reshape(D * H // 2, 2, W)
+    return np.ascontiguousarray(rows.transpose(0, 2, 1)).reshape(-1)
+
+
+@pytest.mark.timeout(600)
+def test_sample_points_equals_the_numpy_restatement_bitwise(pkg, PM):
+    pts = R.points()
+    dev = torch.from_numpy(pts).cuda()
+    for name, builder in R.catalogue(PM).items():
+        prog = builder.build()
+        for distance_only in (False, True):
+            want = R.run(builder.ops, pts, distance_only)
+            same_bits(prog.sample_points(dev, distance_only).cpu().numpy(), want, f"{name} device buffers d_only={distance_only}")
+            same_bits(prog.sample_points_host(pts, distance_only), want, f"{name} host buffers d_only={distance_only}")
+            for n in (1, 255, 257, 1000):                    # the scalar kernel alone, both kernels, an unaligned start
+                same_bits(prog.sample_points(dev[:n].contiguous(), distance_only).cpu().numpy(), want[:n], f"{name} n={n}")
+            off = dev[3:3 + 512].clone()                     # 512 points whose buffer is not 16-byte aligned: no staged form
+            flat = torch.empty(3 * 512 + 1, device="cuda")
+            flat[1:] = off.reshape(-1)
+            view = flat[1:].view(512, 3)
+            assert view.data_ptr() % 16 != 0
+            same_bits(prog.sample_points(view, distance_only).cpu().numpy(), want[3:3 + 512], f"{name} unaligned")
+        assert prog.sample_points(dev[:0].contiguous()).shape == (0, 7)
+        assert pkg.lib.sdfv_program_sample_points(prog.h, None, 0, 0, None, None) == 0
+
+
+def expected_textures(pkg, grid, dims, samples, srgb, layout):
+    """What sdfv_pack_samples leaves on an sdfv_grid_init-ed grid when fed `samples` (numpy [n, 7]) at every voxel."""
+    t0, t1 = pkg.alloc_textures(grid)
+    pkg.grid_init(grid, t0, t1)
+    n = dims[0] * dims[1] * dims[2]
+    vol = None if layout is None else torch.full((n,), float(pkg.AIR_DIST), device="cuda")
+    with pkg.options({pkg._capi.OPT_EXT_SRGB_QUANT: srgb}):
+        pkg.pack_samples(grid, torch.from_numpy(samples).cuda(), t0, t1, dist=vol,
+                         flags=pkg._capi.PASS_VOLUME_INTERLEAVED if layout == "ilv" else 0)
+    torch.cuda.synchronize()
+    return t0.cpu().numpy(), t1.cpu().numpy(), None if vol is None else vol.cpu().numpy()
+
+
+@pytest.mark.timeout(1500)
+@pytest.mark.parametrize("dims", [(9, 7, 5), (64, 64, 64), (250, 130, 66), (256, 256, 256)])
+def test_fill_equals_packing_the_numpy_samples_bitwise(pkg, PM, dims):
+    K = pkg._capi
+    bb_min, bb_max = (-1.0, -0.9, -0.8), (1.0, 0.9, 0.8)
+    W, H, D = dims
+    grid = pkg.make_grid(dims, bb_min, bb_max)
+    pos = voxel_positions(dims, bb_min, bb_max)
+    names = ("all_ops",) if W * H * D > 1 << 22 else ("all_ops", "deep", "anchor", "no_material")
+    for name in names:
+        builder = R.catalogue(PM)[name]
+        prog = builder.build()
+        samples = R.run(builder.ops, pos)
+        for srgb in (0, 1):
+            want = {}
+            for layout in (None, "plain") + (("ilv",) if H % 2 == 0 else ()):
+                want[layout] = expected_textures(pkg, grid, dims, samples, srgb, layout)
+            same_bits(want["plain"][2].reshape(D, H, W), want["plain"][0][..., 0], "the packed volume is tex0.r")
+            if H % 2 == 0:
+                same_bits(want["ilv"][2], interleave(want["plain"][2].reshape(D, H, W)), "the packed interleaved volume")
+            for layout in want:
+                for nt in (0, 1, 2):
+                    for slabs in (1, 2):
+                        t0, t1 = pkg.alloc_textures(grid)
+                        t0.fill_(-7.0), t1.fill_(-7.0)
+                        vol = None if layout is None else torch.full((D, H, W), -7.0, device="cuda")
+                        flags = K.PASS_VOLUME_INTERLEAVED if layout == "ilv" else 0
+                        with pkg.options({K.OPT_EXT_SRGB_QUANT: srgb, K.OPT_FILL_NONTEMPORAL: nt}):
+                            cuts = [0, D] if slabs == 1 else [0, D // 2, D]
+                            for z0, z1 in zip(cuts[:-1], cuts[1:]):
+                                g = pkg.make_grid(dims, bb_min, bb_max, z_begin=z0, z_end=z1)
+                                prog.fill_grid(g, t0[z0:z1], t1[z0:z1], dist=None if vol is None else vol[z0:z1], flags=flags)
+                        torch.cuda.synchronize()
+                        what = f"{dims} {name} srgb={srgb} volume={layout} nt={nt} slabs={slabs}"
+                        same_bits(t0.cpu().numpy(), want[layout][0], what + " tex0")
+                        same_bits(t1.cpu().numpy(), want[layout][1], what + " tex1")
+                        if vol is not None:
+                            same_bits(vol.cpu().numpy().reshape(-1), want[layout][2], what + " volume")
+            if H % 2:  # the interleaved volume pairs rows: an odd height is an argument error, as for the demo's fill
+                t0, t1 = pkg.alloc_textures(grid)
+                vol = torch.empty((D, H, W), device="cuda")
+                with pytest.raises(pkg.SdfvError, match="must be even"):
+                    prog.fill_grid(grid, t0, t1, dist=vol, flags=K.PASS_VOLUME_INTERLEAVED)
+    assert float(want[None][1][..., 3].min()) == float(want[None][1][..., 3].max()) == float(np.float32(pkg.AIR_DIST))
+
+
+@pytest.mark.timeout(600)
+def test_the_demo_as_a_program_fills_the_demo_distance(pkg, PM):
+    """CUBE 0.95, SPHERE 1.05, SUBTRACT at 256^3: tex0.r of the program fill == tex0.r of sdfv_fill_grid, every voxel."""
+    dims = (256, 256, 256)
+    grid = pkg.make_grid(dims)
+    prog = R.catalogue(PM)["anchor"].build()
+    p0, p1 = pkg.alloc_textures(grid)
+    d0, d1 = pkg.alloc_textures(grid)
+    prog.fill_grid(grid, p0, p1)
+    pkg.fill_grid(pkg.default_params(), grid, d0, d1)
+    torch.cuda.synchronize()
+    assert bool((p0[..., 0].contiguous().view(torch.int32) == d0[..., 0].contiguous().view(torch.int32)).all())
+    assert 0.0 < float((p0[..., 0] < 0.1).float().mean()) < 1.0
+
+
+def reference_sampler(oracle, ops, dims, bb):
+    """An or_sample_fn over the numpy restatement: every voxel position of the grid evaluated once, looked up by position."""
+    pos = voxel_positions(dims, bb[:3], bb[3:])
+    rec = R.run(ops, pos)
+    table = {pos[i].tobytes(): rec[i] for i in range(len(pos))}
+
+    @oracle.SAMPLE_FN
+    def ref_sample(_user, p, _distance_only, out):
+        s = table[np.array([p[0], p[1], p[2]], np.float32).tobytes()]
+        for i in range(7):
+            out[i] = s[i]
+    return ref_sample
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("dims,layout", [((24, 18, 20), 1), ((24, 18, 20), 2), ((21, 17, 11), 1)])
+def test_a_program_loads_through_the_viewer_like_the_oracle_loop(pkg, PM, V, oracle, dims, layout):
+    builder = R.catalogue(PM)["all_ops"]
+    bb = builder.bb
+    prog = builder.build()
+    surf = prog.as_surface()
+    assert surf.struct.sample_batch_device
+    v = V.Viewer.new_voxels(dims, bb, 3, layout=layout)
+    stream = torch.cuda.Stream()
+    v.set_stream(stream.cuda_stream)
+    r0, r1 = oracle.grid_init(dims)
+    lm = oracle.lm_new(dims, 3)
+    ref_sample = reference_sampler(oracle, builder.ops, dims, bb)
+    calls = 0
+    while v.state()["remaining"]:
+        n = v.update(surf, budget_ns=0)        # one run per call: every intermediate state is compared
+        assert n > 0
+        assert oracle.viewer_update_fn(ref_sample, dims, lm, r0, r1, max_iterations=n, bb_min=bb[:3], bb_max=bb[3:]) == n
+        t0, t1 = v.download()
+        same_bits(t0, r0, f"{dims} layout {layout} call {calls} tex0")
+        same_bits(t1, r1, f"{dims} layout {layout} call {calls} tex1")
+        calls += 1
+    assert calls >= 3 and v.state()["lod"] == 1.0
+    v.close()
+
+
+@pytest.mark.timeout(900)
+def test_device_route_host_route_and_dense_fill_agree_at_96x80x72(pkg, PM, V):
+    dims = (96, 80, 72)
+    builder = R.catalogue(PM)["all_ops"]
+    bb = builder.bb
+    prog = builder.build()
+    grid = pkg.make_grid(dims, bb[:3], bb[3:])
+    f0, f1 = pkg.alloc_textures(grid)
+    prog.fill_grid(grid, f0, f1)
+    torch.cuda.synchronize()
+    loaded = {}
+    for route in ("device", "host"):
+        surf = prog.as_surface(device_route=route == "device")
+        assert bool(surf.struct.sample_batch_device) == (route == "device")
+        v = V.Viewer.new_voxels(dims, bb, 3)
+        while v.state()["remaining"]:
+            assert v.update(surf, budget_s=0.03) > 0
+        v.commit()
+        loaded[route] = v.download()
+        if route == "device":
+            view = V.View((C.c_float * 3)(2.5, 3.0, 5.0), (C.c_float * 3)(0.0, 0.0, 0.0), (C.c_float * 3)(0.0, 1.0, 0.0), 45.0, 0.1, 1000.0)
+            frame = v.render(160, 120, view).cpu().numpy()
+        v.close()
+    for route in loaded:
+        same_bits(loaded[route][0], f0.cpu().numpy(), f"{route} route tex0 vs the dense fill")
+        same_bits(loaded[route][1], f1.cpu().numpy(), f"{route} route tex1 vs the dense fill")
+    # a frame from the viewer == a frame from the dense-filled textures (the same camera, the viewer's default uniforms)
+    rp = pkg.default_render_params(grid)
+    cam = pkg.camera_look_at(aspect=160 / 120)
+    want = pkg.raymarch(rp, f0, f1, cam, 160, 120)[0].cpu().numpy()
+    same_bits(frame, want, "a frame of the loaded viewer vs one of the dense fill")
+    assert float(np.abs(want[..., :3]).max()) > 0.0
+
+
+@pytest.mark.timeout(900)
+def test_cpp_program_sdf_loads_through_the_cpp_viewer(pkg, PM, host):
+    """A C++ ProgramSDF handed to the C++ SDFViewer::update (no C surface in between): the class's device sampler loads the
+    grid to the bits of the dense fill."""
+    host.H.sdfvh_program_sdf_new.restype, host.H.sdfvh_program_sdf_new.argtypes = C.c_void_p, [C.c_void_p]
+    host.H.sdfvh_sdf_has_device_sampler.restype, host.H.sdfvh_sdf_has_device_sampler.argtypes = C.c_int, [C.c_void_p]
+    dims = (40, 36, 28)
+    builder = R.catalogue(PM)["all_ops"]
+    prog = builder.build()
+    sdf = host.SDF(host.H.sdfvh_program_sdf_new(prog.h))
+    assert host.H.sdfvh_sdf_has_device_sampler(sdf.h) == 1
+    v = host.Viewer.new_voxels(dims, builder.bb, 3)
+    calls = 0
+    while v.remaining():
+        assert v.update(sdf, 0.03) > 0, v.last_error()
+        calls += 1
+        assert calls < 10000
+    t0, t1 = v.download()
+    grid = pkg.make_grid(dims, builder.bb[:3], builder.bb[3:])
+    f0, f1 = pkg.alloc_textures(grid)
+    prog.fill_grid(grid, f0, f1)
+    torch.cuda.synchronize()
+    same_bits(t0, f0.cpu().numpy(), "ProgramSDF through SDFViewer::update tex0 vs the dense fill")
+    same_bits(t1, f1.cpu().numpy(), "ProgramSDF through SDFViewer::update tex1 vs the dense fill")
+    del v, sdf
+
+
+@pytest.mark.timeout(900)
+def test_plain_c_program_fills_and_loads(tmp_path):
+    """tests/c/program_smoke.c: C11, no C++ and no Python between the caller and the libraries."""
+    exe = tmp_path / "program_smoke"
+    lib = os.path.join(ROOT, "sdf-viewer_amd")
+    cmd = ["gcc", "-std=c11", "-Wall", "-Wextra", "-Werror", "-O2", "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
+           "-D__HIP_PLATFORM_AMD__", os.path.join(ROOT, "tests", "c", "program_smoke.c"), "-o", str(exe), "-L", lib,
+           "-lsdfviewer_host", "-lsdfgrid", "-L", "/opt/rocm/lib", "-lamdhip64", "-lm", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "program_smoke ok" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

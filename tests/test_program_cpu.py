@@ -1,0 +1,325 @@
+"""CPU tests of SDF programs (include/sdfgrid.h "SDF programs", include/sdfprogram.h): the host mirror against a numpy
+restatement of the header's table (tests/program_ref.py), the demo anchor against the oracle, what sdfv_program_create rejects,
+and what the built kernels look like.  No device needed."""
+import ctypes as C
+import importlib
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import program_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LLVM_TOOLS = "/opt/rocm/lib/llvm/bin"
+INVALID, NO_DEVICE = -1, -4
+
+
+@pytest.fixture(scope="module")
+def PM(pkg):
+    return importlib.import_module("sdf-viewer_amd.program")
+
+
+@pytest.fixture(scope="module")
+def V(pkg):
+    return importlib.import_module("sdf-viewer_amd.viewer")
+
+
+def surface_records(V, surface, pts, distance_only, batch):
+    """The records the surface's HOST callbacks give for pts: through sample (one call per point) or sample_batch."""
+    s = surface.struct
+    out = np.full((len(pts), 7), np.nan, np.float32)
+    if batch:
+        rc = s.sample_batch(s.user, pts.ctypes.data_as(V.FP), len(pts), int(distance_only), out.ctypes.data_as(C.POINTER(V.Sample)))
+        assert rc == 0
+    else:
+        rec = V.Sample()
+        for i, p in enumerate(pts):
+            assert s.sample(s.user, (C.c_float * 3)(*p), int(distance_only), C.byref(rec)) == 0
+            out[i] = np.frombuffer(rec, np.float32)
+    return out
+
+
+def test_host_mirror_equals_the_numpy_restatement_bitwise(pkg, PM, V):
+    pts = R.points()
+    assert len(pts) >= 4096
+    used, frames_max, values_max = set(), 0, 0
+    for name, builder in R.catalogue(PM).items():
+        used |= {op for op, _ in builder.ops}
+        frames = values = 0
+        for op, _ in builder.ops:                       # the catalogue reaches the depths the header allows
+            frames += op in (R.PUSH_AFFINE, R.PUSH_SCALE)
+            frames -= op in (R.POP, R.POP_SCALE)
+            values += op in (R.SPHERE, R.CUBE, R.BOX, R.CYLINDER, R.TORUS, R.PLANE)
+            values -= op in (R.UNION, R.INTERSECT, R.SUBTRACT, R.SMOOTH_UNION, R.SMOOTH_SUBTRACT)
+            frames_max, values_max = max(frames_max, frames), max(values_max, values)
+        prog = builder.build()
+        surf = prog.as_surface()
+        assert surf.bounding_box() == tuple(np.float32(v) for v in builder.bb)
+        assert surf.struct.sample_concurrency(surf.struct.user) > 1
+        for distance_only in (False, True):
+            want = R.run(builder.ops, pts, distance_only)
+            for batch in (True, False):
+                got = surface_records(V, surf, pts, distance_only, batch)
+                bad = np.flatnonzero((got.view(np.uint32) != want.view(np.uint32)).any(axis=1))
+                assert bad.size == 0, (name, distance_only, batch, pts[bad[:4]], got[bad[:4]], want[bad[:4]])
+            if distance_only:
+                assert (want[:, 1:] == 0).all()
+        if name == "all_ops":
+            assert len(np.unique(R.run(builder.ops, pts)[:, 1:], axis=0)) >= 4  # several materials do reach the result
+    assert used == set(range(1, 19)) and frames_max == R.MAX_FRAMES and values_max == R.MAX_VALUES
+
+
+def program_sdf(host, prog):
+    """A C++ ProgramSDF over `prog` (host/program_sdf.hpp) behind the test library's SDFSurface handle."""
+    host.H.sdfvh_program_sdf_new.restype, host.H.sdfvh_program_sdf_new.argtypes = C.c_void_p, [C.c_void_p]
+    host.H.sdfvh_sdf_has_device_sampler.restype, host.H.sdfvh_sdf_has_device_sampler.argtypes = C.c_int, [C.c_void_p]
+    return host.SDF(host.H.sdfvh_program_sdf_new(prog.h))
+
+
+def test_the_cpp_class_program_sdf_equals_the_numpy_restatement_bitwise(pkg, PM, host):
+    """class ProgramSDF : SDFSurface itself -- what a C++ host constructs, and what the C surface's callbacks go through:
+    bounding_box, sample, sample_batch, name, sample_concurrency and has_device_sampler through the test library."""
+    pts = R.points()
+    for name, builder in R.catalogue(PM).items():
+        prog = builder.build()
+        sdf = program_sdf(host, prog)
+        assert tuple(sdf.bounding_box()) == tuple(np.float32(v) for v in builder.bb)
+        assert sdf.name() == "Program" and sdf.sample_concurrency() > 1 and sdf.children() == []
+        assert bool(host.H.sdfvh_sdf_has_device_sampler(sdf.h)) == (pkg.lib.sdfv_device_count() > 0)
+        for distance_only in (False, True):
+            want = R.run(builder.ops, pts, distance_only)
+            got = sdf.sample_batch(pts, distance_only)
+            bad = np.flatnonzero((got.view(np.uint32) != want.view(np.uint32)).any(axis=1))
+            assert bad.size == 0, (name, distance_only, pts[bad[:4]], got[bad[:4]], want[bad[:4]])
+            one = np.stack([sdf.sample(p, distance_only) for p in pts[::7]])
+            np.testing.assert_array_equal(one.view(np.uint32), want[::7].view(np.uint32))
+        del sdf
+    host.H.sdfvh_program_sdf_new.restype, host.H.sdfvh_program_sdf_new.argtypes = C.c_void_p, [C.c_void_p]
+    assert host.H.sdfvh_program_sdf_new(None) is None      # the constructor refuses a NULL program (it throws; the shim reports it)
+
+
+def test_the_demo_as_a_program_has_the_oracle_distance(pkg, PM, V, oracle):
+    """CUBE 0.95, SPHERE 1.05, SUBTRACT is the demo's distance (demo/mod.rs:51-61): bit for bit the oracle's, on the golden
+    points and on every voxel position of the 9 x 7 x 5 golden grid."""
+    golden = os.path.join(ROOT, "tests", "golden")
+    pts = np.ascontiguousarray(np.load(os.path.join(golden, "points_512.npz"))["points"], dtype=np.float32).reshape(-1, 3)
+    dims = (9, 7, 5)
+    axes = []
+    for a in range(3):
+        i = np.arange(dims[a], dtype=np.float32)
+        axes.append((i / (np.float32(dims[a]) - np.float32(1))) * np.float32(2.0) + np.float32(-1.0))
+    zz, yy, xx = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    vox = np.stack([xx, yy, zz], axis=-1).reshape(-1, 3).astype(np.float32)
+    allp = np.ascontiguousarray(np.concatenate([pts, vox]))
+    assert len(pts) >= 512 and len(vox) == 9 * 7 * 5
+    prog = R.catalogue(PM)["anchor"].build()
+    got = surface_records(V, prog.as_surface(), allp, True, True)
+    want = oracle.sample_many(oracle.params_from(pkg.default_params()), allp, distance_only=True)
+    want = np.asarray(want, np.float32).reshape(len(allp), -1)
+    np.testing.assert_array_equal(got[:, 0].view(np.uint32), want[:, 0].view(np.uint32))
+    np.testing.assert_array_equal(R.run(R.catalogue(PM)["anchor"].ops, allp)[:, 0].view(np.uint32), want[:, 0].view(np.uint32))
+
+
+def create_rc(pkg, ops, bb=(-1, -1, -1, 1, 1, 1), n=None, reserved=None):
+    """(status, message) of sdfv_program_create for [(opcode, operands)]; frees an accepted program."""
+    arr = (pkg._capi.ProgOp * max(len(ops), 1))()
+    for i, (op, operands) in enumerate(ops):
+        arr[i].op = op
+        for k, v in enumerate(operands):
+            arr[i].a[k] = v
+    if reserved is not None:
+        arr[reserved[0]].reserved[reserved[1]] = 1
+    h = C.c_void_p(123)
+    rc = pkg.lib.sdfv_program_create(C.cast(arr, C.c_void_p), len(ops) if n is None else n, (C.c_float * 6)(*bb), C.byref(h))
+    msg = pkg.lib.sdfv_last_error().decode()
+    if rc == 0:
+        pkg.lib.sdfv_program_free(h)
+    else:
+        assert h.value is None
+    return rc, msg
+
+
+def test_create_rejects_what_the_header_says_and_names_the_instruction(pkg, PM):
+    S, Cb, U = (R.SPHERE, (0.5,)), (R.CUBE, (0.5,)), (R.UNION, ())
+    ident = (1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0)
+    inf, nan = float("inf"), float("nan")
+    rejected = [
+        ("unknown opcode", [S, (19, ()), U], 1), ("unknown opcode", [(0, ())], 0), ("unknown opcode", [S, Cb, (0xffffffff, ())], 2),
+        ("value stack underflow", [S, U], 1), ("value stack underflow", [(R.ROUND, (0.1,))], 0),
+        ("value stack underflow", [(R.PUSH_SCALE, (2.0, 0.5)), (R.POP_SCALE, (2.0,)), S], 1),
+        ("value stack overflow", [S] * 9 + [U] * 8, 8),
+        ("frame stack overflow", [(R.PUSH_AFFINE, ident)] * 5 + [S] + [(R.POP, ())] * 5, 4),
+        ("frame stack underflow", [S, (R.POP, ())], 1),
+        ("closes a PUSH_SCALE", [(R.PUSH_SCALE, (2.0, 0.5)), S, (R.POP, ())], 2),
+        ("closes a PUSH_AFFINE", [(R.PUSH_AFFINE, ident), S, (R.POP_SCALE, (2.0,))], 2),
+        ("not finite", [S, (R.BOX, (0.1, inf, 0.1)), U], 1), ("not finite", [(R.SPHERE, (nan,))], 0),
+        ("not finite", [(R.SPHERE, (0.5, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, -inf))], 0),
+        ("must be > 0", [S, Cb, (R.SMOOTH_UNION, (0.0,))], 2), ("must be > 0", [S, Cb, (R.SMOOTH_SUBTRACT, (-0.1,))], 2),
+        ("must be > 0", [(R.PUSH_SCALE, (0.0, 1.0)), S, (R.POP_SCALE, (1.0,))], 0),
+        ("must be > 0", [(R.PUSH_SCALE, (2.0, -0.5)), S, (R.POP_SCALE, (2.0,))], 0),
+        ("must be > 0", [(R.PUSH_SCALE, (2.0, 0.5)), S, (R.POP_SCALE, (-2.0,))], 2),
+        ("open frame", [(R.PUSH_AFFINE, ident), S], 1),
+        ("values, not 1", [S, Cb], 1), ("values, not 1", [(R.MATERIAL, (1, 1, 1))], 0),
+    ]
+    for text, ops, at in rejected:
+        rc, msg = create_rc(pkg, ops)
+        assert rc == INVALID and text in msg and re.match(rf"op {at}\b", msg), (text, at, rc, msg)
+    rc, msg = create_rc(pkg, [S, Cb, U], reserved=(1, 2))
+    assert rc == INVALID and "reserved" in msg and msg.startswith("op 1 "), msg
+    # the counts and the box
+    assert create_rc(pkg, [S], n=0)[0] == INVALID
+    rc, msg = create_rc(pkg, [S] + [(R.MATERIAL, (1, 1, 1))] * 256)
+    assert rc == INVALID and "257" in msg, msg
+    for bb in ((-1, -1, -1, 1, -1, 1), (-1, -1, -1, 1, 1, -2), (-1, nan, -1, 1, 1, 1), (-1, -1, -1, inf, 1, 1)):
+        rc, msg = create_rc(pkg, [S], bb=bb)
+        assert rc == INVALID and "bounding box" in msg, (bb, msg)
+    out = C.c_void_p()
+    one = (pkg._capi.ProgOp * 1)()
+    assert pkg.lib.sdfv_program_create(None, 1, (C.c_float * 6)(-1, -1, -1, 1, 1, 1), C.byref(out)) == INVALID
+    assert pkg.lib.sdfv_program_create(C.cast(one, C.c_void_p), 1, None, C.byref(out)) == INVALID
+    pkg.lib.sdfv_program_free(None)
+    # a valid program of the maximum size that reaches both maximum depths is accepted, and handed back as it was given
+    big = [(R.PUSH_AFFINE, ident), (R.PUSH_SCALE, (2.0, 0.5)), (R.PUSH_AFFINE, ident), (R.PUSH_SCALE, (4.0, 0.25))]
+    big += [S] * 8 + [U] * 7 + [(R.POP_SCALE, (4.0,)), (R.POP, ()), (R.POP_SCALE, (2.0,)), (R.POP, ())]
+    big += [(R.MATERIAL, (0.1, 0.2, 0.3, 0.4, 0.5, 0.6))] * (256 - len(big))
+    assert len(big) == 256
+    assert create_rc(pkg, big)[0] == 0
+    b = PM.Program()
+    b.ops = [(op, tuple(float(v) for v in a)) for op, a in big]
+    prog = b.build()
+    ops, bb = prog.ops()
+    assert len(ops) == 256 and bb == (-1.0, -1.0, -1.0, 1.0, 1.0, 1.0) and (ops["reserved"] == 0).all()
+    assert [int(o) for o in ops["op"]] == [op for op, _ in big] and tuple(ops["a"][1][:2]) == (2.0, 0.5)
+    with pytest.raises(pkg.SdfvError, match="op 1 "):
+        PM.Program().sphere(0.5).union().build()
+
+
+def test_device_entry_points_need_a_device_and_compute_nothing_without_one(pkg, PM):
+    prog = R.catalogue(PM)["anchor"].build()
+    lib = pkg.lib
+    g = pkg.make_grid((4, 4, 4))
+    # argument errors come first, device or not
+    assert lib.sdfv_program_sample_points(None, 16, 1, 0, 16, None) == INVALID
+    assert lib.sdfv_program_fill_grid_commit(prog.h, C.byref(g), 16, 20, None, 0, None) == INVALID and b"16-byte" in lib.sdfv_last_error()
+    assert lib.sdfv_program_fill_grid_commit(prog.h, C.byref(g), 16, 16, None, pkg._capi.PASS_VOLUME_INTERLEAVED, None) == INVALID
+    assert lib.sdfv_program_fill_grid_commit(prog.h, C.byref(g), 16, 16, 16, 4, None) == INVALID
+    assert lib.sdfv_program_ops(None, None, None, None) == INVALID
+    if lib.sdfv_device_count() == 0:
+        pts = np.zeros((8, 3), np.float32)
+        out = np.full((8, 7), 7.0, np.float32)
+        assert lib.sdfv_program_sample_points_host(prog.h, pts.ctypes.data, 8, 0, out.ctypes.data) == NO_DEVICE
+        assert b"no HIP device" in lib.sdfv_last_error() and (out == 7.0).all()
+        assert lib.sdfv_program_sample_points(prog.h, 16, 8, 0, 16, None) == NO_DEVICE
+        assert lib.sdfv_program_fill_grid_commit(prog.h, C.byref(g), 16, 16, None, 0, None) == NO_DEVICE
+        # the surface still works on the host: only the device callback is missing
+        assert not prog.as_surface().struct.sample_batch_device
+    assert prog.as_surface().struct.sample_batch and prog.as_surface(device_route=False).struct.sample
+
+
+# ---- the built kernels (the helper pattern of tests/test_abi.py) ----
+@pytest.fixture(scope="module")
+def code_objects(tmp_path_factory):
+    """Every gfx950 code object inside libsdfgrid.so, unbundled: [(path of the .co, text of its metadata notes)]."""
+    tmp_path = tmp_path_factory.mktemp("program_code_objects")
+    lib = os.path.join(ROOT, "sdf-viewer_amd", "libsdfgrid.so")
+    if not all(os.path.exists(os.path.join(LLVM_TOOLS, t)) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf", "llvm-objdump")):
+        pytest.skip("LLVM binary tools not installed")
+    fat = tmp_path / "fat.bin"
+    subprocess.run([f"{LLVM_TOOLS}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", lib, str(tmp_path / "unused.so")], check=True)
+    blob = fat.read_bytes()
+    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)]
+    assert starts, "no offload bundle in the library"
+    out = []
+    for k, at in enumerate(starts):
+        piece = tmp_path / f"bundle{k}.bin"
+        piece.write_bytes(blob[at:starts[k + 1] if k + 1 < len(starts) else len(blob)])
+        co = tmp_path / f"bundle{k}.co"
+        subprocess.run([f"{LLVM_TOOLS}/clang-offload-bundler", "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                        f"--input={piece}", f"--output={co}"], check=True)
+        notes = subprocess.run([f"{LLVM_TOOLS}/llvm-readelf", "--notes", str(co)], check=True, capture_output=True, text=True).stdout
+        out.append((co, notes))
+    return out
+
+
+def kernel_table(code_objects):
+    table = {}
+    for co, notes in code_objects:
+        for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
+            def field(key, blk=blk):
+                return int(re.search(r"\." + key + r":\s+(\d+)", blk).group(1))
+            name = re.search(r"\n\s+\.name:\s+(\S+)\n\s+\.private_segment_fixed_size", blk).group(1)
+            table[name] = dict(vgpr=field("vgpr_count"), vgpr_spill=field("vgpr_spill_count"), sgpr_spill=field("sgpr_spill_count"),
+                               lds=field("group_segment_fixed_size"), scratch=field("private_segment_fixed_size"),
+                               kernarg=field("kernarg_segment_size"), co=co)
+    return table
+
+
+def disassembly(co, symbol):
+    text = subprocess.run([f"{LLVM_TOOLS}/llvm-objdump", "-d", str(co)], check=True, capture_output=True, text=True).stdout
+    parts = re.split(r"\n[0-9a-f]{16} <([^>]+)>:\n", text)
+    return dict(zip(parts[1::2], parts[2::2]))[symbol]
+
+
+PROGRAM_KERNELS = ("sdfprog_fill_tx64", "sdfprog_fill_tx128", "sdfprog_fill_tx256", "sdfprog_fill_tx64_nt", "sdfprog_fill_tx128_nt",
+                   "sdfprog_fill_tx256_nt", "sdfprog_sample_points", "sdfprog_sample_points_staged")
+
+
+def test_program_kernels_keep_their_state_in_registers_and_fetch_instructions_by_scalar_loads(code_objects):
+    table = kernel_table(code_objects)
+    for name in PROGRAM_KERNELS:
+        k = table[name]                                   # stable C names
+        assert k["scratch"] == 0 and k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0, (name, k)
+        # what DESIGN.md 3.6 states, as ceilings: 7 waves per SIMD (512 / 72) for the full-row fill and the samplers, 6 (512 / 80)
+        # for the fills that hold several rows per workgroup
+        assert k["vgpr"] <= (80 if ("tx64" in name or "tx128" in name) else 72), (name, k)
+        assert k["kernarg"] <= 256, (name, k)             # a pointer and a count, not the instructions
+        # [(opcode, address, branch target or None)] from the disassembly's own address column
+        ins = []
+        for ln in disassembly(k["co"], name).split("\n"):
+            m = re.match(r"\s+(\S+)[^/]*//\s*([0-9A-Fa-f]{12}):[^<]*(?:<[^>+]*\+0x([0-9a-f]+)>)?", ln)
+            if m:
+                ins.append((m.group(1), int(m.group(2), 16), None if m.group(3) is None else int(m.group(3), 16)))
+        ops = [i[0] for i in ins]
+        base = ins[0][1]
+        # the interpreter loop: the backward branch with the widest span; the instruction fetch inside it is scalar
+        back = [(at - (base + to), base + to, at) for o, at, to in ins if o.startswith(("s_cbranch", "s_branch")) and to is not None
+                and base + to < at]
+        assert back, name
+        _, lo, hi = max(back)
+        loop = [o for o, at, _ in ins if lo <= at <= hi]
+        assert len(loop) > 200, (name, len(loop))          # it does hold the eighteen instruction bodies
+        wide = [o for o in loop if re.match(r"s_load_dwordx(4|8|16)$", o)]
+        assert wide, (name, "no wide scalar load in the interpreter loop")
+        assert not any(o.startswith(("global_load", "flat_load", "buffer_load", "scratch_")) for o in loop), name
+        # outside the loop: the points (sampler) or the sRGB table (fill), nothing else is loaded per lane
+        vector_loads = [o for o in ops if o.startswith(("global_load", "flat_load", "buffer_load"))]
+        assert len(vector_loads) <= (2 if "sample_points" in name else 1), (name, vector_loads)
+    # the fill stores 16-byte texels, streamed past L2 in the _nt kernels (the fused form's default)
+    for name, nt in (("sdfprog_fill_tx256", 0), ("sdfprog_fill_tx256_nt", 2)):
+        code = [ln.split("//")[0].split() for ln in disassembly(table[name]["co"], name).split("\n")]
+        stores = [ln for ln in code if ln and ln[0] == "global_store_dwordx4"]
+        assert len(stores) == 2 and sum("nt" in ln[1:] for ln in stores) == nt, (name, stores)
+
+
+def test_program_headers_compile_as_pedantic_c99(tmp_path):
+    src = tmp_path / "program_headers.c"
+    src.write_text('#include "sdfprogram.h"\n#include "sdfgrid.h"\n'
+                   "int main(void) {\n"
+                   "    sdfv_prog_op op[3] = {{SDFV_OP_CUBE, {0, 0, 0}, {0.95f}}, {SDFV_OP_SPHERE, {0, 0, 0}, {1.05f}}, {SDFV_OP_SUBTRACT, {0, 0, 0}, {0}}};\n"
+                   "    float bb[6] = {-1, -1, -1, 1, 1, 1};\n"
+                   "    sdfv_program *p = 0;\n"
+                   "    sdfv_surface s;\n"
+                   "    if (sizeof(sdfv_prog_op) != 64 || SDFV_PROGRAM_MAX_OPS != 256) return 1;\n"
+                   "    if (sdfv_program_create(op, 3, bb, &p) != 0) return 2;\n"
+                   "    if (sdfv_program_as_surface(p, &s) != 0 || !s.sample || s.user != (void *)p) return 3;\n"
+                   "    sdfv_program_free(p);\n"
+                   "    return 0;\n}\n")
+    exe = tmp_path / "program_headers"
+    lib_dir = os.path.join(ROOT, "sdf-viewer_amd")
+    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
+                        "-o", str(exe), "-L", lib_dir, "-lsdfviewer_host", "-lsdfgrid", "-Wl,-rpath," + lib_dir], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert subprocess.run([str(exe)], timeout=120).returncode == 0
