@@ -43,6 +43,16 @@ struct FillArgs {
     uint32_t signal_value;   // starts -- the communicator's stream waits on it (hipStreamWaitValue32); nullptr = none
 };
 
+// voxel index -> position (voxel_coord): the grid's constants into any argument block that carries them under these names.
+template <typename Args>
+inline void set_voxel_coords(Args& a, const sdfv_grid& g) {
+    for (int i = 0; i < 3; ++i) {
+        a.dm1[i] = (float)g.dims[i] - 1.0f;        // scene/sdf/mod.rs:168
+        a.bb_size[i] = g.bb_max[i] - g.bb_min[i];  // scene/sdf/mod.rs:167
+        a.bb_min[i] = g.bb_min[i];
+    }
+}
+
 // Exact division of a 32-bit index by a launch constant (fill_kernels.hip div_u32).
 struct DivU32 {
     unsigned long long magic;  // floor((2^64 - 1) / d) + 1

@@ -8,159 +8,30 @@
 //   - the (y, z) coordinates of the workgroup's rows (idx/(dim-1)*size+min costs an IEEE divide per
 //     axis: x is fixed per thread and computed once, y/z once per row instead of once per voxel);
 // the demo SDF's parameter block (the "CSG-tree params") rides in the kernel arguments, i.e. SGPRs.
+// The row-chunk form's body is dense_fill_rows in kernel_common.h (shared with the SDF-program fill, program_kernels.hip),
+// which also holds the staging helpers the other dense forms here use.
 //
 // Pass kernel (fill_pass_kernel): one LoadingManager pass with stride `step` and the update_required
 // test (reads tex0.r, 4 B per visited voxel) -- the progressive / changed_box path.
 #include "fill_kernels.h"
 
-#include "demo_sdf_device.h"
+#include "kernel_common.h"
 
 namespace sdfv {
 
-__constant__ float c_srgb_lut[256] = {
-#include "srgb_lut.inc"
-};
-
 namespace {
 
-constexpr int kBlock = 256;
-
-struct LdsLut {
-    const float* p;
-    __device__ __forceinline__ float operator[](uint32_t i) const { return p[i]; }
-};
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-template <bool NT>
-__device__ __forceinline__ void store_texel(float4* dst, const float4& v) {
-    if (NT) {  // global_store_dwordx4 ... nt: write-once stream, nothing re-reads it from L2
-        v4f t = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(dst));
-    } else {
-        *dst = v;
-    }
-}
-
-// A load of data this kernel looks at ONCE (the distance volume under a pass's update_required test, tex0 under a commit):
-// nontemporal -- global_load ... nt does not allocate in L2 / the Infinity Cache, so a scan that follows a fill does not have to
-// push the fill's dirty lines out of the way first.  tools/ubench/read_stream.hip, 512 MiB read once behind 1 GiB of stores:
-// plain loads 0.128 ms (4.2 TB/s), nt loads 0.080 ms (6.7 TB/s); eight reads in a row: 6.7 vs 7.0 TB/s.  The step-1 no-op pass
-// of a loaded 512^3 grid went 0.144 -> see EXPERIMENTS R6.2.
-__device__ __forceinline__ float4 load_once(const float4* p) {
-    const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-__device__ __forceinline__ float load_once(const float* p) { return __builtin_nontemporal_load(p); }
 // ... chosen per launch (PassArgs::stream_loads, wave-uniform)
 template <typename T>
 __device__ __forceinline__ T load_scan(const T* p, uint32_t stream) {
     return stream ? load_once(p) : *p;
 }
 
-// Entry of the distance volume for voxel x of slab row `row` (= z_local * H + y) in either layout (FillArgs::dist_ilv).
-__device__ __forceinline__ uint64_t vol_index(uint32_t ilv, uint64_t row, uint32_t x, uint32_t W) {
-    return ilv ? ((row >> 1) * W + x) * 2 + (row & 1) : row * W + x;
-}
-
-// TX = lanes along x per row segment (64, 128 or 256); a workgroup owns TY = 256 / TX consecutive rows x TX
-// voxels and does ONE voxel per thread, so the grid walks memory front to back in dispatch order exactly
-// like a memset.  Measured on MI355X (profiles/r01/v1_fill_sweep.json, r01/v2_fill_sweep.json): persistent
-// strided workgroups lose 25-40 % of the store rate and 2/4/8 rows per thread lose 7/11/14 %.
-// Boundary-first order: logical workgroup `b` of a launch -> the workgroup of the memory-order grid whose voxels it
-// fills.  The first order_lead * bps workgroups are the slab's leading slices, the next bps its LAST slice, then the
-// interior in memory order.  All operands are wave-uniform (SGPRs).
-struct OrderedBlock {
-    uint32_t block;     // memory-order workgroup index
-    bool boundary;      // one of the slices a z-neighbour waits for
-    bool last_slice;    // ... the slab's last one (goes to the upper neighbour)
-};
-__device__ __forceinline__ OrderedBlock ordered_block(const FillArgs& a, uint32_t b) {
-    OrderedBlock r;
-    const uint32_t lead = a.order_lead * a.order_bps;
-    r.boundary = b < lead + a.order_bps;
-    r.last_slice = r.boundary && b >= lead;
-    r.block = r.last_slice ? (a.slab_d - 1) * a.order_bps + (b - lead) : (r.boundary ? b : b - a.order_bps);
-    return r;
-}
-
-// The boundary workgroups' packed copies (one message per neighbour and direction instead of one per texture).
-__device__ __forceinline__ void store_staged(const FillArgs& a, const OrderedBlock& ob, uint64_t o, const float4& v0,
-                                             const float4& v1) {
-    const uint64_t slice = (uint64_t)a.W * a.H;
-    float4 *d0 = nullptr, *d1 = nullptr;
-    if (ob.last_slice) {
-        if (a.stage_hi) {
-            const uint64_t w = o - (uint64_t)(a.slab_d - 1) * slice;
-            d0 = a.stage_hi + w;
-            d1 = a.stage_hi + slice + w;
-        }
-    } else if (a.stage_lo) {
-        d0 = a.stage_lo + o;  // o < order_lead * slice
-        d1 = a.stage_lo + a.order_lead * slice + o;
-    }
-    if (!d0) return;
-    *d0 = v0;
-    *d1 = v1;
-}
-
+// The row-chunk form: dense_fill_rows (kernel_common.h) over the demo tree.
 template <int TX, bool NT, typename Cfg, bool ORDERED = false>
 __global__ __launch_bounds__(kBlock) void fill_dense_kernel(FillArgs a) {
-    constexpr int TY = kBlock / TX;
-    __shared__ float s_lut[256];
-    __shared__ float2 s_yz[TY];
-
-    const uint32_t tid = threadIdx.x;
-    const uint32_t n_rows = a.H * a.slab_d;  // rows of the slab: row = z_local * H + y
-    // "this launch has started" = everything enqueued before it on its stream has finished: the multi-GPU fill step lets
-    // the communicator's stream wait on this word (hipStreamWaitValue32) instead of on an event recorded before the fill
-    if (!ORDERED && a.signal && blockIdx.x == 0 && tid == 0)
-        __hip_atomic_store(a.signal, a.signal_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    OrderedBlock ob{blockIdx.x, false, false};
-    if (ORDERED) ob = ordered_block(a, blockIdx.x + a.block_base);
-    // 1-D grid, x-chunk fastest: workgroup id -> (row group, x chunk); both uniform (SGPRs)
-    const uint32_t row_group = a.x_chunks == 1 ? ob.block : ob.block / a.x_chunks;
-    const uint32_t chunk = ob.block - row_group * a.x_chunks;
-    const uint32_t row0 = row_group * TY;
-    s_lut[tid] = c_srgb_lut[tid];
-    if (tid < TY && row0 + tid < n_rows) {
-        const uint32_t row = row0 + tid;
-        const uint32_t zl = row / a.H, y = row - zl * a.H;
-        s_yz[tid] = make_float2(voxel_coord(y, a.dm1[1], a.bb_size[1], a.bb_min[1]),
-                                voxel_coord(a.z_begin + zl, a.dm1[2], a.bb_size[2], a.bb_min[2]));
-    }
-    __syncthreads();
-
-    const LdsLut lut{s_lut};
-    const uint32_t tx = tid % TX, ty = tid / TX;
-    const uint32_t x = chunk * TX + tx;
-    const uint32_t row = row0 + ty;
-    const bool in_range = ORDERED || (x < a.W && row < n_rows);  // ordered launches cover whole workgroups only
-    const bool ilv = !ORDERED && TY >= 2 && a.dist_ilv;          // block-uniform; the launcher picks TY >= 2 for this layout
-    if (!ilv && !in_range) return;
-    float4 v0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), v1 = v0;
-    const uint64_t o = (uint64_t)row * a.W + x;
-    if (in_range) {
-        const float px = voxel_coord(x, a.dm1[0], a.bb_size[0], a.bb_min[0]);
-        const float2 yz = s_yz[ty];
-        fill_voxel<Cfg>(a.prm, a.sdf_id, px, yz.x, yz.y, lut, a.air_dist, v0, v1);
-        if (!ORDERED || !a.stage_only) {
-            store_texel<NT>(a.tex0 + o, v0);
-            store_texel<NT>(a.tex1 + o, v1);
-            if (a.dist && !ilv) a.dist[o] = v0.x;  // wave-uniform: +4 B/voxel instead of a second pass over tex0
-        }
-    }
-    if (ilv) {
-        // y-interleaved volume: rows 2p and 2p + 1 of this workgroup meet in LDS and leave as ONE row of pairs -- 8-byte
-        // stores, whole lines, from the workgroup that computed both (two workgroups writing the halves of a line would make
-        // the memory side merge partial lines).  row0 is even (TY even), and so is the slab's row count (H even).
-        __shared__ float s_d[kBlock];
-        s_d[tid] = v0.x;
-        __syncthreads();
-        if ((ty & 1u) == 0 && in_range)
-            reinterpret_cast<float2*>(a.dist)[(uint64_t)(row >> 1) * a.W + x] = make_float2(s_d[tid], s_d[tid + TX]);
-    }
-    if (ORDERED && ob.boundary) store_staged(a, ob, o, v0, v1);  // wave-uniform
+    if (!ORDERED) signal_launch_started(a);
+    dense_fill_rows<TX, NT, ORDERED>(a, DemoFillEval<Cfg>{a.prm, a.sdf_id});
 }
 
 // The dense fused fill that writes the y-INTERLEAVED volume, for widths that are multiples of 256: a thread owns voxel x of
@@ -172,19 +43,12 @@ __global__ __launch_bounds__(kBlock) void fill_dense_pairrows_kernel(FillArgs a)
     __shared__ float s_lut[256];
     __shared__ float2 s_yz[2];
     const uint32_t tid = threadIdx.x;
-    if (a.signal && blockIdx.x == 0 && tid == 0)  // see fill_dense_kernel
-        __hip_atomic_store(a.signal, a.signal_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    signal_launch_started(a);
     const uint32_t pair = a.x_chunks == 1 ? blockIdx.x : blockIdx.x / a.x_chunks;  // pair-row p of the slab: rows 2p, 2p + 1
     const uint32_t chunk = blockIdx.x - pair * a.x_chunks;
-    s_lut[tid] = c_srgb_lut[tid];
-    if (tid < 2) {
-        const uint32_t row = 2 * pair + tid;
-        const uint32_t zl = row / a.H, y = row - zl * a.H;  // (H is even: both rows lie in one slice)
-        s_yz[tid] = make_float2(voxel_coord(y, a.dm1[1], a.bb_size[1], a.bb_min[1]),
-                                voxel_coord(a.z_begin + zl, a.dm1[2], a.bb_size[2], a.bb_min[2]));
-    }
+    const LdsLut lut = stage_srgb_lut(s_lut);
+    if (tid < 2) s_yz[tid] = stage_row_yz(a, 2 * pair + tid);  // (H is even: both rows lie in one slice)
     __syncthreads();
-    const LdsLut lut{s_lut};
     const uint32_t x = chunk * kBlock + tid;  // W is a multiple of kBlock: always inside
     const float px = voxel_coord(x, a.dm1[0], a.bb_size[0], a.bb_min[0]);
     const uint64_t o = (uint64_t)(2 * pair) * a.W + x;
@@ -209,21 +73,15 @@ __global__ __launch_bounds__(kBlock) void fill_dense_ilv_paired_kernel(FillArgs 
     __shared__ float s_lut[256];
     __shared__ float2 s_yz;
     const uint32_t tid = threadIdx.x;
-    if (a.signal && blockIdx.x == 0 && tid == 0)  // see fill_dense_kernel
-        __hip_atomic_store(a.signal, a.signal_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    signal_launch_started(a);
     const uint32_t slot = blockIdx.x >> 3, unit = (slot >> 1) * 8u + (blockIdx.x & 7u), half = slot & 1u;
     if (unit >= n_units) return;  // (the grid is padded to whole groups of 16)
     const uint32_t pair = a.x_chunks == 1 ? unit : unit / a.x_chunks;
     const uint32_t chunk = unit - pair * a.x_chunks;
     const uint32_t row = 2u * pair + half;
-    s_lut[tid] = c_srgb_lut[tid];
-    if (tid == 0) {
-        const uint32_t zl = row / a.H, y = row - zl * a.H;
-        s_yz = make_float2(voxel_coord(y, a.dm1[1], a.bb_size[1], a.bb_min[1]),
-                           voxel_coord(a.z_begin + zl, a.dm1[2], a.bb_size[2], a.bb_min[2]));
-    }
+    const LdsLut lut = stage_srgb_lut(s_lut);
+    if (tid == 0) s_yz = stage_row_yz(a, row);
     __syncthreads();
-    const LdsLut lut{s_lut};
     const uint32_t x = chunk * kBlock + tid;  // W is a multiple of kBlock: always inside
     const float px = voxel_coord(x, a.dm1[0], a.bb_size[0], a.bb_min[0]);
     const uint64_t o = (uint64_t)row * a.W + x;
@@ -246,8 +104,7 @@ __global__ __launch_bounds__(kBlock) void fill_dense_flat_kernel(FillArgs a) {
     __shared__ float2 s_yz[kBlock + 1];
     const uint32_t tid = threadIdx.x;
     const uint32_t n_vox = a.W * a.H * a.slab_d;  // < 2^32, checked by the launcher
-    if (!ORDERED && a.signal && blockIdx.x == 0 && tid == 0)  // see fill_dense_kernel
-        __hip_atomic_store(a.signal, a.signal_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (!ORDERED) signal_launch_started(a);
     OrderedBlock ob{blockIdx.x, false, false};
     if (ORDERED) ob = ordered_block(a, blockIdx.x + a.block_base);  // slices are whole numbers of workgroups here
     const uint32_t v0 = ob.block * kBlock;
@@ -259,20 +116,13 @@ __global__ __launch_bounds__(kBlock) void fill_dense_flat_kernel(FillArgs a) {
     const uint32_t row_first = div_w(v0);
     const uint32_t v_last = min(v0 + kBlock - 1, n_vox - 1);
     const uint32_t n_rows_here = div_w(v_last) - row_first + 1;  // <= kBlock + 1
-    s_lut[tid] = c_srgb_lut[tid];
-    for (uint32_t r = tid; r < n_rows_here; r += kBlock) {
-        const uint32_t row = row_first + r;
-        const uint32_t zl = row / a.H, y = row - zl * a.H;
-        const uint32_t z = a.z_begin + (STRIDED ? zl * a.z_step : zl);
-        s_yz[r] = make_float2(voxel_coord(y, a.dm1[1], a.bb_size[1], a.bb_min[1]),
-                              voxel_coord(z, a.dm1[2], a.bb_size[2], a.bb_min[2]));
-    }
+    const LdsLut lut = stage_srgb_lut(s_lut);
+    for (uint32_t r = tid; r < n_rows_here; r += kBlock) s_yz[r] = stage_row_yz(a, row_first + r, STRIDED ? a.z_step : 1u);
     __syncthreads();
     const uint32_t v = v0 + tid;
     if (!ORDERED && v >= n_vox) return;  // ordered launches cover whole workgroups only
     const uint32_t row = div_w(v);
     const uint32_t x = v - row * a.W;
-    const LdsLut lut{s_lut};
     const float px = voxel_coord(x, a.dm1[0], a.bb_size[0], a.bb_min[0]);
     const float2 yz = s_yz[row - row_first];
     float4 v0t, v1t;

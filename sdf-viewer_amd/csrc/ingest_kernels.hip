@@ -12,22 +12,11 @@
 // are re-sliced per record in LDS (a stride of 7 dwords is conflict-free), like points_kernels.hip's staged form.
 #include "ingest_kernels.h"
 
-#include "demo_sdf_device.h"
+#include "kernel_common.h"
 
 namespace sdfv {
 
 namespace {
-
-constexpr int kBlock = 256;
-
-__constant__ float c_ingest_srgb_lut[256] = {
-#include "srgb_lut.inc"
-};
-
-struct LdsLut {
-    const float* p;
-    __device__ __forceinline__ float operator[](uint32_t i) const { return p[i]; }
-};
 
 template <bool ROUND>
 __global__ __launch_bounds__(kBlock) void pack_samples_kernel(PackArgs a) {
@@ -36,7 +25,7 @@ __global__ __launch_bounds__(kBlock) void pack_samples_kernel(PackArgs a) {
     const uint32_t t = threadIdx.x;
     const uint64_t first = (uint64_t)blockIdx.x * kBlock;          // first record of this workgroup
     const uint64_t here = a.n - first < kBlock ? a.n - first : kBlock;  // records it holds
-    s_lut[t] = c_ingest_srgb_lut[t];
+    const LdsLut lut = stage_srgb_lut(s_lut);
     const float* src = reinterpret_cast<const float*>(a.samples) + first * 7;
     const uint32_t words = (uint32_t)here * 7;
 #pragma unroll
@@ -49,13 +38,8 @@ __global__ __launch_bounds__(kBlock) void pack_samples_kernel(PackArgs a) {
     const uint64_t i = first + t;
     const uint64_t flat = a.index_base + (a.indices ? (uint64_t)a.indices[i] : i);
     if (flat >= a.n_voxels) return;  // not a voxel of this slab: skipped (a host may mark records it does not want stored so)
-    const float* r = s_rec + t * 7;
-    Sample s;
-    s.distance = r[0];
-    s.m.r = r[1]; s.m.g = r[2]; s.m.b = r[3];
-    s.m.metallic = r[4]; s.m.roughness = r[5]; s.m.occlusion = r[6];
     float4 t0, t1;
-    pack_sample<ROUND>(s, LdsLut{s_lut}, 0.0f, t0, t1);
+    pack_sample<ROUND>(read_record(s_rec + t * 7), lut, 0.0f, t0, t1);
     a.tex0[flat] = t0;
     float* o1 = a.tex1 + flat * 4;  // .rgb only: global_store_dwordx3
     typedef float v3f __attribute__((ext_vector_type(3)));
@@ -65,8 +49,7 @@ __global__ __launch_bounds__(kBlock) void pack_samples_kernel(PackArgs a) {
         uint64_t at = flat;
         if (a.dist_ilv) {  // FillArgs::dist_ilv: rows 2p, 2p + 1 of the slab as one row of pairs
             const uint64_t row = flat / a.W;
-            const uint64_t x = flat - row * a.W;
-            at = ((row >> 1) * a.W + x) * 2 + (row & 1);
+            at = vol_index(1u, row, flat - row * a.W, a.W);
         }
         a.dist[at] = t0.x;
     }

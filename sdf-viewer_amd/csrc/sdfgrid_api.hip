@@ -97,27 +97,32 @@ float air_dist() {
     return a + b;
 }
 
+// The part of a dense fill's kernel arguments that says WHERE it writes, for either argument block (FillArgs,
+// ProgramFillArgs: the fields dense_fill_rows reads); x_chunks is the launcher's.  `a` comes zeroed.
+template <typename Args>
+void set_grid_fill_args(Args& a, const sdfv_grid& g, float* tex0, float* tex1, float* dist = nullptr, uint32_t dist_ilv = 0) {
+    a.W = g.dims[0];
+    a.H = g.dims[1];
+    a.z_begin = g.z_begin;
+    a.slab_d = g.z_end - g.z_begin;
+    sdfv::set_voxel_coords(a, g);
+    a.air_dist = air_dist();
+    a.tex0 = reinterpret_cast<float4*>(tex0);
+    a.tex1 = reinterpret_cast<float4*>(tex1);
+    a.dist = dist;
+    a.dist_ilv = dist_ilv;
+    a.srgb_round = g_options.ext_srgb_quant;
+}
+
 sdfv::FillArgs make_fill_args(const sdfv_demo_params& p, uint32_t sdf_id, const sdfv_grid& g, float* tex0,
                               float* tex1) {
     sdfv::FillArgs a;
     memset(&a, 0, sizeof(a));
     a.prm = p;
     a.sdf_id = sdf_id;
-    a.W = g.dims[0];
-    a.H = g.dims[1];
     a.D = g.dims[2];
-    a.z_begin = g.z_begin;
-    a.slab_d = g.z_end - g.z_begin;
-    for (int i = 0; i < 3; ++i) {
-        a.dm1[i] = (float)g.dims[i] - 1.0f;           // scene/sdf/mod.rs:168
-        a.bb_size[i] = g.bb_max[i] - g.bb_min[i];      // scene/sdf/mod.rs:167
-        a.bb_min[i] = g.bb_min[i];
-    }
-    a.air_dist = air_dist();
     a.z_step = 1;
-    a.srgb_round = g_options.ext_srgb_quant;
-    a.tex0 = reinterpret_cast<float4*>(tex0);
-    a.tex1 = reinterpret_cast<float4*>(tex1);
+    set_grid_fill_args(a, g, tex0, tex1);
     return a;
 }
 
@@ -1661,21 +1666,7 @@ int sdfv_program_fill_grid_commit(const sdfv_program* p, const sdfv_grid* grid, 
     memset(&a, 0, sizeof(a));
     if (int rc = program_device_ops(p, &a.ops)) return rc;
     a.n_ops = (uint32_t)p->ops.size();
-    a.W = grid->dims[0];
-    a.H = grid->dims[1];
-    a.z_begin = grid->z_begin;
-    a.slab_d = grid->z_end - grid->z_begin;
-    for (int i = 0; i < 3; ++i) {
-        a.dm1[i] = (float)grid->dims[i] - 1.0f;            // scene/sdf/mod.rs:168
-        a.bb_size[i] = grid->bb_max[i] - grid->bb_min[i];  // scene/sdf/mod.rs:167
-        a.bb_min[i] = grid->bb_min[i];
-    }
-    a.air_dist = air_dist();
-    a.tex0 = reinterpret_cast<float4*>(tex0);
-    a.tex1 = reinterpret_cast<float4*>(tex1);
-    a.dist = dist;
-    a.dist_ilv = (flags & SDFV_PASS_VOLUME_INTERLEAVED) ? 1u : 0u;
-    a.srgb_round = g_options.ext_srgb_quant;
+    set_grid_fill_args(a, *grid, tex0, tex1, dist, (flags & SDFV_PASS_VOLUME_INTERLEAVED) ? 1u : 0u);
     a.nontemporal = fill_launch_config(dist != nullptr).nontemporal ? 1u : 0u;
     if ((uint64_t)a.H * a.slab_d > 0x7fffffffull || a.W > 0x7fffffffu)
         return fail(SDFV_ERR_INVALID_ARGUMENT, "slab of %u x %u rows is too large for one launch", a.H, a.slab_d);

@@ -20,13 +20,11 @@
 
 #include "../../include/sdfgrid.h"
 #include "api_internal.h"
-#include "demo_sdf_device.h"
+#include "kernel_common.h"
 
 namespace sdfv {
 
 namespace {
-
-constexpr int kBlock = 256;
 
 struct EmitArgs {
     uint32_t W, H;       // grid dims (x, y): flat = (z * H + y) * W + x
@@ -62,10 +60,7 @@ struct UpdateRequired {
     __device__ bool operator()(uint32_t k) const {
         const Lattice p = lattice_point(a, k);
         uint32_t at = flat_index(a, p);
-        if (a.dist_ilv) {  // entry ((row >> 1) * W + x) * 2 + (row & 1), row = z * H + y (as pack_samples_kernel writes it)
-            const uint32_t row = p.z * a.H + p.y;
-            at = ((row >> 1) * a.W + p.x) * 2 + (row & 1);
-        }
+        if (a.dist_ilv) at = vol_index(1u, p.z * a.H + p.y, p.x, a.W);  // (32-bit: the grid holds at most 2^32 voxels)
         // Check if the update is required: was AIR on initial load, or has changed since.  (scene/sdf/mod.rs:184-190)
         bool required = a.dist[at] == a.air_dist;
         if (!required && a.has_box) {
@@ -157,11 +152,7 @@ int sdfv_emit_update_points(const sdfv_grid* grid, uint32_t step, uint64_t curso
         a.ny = (uint32_t)ny;
         a.cursor = (uint32_t)cursor;
         a.n = (uint32_t)n;
-        for (int i = 0; i < 3; ++i) {
-            a.dm1[i] = (float)grid->dims[i] - 1.0f;
-            a.bb_size[i] = grid->bb_max[i] - grid->bb_min[i];
-            a.bb_min[i] = grid->bb_min[i];
-        }
+        sdfv::set_voxel_coords(a, *grid);
         a.has_box = changed_box ? 1u : 0u;
         if (changed_box) memcpy(a.box, changed_box, sizeof(a.box));
         a.dist = dist;

@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 
 import program_ref as R
+from kernel_objects import code_objects, disassembly, kernel_table  # noqa: F401 (code_objects is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM_TOOLS = "/opt/rocm/lib/llvm/bin"
 INVALID, NO_DEVICE = -1, -4
 
 
@@ -219,50 +219,7 @@ def test_device_entry_points_need_a_device_and_compute_nothing_without_one(pkg, 
     assert prog.as_surface().struct.sample_batch and prog.as_surface(device_route=False).struct.sample
 
 
-# ---- the built kernels (the helper pattern of tests/test_abi.py) ----
-@pytest.fixture(scope="module")
-def code_objects(tmp_path_factory):
-    """Every gfx950 code object inside libsdfgrid.so, unbundled: [(path of the .co, text of its metadata notes)]."""
-    tmp_path = tmp_path_factory.mktemp("program_code_objects")
-    lib = os.path.join(ROOT, "sdf-viewer_amd", "libsdfgrid.so")
-    if not all(os.path.exists(os.path.join(LLVM_TOOLS, t)) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf", "llvm-objdump")):
-        pytest.skip("LLVM binary tools not installed")
-    fat = tmp_path / "fat.bin"
-    subprocess.run([f"{LLVM_TOOLS}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", lib, str(tmp_path / "unused.so")], check=True)
-    blob = fat.read_bytes()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)]
-    assert starts, "no offload bundle in the library"
-    out = []
-    for k, at in enumerate(starts):
-        piece = tmp_path / f"bundle{k}.bin"
-        piece.write_bytes(blob[at:starts[k + 1] if k + 1 < len(starts) else len(blob)])
-        co = tmp_path / f"bundle{k}.co"
-        subprocess.run([f"{LLVM_TOOLS}/clang-offload-bundler", "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                        f"--input={piece}", f"--output={co}"], check=True)
-        notes = subprocess.run([f"{LLVM_TOOLS}/llvm-readelf", "--notes", str(co)], check=True, capture_output=True, text=True).stdout
-        out.append((co, notes))
-    return out
-
-
-def kernel_table(code_objects):
-    table = {}
-    for co, notes in code_objects:
-        for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
-            def field(key, blk=blk):
-                return int(re.search(r"\." + key + r":\s+(\d+)", blk).group(1))
-            name = re.search(r"\n\s+\.name:\s+(\S+)\n\s+\.private_segment_fixed_size", blk).group(1)
-            table[name] = dict(vgpr=field("vgpr_count"), vgpr_spill=field("vgpr_spill_count"), sgpr_spill=field("sgpr_spill_count"),
-                               lds=field("group_segment_fixed_size"), scratch=field("private_segment_fixed_size"),
-                               kernarg=field("kernarg_segment_size"), co=co)
-    return table
-
-
-def disassembly(co, symbol):
-    text = subprocess.run([f"{LLVM_TOOLS}/llvm-objdump", "-d", str(co)], check=True, capture_output=True, text=True).stdout
-    parts = re.split(r"\n[0-9a-f]{16} <([^>]+)>:\n", text)
-    return dict(zip(parts[1::2], parts[2::2]))[symbol]
-
-
+# ---- the built kernels (tests/kernel_objects.py) ----
 PROGRAM_KERNELS = ("sdfprog_fill_tx64", "sdfprog_fill_tx128", "sdfprog_fill_tx256", "sdfprog_fill_tx64_nt", "sdfprog_fill_tx128_nt",
                    "sdfprog_fill_tx256_nt", "sdfprog_sample_points", "sdfprog_sample_points_staged")
 
