@@ -390,7 +390,11 @@ int sdfv_emit_update_points(const sdfv_grid *grid, uint32_t step, uint64_t curso
  *
  * Arithmetic: IEEE f32, every step rounded on its own (nothing contracted), evaluated left to right as written:
  * a*x + b*y + c*z + d is ((a*x + b*y) + c*z) + d.  Only + - * / sqrt |x| and compares occur, so the device, the host mirror
- * (host/program_sdf.cpp) and any restatement agree bit for bit.  Operands are finite.  min(a, b) is `b < a ? b : a` and
+ * (host/program_sdf.cpp) and any restatement agree bit for bit.  Operands are finite.  POINTS may be anything: huge, subnormal,
+ * infinite or NaN coordinates are evaluated by the same rules like any other (an overflowing square is inf, inf - inf is NaN,
+ * every compare with a NaN is false), every call returns, and the other points of the batch are not affected.  The bit-for-bit
+ * promise holds for every result while no NaN arises; a distance that is NaN is a NaN with unspecified payload and sign (the
+ * material fields beside it are still those the compares, as written, select).  min(a, b) is `b < a ? b : a` and
  * max(a, b) is `a < b ? b : a`: fminf / fmaxf for finite operands, with the sign of a zero result pinned.  len(x, y, z) is
  * sqrt(x*x + y*y + z*z); q = (x, y, z); a[] are the instruction's operands, unused ones must be finite (0).
  *

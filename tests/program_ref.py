@@ -26,12 +26,16 @@ def length3(x, y, z):
     return np.sqrt(x * x + y * y + z * z)
 
 
-def run(ops, points, distance_only=False):
-    """ops: [(opcode, operands)], points: [n, 3] float32 -> [n, 7] float32 records."""
+@np.errstate(all="ignore")                     # huge and non-finite points overflow and make NaNs: that is what they are for
+def run(ops, points, distance_only=False, want_index=False, want_decided=False):
+    """ops: [(opcode, operands)], points: [n, 3] float32 -> [n, 7] float32 records (with want_index: and the index of the
+    MATERIAL instruction each record's material comes from, -1 for the initial one; with want_decided: and whether every compare
+    that chose between two materials for the point had two numbers to compare, no NaN)."""
     p = np.ascontiguousarray(points, dtype=F).reshape(-1, 3)
     n = p.shape[0]
     x, y, z = p[:, 0].copy(), p[:, 1].copy(), p[:, 2].copy()
     zero = np.zeros(n, F)
+    decided = np.ones(n, bool)
     frames, values = [], []
     cur = -1                                   # index of the current MATERIAL instruction
     for pc, (op, operands) in enumerate(ops):
@@ -75,6 +79,7 @@ def run(ops, points, distance_only=False):
             bd, bm = values.pop()
             ad, am = values.pop()
             k = a[0]
+            decided &= ~(np.isnan(ad) | np.isnan(bd))
             if op == UNION:
                 first = ad <= bd
                 d = np.where(first, ad, bd)
@@ -115,7 +120,8 @@ def run(ops, points, distance_only=False):
             if op == MATERIAL:
                 table[pc] = [F(v) for v in operands] + [F(0)] * (6 - len(operands))
         out[:, 1:] = table[m]
-    return out
+    extra = ((m,) if want_index else ()) + ((decided,) if want_decided else ())
+    return (out,) + extra if extra else out
 
 
 def _rot_z(deg):
@@ -161,12 +167,173 @@ def catalogue(program_module):
         deep.smooth_union(0.08) if i % 2 else deep.union()
     cat["deep"] = deep
     cat["sixteen"] = sixteen(program_module)
+    cat["single"] = P(bb).sphere(0.6)                                             # the shortest program there is
+    cat["envelope"] = envelope(program_module)
+    cat["late_material"] = late_material(program_module)
+    cat["ties"] = ties(program_module)
+    cat["ties_zero"] = ties_zero(program_module)
     return cat
 
 
 def sixteen(program_module):
     """The package's 16-primitive example model (what tools/program_bench.py times as its large program)."""
     return program_module.example_sixteen()
+
+
+ENVELOPE_FIRST, ENVELOPE_PLANES = 54, 85
+
+
+def envelope(program_module):
+    """Exactly 256 instructions, 85 materials: two leading MATERIALs as padding, then MATERIAL, PLANE[, UNION] 85 times; the last
+    instruction is a UNION that matters and the last MATERIAL (pc 253) wins somewhere.  Plane i is the tangent
+    d = t_i^2 - 2 t_i x of -x^2 at t_i = voxel x-position ENVELOPE_FIRST + i of a 256-wide grid over [-1, 1]:
+    d_i = (x - t_i)^2 - x^2, so the union's winner at x is the tangent touching nearest to x -- every voxel 54..138 of every row
+    has a material of its own, and voxels 64..127 (one wave of a 256-wide row) carry 64 distinct ones."""
+    s = program_module.Program((-1.0, -0.9, -0.8, 1.0, 0.9, 0.8))
+    s.material(0.0, 0.0, 1.0).material(0.0, 1.0, 0.0)
+    for i in range(ENVELOPE_PLANES):
+        t = float(F(ENVELOPE_FIRST + i) / F(255) * F(2) + F(-1))                  # the voxel position, as the fill rounds it
+        s.material((i + 1) / 128.0, 1.0 - i / 128.0, (i % 7) / 8.0, (i % 5) / 4.0, (i % 3) / 2.0, 1.0 - (i % 11) / 16.0)
+        s.plane(-2.0 * t, 0.0, 0.0, t * t)
+        if i:
+            s.union()
+    assert len(s.ops) == MAX_OPS
+    return s
+
+
+def late_material(program_module):
+    """A primitive BEFORE the first MATERIAL (it carries the initial all-zero material, the interpreter's kNoMaterial) unioned
+    with primitives after it.  The first is the plane x folded by four SHELLs into a triangle wave of period 0.25 and amplitude
+    1/16 along x; the others are shallow planes whose values lie inside that amplitude on every row of the grid, so along any row
+    the winner alternates eight times per unit length: every wave holds lanes without a material index next to lanes with one."""
+    P = program_module.Program((-1.0, -0.9, -0.8, 1.0, 0.9, 0.8))
+    P.plane(1.0, 0.0, 0.0, 0.0).shell(0.5).shell(0.25).shell(0.125).shell(0.0625)  # no material yet
+    P.material(0.9, 0.2, 0.3, 0.0, 0.5, 1.0).plane(0.0, 0.05, 0.0, 0.0).union()
+    P.material(0.2, 0.9, 0.3, 0.5, 0.25, 0.75).plane(0.0, 0.0, 0.05, 0.0).union()
+    P.material(0.3, 0.2, 0.9, 1.0, 0.75, 0.5).plane(0.25, 0.0, 0.0, 0.1875).union()
+    return P
+
+
+TIE_CENTRES = ((-0.5, -0.5), (0.5, -0.5), (-0.5, 0.5), (0.5, 0.5), (0.0, 0.0))
+
+
+def ties(program_module):
+    """The same sphere pushed twice under two different materials and combined, once per combinator, in five sub-trees joined
+    by unions: within a sub-tree EVERY point is an exact tie (a.d == b.d bit for bit), so the material is what the header's tie
+    rule says and nothing else."""
+    P = program_module.Program()
+    combine = (lambda p: p.union(), lambda p: p.intersect(), lambda p: p.subtract(), lambda p: p.smooth_union(0.125),
+               lambda p: p.smooth_subtract(0.125))
+    for i, ((cx, cy), comb) in enumerate(zip(TIE_CENTRES, combine)):
+        P.push_affine(program_module.translation(cx, cy, 0.0))
+        P.material(0.1 + 0.2 * i, 0.9, 0.1, 0.0, 0.25, 1.0).sphere(0.25)
+        P.material(0.1 + 0.2 * i, 0.1, 0.9, 1.0, 0.75, 0.5).sphere(0.25)
+        comb(P)
+        P.pop()
+        if i:
+            P.union()
+    return P
+
+
+def ties_zero(program_module):
+    """Zeros of both signs and a smooth pair exactly k apart, at the points ZERO_POINTS below (all exactly representable):
+    * SHELL: |(|x| - 0.5)| - 0.25 is +0 at |x| = 0.75 and 0.25; ROUND: (|x| - 0.25) - 0.25 is +0 at |x| = 0.5;
+    * SUBTRACT of that rounded cube from a sphere of radius 1: max(a.d, -(+0)) is -0 where a.d < 0, with b's material;
+    * POP_SCALE carries a -0 through a multiply;
+    * two planes x and x + 0.25 under SMOOTH_UNION / SMOOTH_SUBTRACT with k = 0.25: k - |a.d - b.d| == 0 wherever x + 0.25 is
+      exact."""
+    P = program_module.Program()
+    P.material(0.2, 0.4, 0.6, 0.1, 0.2, 0.3).push_scale(2.0).sphere(1.0)
+    P.material(0.6, 0.4, 0.2, 0.3, 0.2, 0.1).cube(0.25).round(0.25).subtract().pop_scale(2.0)   # -0 on the cube's surface
+    P.material(0.5, 0.5, 0.0, 0.0, 1.0, 1.0).push_affine(program_module.translation(0.0, 4.0, 0.0)).cube(0.5).shell(0.25).pop()
+    P.union()
+    P.material(1.0, 0.0, 0.0, 0.5, 0.5, 0.5).push_affine(program_module.translation(0.0, -8.0, 0.0)).plane(1.0, 0.0, 0.0, 0.0)
+    P.material(0.0, 0.0, 1.0, 0.25, 0.25, 0.25).plane(1.0, 0.0, 0.0, 0.25).smooth_union(0.25)
+    P.material(0.0, 1.0, 0.0, 0.75, 0.75, 0.75).plane(-1.0, 0.0, 0.0, 0.5).smooth_subtract(0.25)
+    P.cube(1.0).intersect().pop()
+    P.union()
+    return P
+
+
+ZERO_POINTS = [(1.0, 0, 0), (-1.0, 0.5, 0), (0.25, -1.0, 1.0), (0.5, 0.5, -1.0),           # -0: on the scaled rounded cube
+               (0.75, 4.0, 0), (0.25, 4.0, 0), (0, 4.75, 0.5), (0, 3.75, 0.25),             # +0: on the shell's two surfaces
+               (0.5, -8.0, 0), (-0.5, -8.0, 0.5), (0.125, -8.5, 0), (-0.75, -8.0, 0), (0.25, -8.0, 0), (0.375, -7.5, 0.5)]
+
+
+def grid_positions(dims, bb_min, bb_max):
+    """The fill's voxel positions, idx / (dim - 1) * size + min in three f32 roundings, x fastest: [D * H * W, 3]."""
+    axes = []
+    for a in range(3):
+        i = np.arange(dims[a], dtype=F)
+        axes.append(((i / (F(dims[a]) - F(1))) * (F(bb_max[a]) - F(bb_min[a]))) + F(bb_min[a]))
+    zz, yy, xx = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.stack([xx, yy, zz], axis=-1).reshape(-1, 3).astype(F)
+
+
+ROW_GRID = ((256, 6, 4), (-1.0, -0.9, -0.8), (1.0, 0.9, 0.8))        # 256-wide rows: four waves each
+ENVELOPE_GRID_64 = (64, 6, 4)                                        # ... and one wave per row, over the touch points alone
+
+
+def envelope_box_64():
+    t = [float(F(ENVELOPE_FIRST + i) / F(255) * F(2) + F(-1)) for i in (0, ENVELOPE_PLANES - 1)]
+    return (t[0], -0.9, -0.8), (t[1], 0.9, 0.8)
+
+
+def assert_envelope_stresses(ops, positions, width, distinct=ENVELOPE_PLANES):
+    """What `envelope` is for, asserted on the numpy restatement so that an edit to the program cannot make the comparison
+    vacuous: some 64-aligned run of every row holds at least 48 distinct material indices, `distinct` materials reach the
+    result (all 85 on a 256-wide row), and a MATERIAL at pc >= 250 wins somewhere."""
+    assert len(ops) == MAX_OPS and ops[-1][0] != MATERIAL
+    rec, m = run(ops, positions, want_index=True)
+    rows = m.reshape(-1, width)
+    for row in rows:
+        assert max(len(np.unique(row[x:x + 64])) for x in range(0, width, 64)) >= 48
+    assert len(np.unique(m)) == distinct == len(np.unique(rec[:, 1:], axis=0)) and m.max() >= 250 and m.min() >= 0
+    return rec
+
+
+def assert_late_material_stresses(ops, positions, width):
+    """What `late_material` is for: 64-aligned runs of a row that hold lanes with NO material index (-1: the initial all-zero
+    material) next to lanes with a real one -- at least half of all runs, and some with two real ones."""
+    rec, m = run(ops, positions, want_index=True)
+    runs = m.reshape(-1, 64) if width % 64 == 0 else None
+    assert runs is not None
+    mixed = [r for r in runs if (r == -1).any() and (r >= 0).any()]
+    assert 2 * len(mixed) >= len(runs) and any(len(np.unique(r)) >= 3 for r in mixed), (len(mixed), len(runs))
+    return rec
+
+
+def odd_batch():
+    """(points [n, 3], ordinary [n] bool): +-inf, NaN, +-3e38 and subnormal coordinates, alone and in pairs, every third point of
+    a batch of ordinary ones -- so every wave and every 256-point block holds both kinds.  n is not a multiple of 256."""
+    inf, nan, big, sub = np.inf, np.nan, 3e38, 1e-41
+    odd = []
+    for v in (inf, -inf, nan, big, -big, sub, -sub):
+        odd += [(v, 0.25, -0.5), (0.125, v, 0.375), (-0.25, 0.5, v), (v, v, 0.0), (v, -v, v)]
+    odd += [(inf, nan, -inf), (big, sub, -big), (nan, nan, nan), (sub, sub, -sub), (inf, big, sub), (-0.0, 0.0, -0.0)]
+    ordinary = points()[:1337].copy()
+    pts = ordinary.copy()
+    where = np.arange(1, len(pts), 3)
+    pts[where] = np.array(odd, F)[np.arange(len(where)) % len(odd)]
+    mask = np.ones(len(pts), bool)
+    mask[where] = False
+    assert len(pts) % 256 and np.isfinite(pts[mask]).all() and (np.float32(sub) != 0)
+    return pts, mask
+
+
+def assert_records_under_the_nan_rule(got, want, decided, ordinary, what):
+    """What include/sdfgrid.h promises for any point: a record whose restated distance is a number is equal bit for bit; one
+    whose restated distance is NaN has a NaN distance; material fields are equal wherever the restatement's compares had
+    numbers to compare; the ordinary points of the batch are right bit for bit whatever their neighbours are."""
+    got, want = np.ascontiguousarray(got, F), np.ascontiguousarray(want, F)
+    assert got.shape == want.shape, what
+    gb, wb = got.view(np.uint32), want.view(np.uint32)
+    number = ~np.isnan(want[:, 0])
+    assert (gb[number, 0] == wb[number, 0]).all(), (what, "a distance that is a number")
+    assert np.isnan(got[~number, 0]).all(), (what, "a distance that is NaN")
+    assert (gb[decided, 1:] == wb[decided, 1:]).all(), (what, "materials")
+    assert number[ordinary].all() and decided[ordinary].all() and (gb[ordinary] == wb[ordinary]).all(), (what, "ordinary points")
+    assert (~number).any() and number[~ordinary].any(), (what, "the batch holds both NaN and numeric results at odd points")
 
 
 def points(seed=11, n=4096):
@@ -178,6 +345,12 @@ def points(seed=11, n=4096):
                (0, 0.3, 0), (0, 0, 0.7), (0.25, 0, 0), (0.6, 0, 0.2), (0.8, 0, 0), (0, 0, -0.1), (-0.95, 0.95, 0.95),
                (2.0, 0, 0), (0, -3.5, 0), (1.5, 1.5, 1.5), (-2.0, 0.25, 7.0), (1.0, 1.0, 1.0), (-1.0, -1.0, -1.0),
                (0.35, 0, 0), (0.3, 0.3, 0.3), (0.32, 0, 0), (0, 0.55, 0), (0, -0.55, 0.125), (1e-20, -1e-20, 0)]
-    out = np.concatenate([p, np.array(awkward, F)])
+    awkward += ZERO_POINTS
+    awkward += [(cx + dx, cy, dz) for cx, cy in TIE_CENTRES for dx, dz in ((0, 0), (0.25, 0), (0.125, 0.125), (-0.375, 0))]
+    sign = lambda shape: rng.choice(np.array([-1.0, 1.0]), shape)                 # noqa: E731
+    tiny = sign((301, 3)) * 10.0 ** rng.uniform(-23.0, -18.0, (301, 3))           # squares and their sums are subnormal or 0
+    huge = sign((301, 3)) * np.minimum(10.0 ** rng.uniform(18.0, np.log10(3e38), (301, 3)), 3e38)   # squares overflow
+    out = np.concatenate([p, np.array(awkward, F), tiny.astype(F), huge.astype(F)])
+    assert np.isfinite(out).all()
     assert len(out) % 256 != 0
     return out

@@ -1,6 +1,7 @@
 """GPU tests of SDF programs: the point sampler and the dense fill of sdfv_program_* against the numpy restatement of the header's
 table (tests/program_ref.py), the demo anchor on the device, a program loaded through the viewer against the oracle's loop, and
-the plain-C path.  Every comparison is bitwise."""
+the plain-C path.  Every comparison is bitwise (but for the test of non-finite points: a NaN distance there is compared as a NaN,
+include/sdfgrid.h leaves its payload and sign open)."""
 import ctypes as C
 import importlib
 import os
@@ -54,11 +55,13 @@ def interleave(vol):
 @pytest.mark.timeout(600)
 def test_sample_points_equals_the_numpy_restatement_bitwise(pkg, PM):
     pts = R.points()
+    nan_records = 0
     dev = torch.from_numpy(pts).cuda()
     for name, builder in R.catalogue(PM).items():
         prog = builder.build()
         for distance_only in (False, True):
             want = R.run(builder.ops, pts, distance_only)
+            nan_records += int(np.isnan(want[:, 0]).sum())
             same_bits(prog.sample_points(dev, distance_only).cpu().numpy(), want, f"{name} device buffers d_only={distance_only}")
             same_bits(prog.sample_points_host(pts, distance_only), want, f"{name} host buffers d_only={distance_only}")
             for n in (1, 255, 257, 1000):                    # the scalar kernel alone, both kernels, an unaligned start
@@ -71,6 +74,60 @@ def test_sample_points_equals_the_numpy_restatement_bitwise(pkg, PM):
             same_bits(prog.sample_points(view, distance_only).cpu().numpy(), want[3:3 + 512], f"{name} unaligned")
         assert prog.sample_points(dev[:0].contiguous()).shape == (0, 7)
         assert pkg.lib.sdfv_program_sample_points(prog.h, None, 0, 0, None, None) == 0
+    assert 0 < nan_records < len(pts)                        # the huge points do make NaNs (inf - inf) in some program
+
+
+@pytest.mark.timeout(600)
+def test_sample_points_on_rows_where_a_wave_holds_many_materials(pkg, PM):
+    """The rows of the 256 x 6 x 4 grid fed to the samplers in order: `envelope` puts 64 distinct material indices into a wave,
+    `late_material` mixes lanes without an index with lanes that have one.  More than 256 points 16-byte aligned (the staged
+    kernel, then the scalar tail), a ragged batch and an unaligned one (the scalar kernel alone)."""
+    dims, bb_min, bb_max = R.ROW_GRID
+    pos = voxel_positions(dims, bb_min, bb_max)
+    dev = torch.from_numpy(pos).cuda()
+    flat = torch.empty(3 * 1000 + 1, device="cuda")
+    flat[1:] = dev[64:1064].reshape(-1)
+    unaligned = flat[1:].view(1000, 3)
+    assert dev.data_ptr() % 16 == 0 and unaligned.data_ptr() % 16 != 0 and len(pos) > 256 and len(pos[:-57]) % 256
+    for name in ("envelope", "late_material"):
+        builder = R.catalogue(PM)[name]
+        prog = builder.build()
+        if name == "envelope":
+            want = R.assert_envelope_stresses(builder.ops, pos, dims[0])
+        else:
+            want = R.assert_late_material_stresses(builder.ops, pos, dims[0])
+        same_bits(prog.sample_points(dev).cpu().numpy(), want, f"{name} rows, aligned")
+        same_bits(prog.sample_points(dev[:-57].contiguous()).cpu().numpy(), want[:-57], f"{name} rows, aligned with a tail")
+        same_bits(prog.sample_points(dev[64:64 + 191].contiguous()).cpu().numpy(), want[64:64 + 191], f"{name} rows, ragged")
+        same_bits(prog.sample_points(unaligned).cpu().numpy(), want[64:1064], f"{name} rows, unaligned")
+        same_bits(prog.sample_points_host(pos), want, f"{name} rows, host buffers")
+        same_bits(prog.sample_points(dev, True).cpu().numpy(), R.run(builder.ops, pos, True), f"{name} rows, distance only")
+
+
+@pytest.mark.timeout(600)
+def test_non_finite_and_extreme_points_on_the_device(pkg, PM, V):
+    """+-inf, NaN, +-3e38 and subnormal coordinates among ordinary points of the same waves, through the device sampler with
+    device and with host buffers and through the host callbacks: ordinary input handling.  The calls return, and the header's
+    rule for NaN results holds (R.assert_records_under_the_nan_rule)."""
+    pts, ordinary = R.odd_batch()
+    dev = torch.from_numpy(pts).cuda()
+    for name in ("all_ops", "envelope"):
+        builder = R.catalogue(PM)[name]
+        prog = builder.build()
+        surf = prog.as_surface()
+        s = surf.struct
+        for distance_only in (False, True):
+            want, decided = R.run(builder.ops, pts, distance_only, want_decided=True)
+            what = f"{name} d_only={distance_only}"
+            R.assert_records_under_the_nan_rule(prog.sample_points(dev, distance_only).cpu().numpy(), want, decided, ordinary, what + " device")
+            R.assert_records_under_the_nan_rule(prog.sample_points_host(pts, distance_only), want, decided, ordinary, what + " host buffers")
+            n = 1001                                         # the scalar kernel alone on part of it
+            R.assert_records_under_the_nan_rule(prog.sample_points(dev[:n].contiguous(), distance_only).cpu().numpy()[:n], want[:n],
+                                                decided[:n], ordinary[:n], what + " ragged")
+            out = np.full((len(pts), 7), np.nan, np.float32)
+            assert s.sample_batch(s.user, pts.ctypes.data_as(V.FP), len(pts), int(distance_only), out.ctypes.data_as(C.POINTER(V.Sample))) == 0
+            R.assert_records_under_the_nan_rule(out, want, decided, ordinary, what + " host callbacks")
+        torch.cuda.synchronize()
 
 
 def expected_textures(pkg, grid, dims, samples, srgb, layout):
@@ -87,18 +144,35 @@ def expected_textures(pkg, grid, dims, samples, srgb, layout):
 
 
 @pytest.mark.timeout(1500)
-@pytest.mark.parametrize("dims", [(9, 7, 5), (64, 64, 64), (250, 130, 66), (256, 256, 256)])
+@pytest.mark.parametrize("dims", [(9, 7, 5), (64, 64, 64), (250, 130, 66), (256, 256, 256), R.ROW_GRID[0]])
 def test_fill_equals_packing_the_numpy_samples_bitwise(pkg, PM, dims):
+    names = ("all_ops",) if dims[0] * dims[1] * dims[2] > 1 << 22 else ("all_ops", "deep", "anchor", "no_material", "envelope",
+                                                                        "late_material")
+    fill_equals_packing(pkg, PM, dims, (-1.0, -0.9, -0.8), (1.0, 0.9, 0.8), names)
+
+
+@pytest.mark.timeout(600)
+def test_fill_of_the_envelope_on_one_wave_per_row_bitwise(pkg, PM):
+    """`envelope` on a 64-wide grid over the x-range of its touch points: the tx64 kernels see 64 distinct materials in a wave."""
+    bb_min, bb_max = R.envelope_box_64()
+    fill_equals_packing(pkg, PM, R.ENVELOPE_GRID_64, bb_min, bb_max, ("envelope",))
+
+
+def fill_equals_packing(pkg, PM, dims, bb_min, bb_max, names):
     K = pkg._capi
-    bb_min, bb_max = (-1.0, -0.9, -0.8), (1.0, 0.9, 0.8)
     W, H, D = dims
     grid = pkg.make_grid(dims, bb_min, bb_max)
     pos = voxel_positions(dims, bb_min, bb_max)
-    names = ("all_ops",) if W * H * D > 1 << 22 else ("all_ops", "deep", "anchor", "no_material")
     for name in names:
         builder = R.catalogue(PM)[name]
         prog = builder.build()
         samples = R.run(builder.ops, pos)
+        # the stress programs do stress, on the reference, before anything is compared (W = 256: the tx256 kernels and, with the
+        # interleaved volume, tx128; W = 64: tx64)
+        if name == "envelope" and dims in (R.ROW_GRID[0], R.ENVELOPE_GRID_64):
+            R.assert_envelope_stresses(builder.ops, pos, W, distinct=min(W, R.ENVELOPE_PLANES))
+        if name == "late_material" and dims == R.ROW_GRID[0]:
+            R.assert_late_material_stresses(builder.ops, pos, W)
         for srgb in (0, 1):
             want = {}
             for layout in (None, "plain") + (("ilv",) if H % 2 == 0 else ()):

@@ -72,6 +72,53 @@ def test_host_mirror_equals_the_numpy_restatement_bitwise(pkg, PM, V):
     assert used == set(range(1, 19)) and frames_max == R.MAX_FRAMES and values_max == R.MAX_VALUES
 
 
+def test_edge_programs_stress_what_they_are_for_on_the_restatement(pkg, PM):
+    """`envelope` and `late_material` exist for what a WAVE of the device sees; that they do put it there is a property of the
+    numpy restatement alone, checked here and again by the GPU tests before they compare."""
+    cat = R.catalogue(PM)
+    dims, lo, hi = R.ROW_GRID
+    pos = R.grid_positions(dims, lo, hi)
+    rec, m = R.run(cat["envelope"].ops, pos, want_index=True)
+    R.assert_envelope_stresses(cat["envelope"].ops, pos, dims[0])
+    for row in m.reshape(-1, dims[0]):
+        assert len(np.unique(row[64:128])) == 64           # voxels 64..127 of every row: 64 distinct materials in one wave
+    lo64, hi64 = R.envelope_box_64()
+    R.assert_envelope_stresses(cat["envelope"].ops, R.grid_positions(R.ENVELOPE_GRID_64, lo64, hi64), 64, distinct=64)
+    R.assert_late_material_stresses(cat["late_material"].ops, pos, dims[0])
+    assert len(cat["single"].ops) == 1 and len(cat["envelope"].ops) == R.MAX_OPS
+    # `ties`: around each sub-tree's centre the two operands are the same bits, and the material is the one the header's tie
+    # rule names -- the first operand's for UNION, INTERSECT and SMOOTH_UNION, the second's for the two subtracts
+    ops = cat["ties"].ops
+    mats = [pc for pc, (op, _) in enumerate(ops) if op == R.MATERIAL]
+    assert len(mats) == 10
+    for i, (cx, cy) in enumerate(R.TIE_CENTRES):
+        near = np.array([(cx + dx, cy + dy, dz) for dx in (-0.125, 0.0, 0.0625) for dy in (-0.0625, 0.125) for dz in (0.0, 0.25)], R.F)
+        _, m = R.run(ops, near, want_index=True)
+        assert (m == mats[2 * i + (1 if i in (2, 4) else 0)]).all(), (i, m)
+    # `ties_zero`: zeros of both signs and smooth pairs exactly k apart, at the constructed points
+    z = R.run(cat["ties_zero"].ops, np.array(R.ZERO_POINTS, R.F))[:, 0]
+    assert (z[:4] == 0).all() and np.signbit(z[:4]).all() and (z[4:8] == 0).all() and not np.signbit(z[4:8]).any()
+    pts = R.points()
+    assert all((pts == np.array(p, R.F)).all(axis=1).any() for p in R.ZERO_POINTS)   # the points every bitwise test runs hold them
+    assert len(pts) % 256 != 0
+    mag = np.abs(pts).max(axis=1)
+    assert ((mag < 1e-18) & (mag > 0)).sum() >= 256 and (mag >= 1e18).sum() >= 256
+
+
+def test_non_finite_and_extreme_points_through_the_host_callbacks(pkg, PM, V):
+    """Points are not the caller's promise the way operands are: +-inf, NaN, +-3e38 and subnormal coordinates among ordinary
+    points.  The calls return; the header's rule for NaN holds (R.assert_records_under_the_nan_rule)."""
+    pts, ordinary = R.odd_batch()
+    for name in ("all_ops", "envelope"):
+        builder = R.catalogue(PM)[name]
+        surf = builder.build().as_surface()
+        for distance_only in (False, True):
+            want, decided = R.run(builder.ops, pts, distance_only, want_decided=True)
+            for batch in (True, False):
+                got = surface_records(V, surf, pts, distance_only, batch)
+                R.assert_records_under_the_nan_rule(got, want, decided, ordinary, (name, distance_only, batch))
+
+
 def program_sdf(host, prog):
     """A C++ ProgramSDF over `prog` (host/program_sdf.hpp) behind the test library's SDFSurface handle."""
     host.H.sdfvh_program_sdf_new.restype, host.H.sdfvh_program_sdf_new.argtypes = C.c_void_p, [C.c_void_p]

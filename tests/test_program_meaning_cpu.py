@@ -1,0 +1,123 @@
+"""CPU tests of what SDF programs MEAN: the host mirror (the code the kernels compile, csrc/program_eval.h) against the float64
+reference written from geometry (tests/program_geometry.py) -- primitives at points whose distance is known by construction,
+whole scenes built through the public builder helpers, materials where the reference can decide them, the smooth operators as
+properties.  The tolerance everywhere is the reference's own derived forward error bound.  No device needed."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+
+import program_geometry as G
+
+
+@pytest.fixture(scope="module")
+def PM(pkg):
+    return importlib.import_module("sdf-viewer_amd.program")
+
+
+@pytest.fixture(scope="module")
+def V(pkg):
+    return importlib.import_module("sdf-viewer_amd.viewer")
+
+
+def host_records(V, builder, pts, distance_only=False):
+    """[n, 7] records from the program's HOST callbacks (sample_batch of the surface sdfv_program_as_surface makes)."""
+    surface = builder.build().as_surface()             # (named: it owns the program for as long as the callbacks run)
+    s = surface.struct
+    pts = np.ascontiguousarray(pts, dtype=np.float32)
+    out = np.full((len(pts), 7), np.nan, np.float32)
+    assert s.sample_batch(s.user, pts.ctypes.data_as(V.FP), len(pts), int(distance_only), out.ctypes.data_as(C.POINTER(V.Sample))) == 0
+    return out
+
+
+def test_primitives_at_points_of_known_distance(pkg, PM, V):
+    """Surface point + t * outward normal has distance t (|n| t for a plane): every feature class of every primitive, bare, moved,
+    rotated and moved, scaled and under frames nested to depth 4.  Independent of the reference's case analysis -- which is
+    held to the same points here too."""
+    cases = G.known_cases()
+    assert len(cases) == (1 + 1 + 3 + 3 + 3 + 3 + 1 + 1) * len(G.FRAME_CHAINS)
+    worst, where = 0.0, None
+    for label, node, pts, known, extra in cases:
+        got = host_records(V, G.emit(node, PM), pts, True)[:, 0].astype(np.float64)
+        ref, bound, _, _ = G.evaluate(node, pts)
+        tol = bound + extra
+        assert np.isfinite(tol).all() and (tol < 1e-4).all(), label     # a bound that decides something: the distances are O(1)
+        err, ref_err = np.abs(got - known), np.abs(ref - known)
+        k = int(np.argmax(err - tol))
+        assert (err <= tol).all(), (label, pts[k], got[k], known[k], tol[k])
+        assert (ref_err <= 1e-12 + extra).all(), (label, "the float64 reference itself", float(ref_err.max()))
+        ratio = float((err / np.maximum(tol, 1e-300)).max())
+        worst, where = (ratio, label) if ratio > worst else (worst, where)
+    print(f"known-distance points: {len(cases)} cases, max error / bound = {worst:.3f} ({where})")
+    assert worst < 1.0
+
+
+SEEDS = G.SCENE_SEEDS      # chosen so that the reference leaves at most 2 % of a scene's points out of the material comparison
+
+
+def test_scenes_equal_the_float64_reference_within_its_bound(pkg, PM, V):
+    scenes = G.scenes()
+    assert len(scenes) >= 6 and set(SEEDS) == set(scenes)
+    used = set()
+    for name, scene in scenes.items():
+        builder = G.emit(scene, PM)
+        used |= {op for op, _ in builder.ops}
+        pts = G.scene_points(SEEDS[name])
+        assert len(pts) >= 4096 + G.SCENE_GRID[0] * G.SCENE_GRID[1] * G.SCENE_GRID[2]
+        ref, bound, mat, decided = G.evaluate(scene, pts)
+        # the material is compared wherever the reference itself can tell: the share it cannot is small, by the reference alone
+        excluded = 1.0 - decided.mean()
+        assert excluded <= 0.02, (name, excluded)
+        assert len(np.unique(mat[decided], axis=0)) >= 3, name
+        got = host_records(V, builder, pts)
+        err = np.abs(got[:, 0].astype(np.float64) - ref)
+        ratio = float((err / np.maximum(bound, 1e-300)).max())
+        print(f"scene {name}: {len(builder.ops)} instructions, {len(pts)} points, material left out at {100 * excluded:.2f} %, "
+              f"max error / bound = {ratio:.3f} (max error {err.max():.2e}, max bound {bound.max():.2e})")
+        k = int(np.argmax(err - bound))
+        assert (err <= bound).all(), (name, pts[k], got[k, 0], ref[k], bound[k])
+        assert np.isfinite(bound).all() and bound.max() < 1e-4, (name, bound.max())
+        wrong = np.flatnonzero(decided & (got[:, 1:].astype(np.float64) != mat).any(axis=1))
+        assert wrong.size == 0, (name, pts[wrong[:4]], got[wrong[:4]], mat[wrong[:4]])
+        assert ratio < 1.0
+        d_only = host_records(V, builder, pts, True)
+        assert (d_only[:, 0] == got[:, 0]).all() and (d_only[:, 1:] == 0).all()
+    assert used == set(range(1, 19))                   # together the scenes use every opcode ...
+    assert {op for op, _ in G.emit(scenes["every_opcode"], PM).ops} == set(range(1, 19))   # ... and one of them does alone
+
+
+def test_the_example_model_is_the_scene_that_describes_it(pkg, PM):
+    """example_sixteen() instruction for instruction from its description: translation(), rigid_inverse(), push_scale() and the
+    operand order of every builder method, as the emitter uses them."""
+    mine, theirs = G.emit(G.scene_sixteen(), PM), PM.example_sixteen()
+    assert [op for op, _ in mine.ops] == [op for op, _ in theirs.ops]
+    for pc, ((_, a), (_, b)) in enumerate(zip(mine.ops, theirs.ops)):
+        assert np.array_equal(np.array(a, np.float32), np.array(b, np.float32)), (pc, a, b)
+
+
+def test_smooth_operators_bracket_and_meet_the_hard_ones(pkg, PM, V):
+    """min - k/4 <= smooth_union <= min, and smooth_union == union where |a - b| >= k; max(a, -b) <= smooth_subtract <=
+    max(a, -b) + k/4, and smooth_subtract == subtract where |a + b| >= k.  a, b, min and max are the float64 reference's; the
+    slack is its bound."""
+    A = G.Rigid(G.Prim("box", 0.5, 0.4, 0.3, mat=(0.9, 0.1, 0.1, 0.0, 0.5, 1.0)), (-0.2, 0.0, 0.1), G.rot((1, 1, 1), 30.0))
+    Bn = G.Rigid(G.Prim("sphere", 0.45, mat=(0.1, 0.1, 0.9, 1.0, 0.5, 0.0)), (0.35, 0.1, -0.05))
+    pts = G.scene_points(31)
+    a, ea, _, _ = G.evaluate(A, pts)
+    b, eb, _, _ = G.evaluate(Bn, pts)
+    for k in (0.05, 0.125, 0.3):
+        kk = G.f32(k)
+        for kind, hard_kind, hard, low, high, gap in (
+                ("smooth_union", "union", np.minimum(a, b), -kk / 4, 0.0, np.abs(a - b)),
+                ("smooth_subtract", "subtract", np.maximum(a, -b), 0.0, kk / 4, np.abs(a + b))):
+            node = G.Comb(kind, A, Bn, k)
+            s = host_records(V, G.emit(node, PM), pts, True)[:, 0].astype(np.float64)
+            _, bound, _, _ = G.evaluate(node, pts)
+            assert (s >= hard + low - bound).all() and (s <= hard + high + bound).all(), (kind, k)
+            far = gap >= kk + ea + eb
+            assert 32 <= far.sum() < len(pts), (kind, k, far.sum())         # both regimes are sampled
+            h = host_records(V, G.emit(G.Comb(hard_kind, A, Bn), PM), pts, True)[:, 0]
+            assert (s[far].astype(np.float32) == h[far]).all(), (kind, k)   # no blend at all: the same f32
+            assert (np.abs(s[far] - hard[far]) <= bound[far]).all(), (kind, k)
+            near = gap < 0.5 * kk
+            assert near.any() and (np.abs(s[near] - hard[near]) > bound[near]).any(), (kind, k)   # ... and a blend where they meet
