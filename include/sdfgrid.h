@@ -40,7 +40,8 @@ extern "C" {
  * The descriptor is size-prefixed: further layouts / outputs are new fields, not new versions. */
 /* 5 (round 6): added sdfv_pack_samples (the device half of SDFViewer::update for host-sampled SDFs); removed
  * sdfv_tune_texture_placement / SDFV_PLACEMENT_SLACK (a probe that never beat the fixed placement in the driver's runs).
- * Still 5: the SDF programs (sdfv_prog_op, sdfv_program_*) are additions only -- nothing that existed changed meaning. */
+ * Still 5: the SDF programs (sdfv_prog_op, sdfv_program_*) and their direct march (sdfv_program_march_desc) are additions only --
+ * nothing that existed changed meaning. */
 #define SDFV_ABI_VERSION 5
 
 typedef enum sdfv_status {
@@ -589,6 +590,49 @@ typedef struct sdfv_march_desc {
     uint32_t *rgba8; /* (added in ABI 5) */
 } sdfv_march_desc;
 int sdfv_raymarch_ex(const sdfv_march_desc *desc, void *stream);
+/* ---- SDF programs rendered directly: material.frag's main() per pixel with the PROGRAM in the texture's place ----
+ * No grid: nothing is filled, nothing is resident but the program, and the surface is as sharp as f32 allows at any resolution.
+ * The per-pixel algorithm is the grid route's (primary ray, bounding-box slab test against rp->bounds_min / bounds_max, the 0.2
+ * origin shift, sdfRaycast's 256 iterations, its 1e-4 out-of-bounds and 1e-5 hit thresholds), with these differences:
+ *   - the march's distance is the program's value at the ray position itself (no 0.1 offset, no clamp, no filtering);
+ *     sdfv_march_aux.steps counts these evaluations;
+ *   - at a hit, raw0 / raw1 are the texel pair sdfv_program_fill_grid_commit would write for a voxel centred on the hit point
+ *     (SDFV_OPT_EXT_SRGB_QUANT honoured), and the shading and gl_FragDepth are sdfv_raymarch_ex's, applied to them;
+ *   - the normal is sdfNormal's four tetrahedron taps of the program's distance at hit +- h: h = normal_h when > 0, else
+ *     1 / length(rp->tex_size / rp->lod_dist_between_samples), the grid route's tap distance for that grid (a caller comparing
+ *     the routes gets the same taps).  With normal_h == 0 and a zero in rp->tex_size the call fails and says so.  tex_size and
+ *     lod_dist_between_samples are otherwise ignored;
+ *   - status -3: a hit whose accumulated distance is negative is dropped (material.frag:145), like a miss.
+ * Everything in the aux record and the depth plane is bit for bit what the host mirror (sdfprogram.h,
+ * sdfv_program_raymarch_host) computes; rgba goes through pow() and is held to 1e-4 like the grid route's.
+ * `size` = sizeof(sdfv_program_march_desc) as the CALLER compiled it, with sdfv_march_desc's rule: fields beyond it are taken as
+ * 0 / NULL, and bytes beyond what this library knows must be 0.
+ *   cameras   HOST array of n_cameras, free again when the call returns (16 ride in a launch's kernel arguments)
+ *   y0, y1    rows [y0, y1) of the width x height image; outputs hold n_cameras x (y1 - y0) x width pixels
+ *   rgba, depth, aux, rgba8   DEVICE, layouts and rgba8 rounding as in sdfv_march_desc; rgba or rgba8 is required
+ * A light-list entry that is not SDFV_LIGHT_AMBIENT fails the call, as for sdfv_raymarch_ex. */
+typedef struct sdfv_program_march_desc {
+    uint32_t size;
+    uint32_t reserved; /* 0 */
+    const sdfv_program *program;
+    const sdfv_render_params *rp;
+    const sdfv_camera *cameras;
+    uint32_t n_cameras;
+    uint32_t width, height;
+    uint32_t y0, y1;
+    float normal_h; /* 0: derive from rp, see above */
+    float *rgba;
+    float *depth;
+    sdfv_march_aux *aux;
+    uint32_t *rgba8;
+} sdfv_program_march_desc;
+/* Needs a device (SDFV_ERR_NO_DEVICE without one, nothing computed), after the argument checks. */
+int sdfv_program_raymarch(const sdfv_program_march_desc *desc, void *stream);
+/* The argument checks of sdfv_program_raymarch on their own (no device needed): on SDFV_OK *checked is the descriptor as the
+ * library reads it (absent fields 0 / NULL) and *normal_h the taps' distance it will use.  What the host mirror calls, so
+ * that both routes refuse the same descriptors with the same messages.  Output pointers are checked for alignment only. */
+int sdfv_program_raymarch_check(const sdfv_program_march_desc *desc, sdfv_program_march_desc *checked, float *normal_h);
+
 /* rows a band set holds: bands of band_height (16 or 8; 0 = 16) rows, the last one of the image possibly short */
 uint32_t sdfv_band_rows_ex(uint32_t height, uint32_t band_first, uint32_t band_step, uint32_t band_height);
 uint32_t sdfv_band_rows(uint32_t height, uint32_t band_first, uint32_t band_step); /* = ..._ex(..., 16) */

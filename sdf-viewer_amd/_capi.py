@@ -88,6 +88,17 @@ class ProgOp(C.Structure):
 
 assert C.sizeof(ProgOp) == 64
 
+
+class ProgramMarchDesc(C.Structure):
+    """sdfv_program_march_desc: the descriptor of sdfv_program_raymarch / sdfv_program_raymarch_host (size-prefixed)."""
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("program", C.c_void_p), ("rp", C.POINTER(RenderParams)),
+                ("cameras", C.POINTER(Camera)), ("n_cameras", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("y0", C.c_uint32), ("y1", C.c_uint32), ("normal_h", C.c_float), ("rgba", C.c_void_p), ("depth", C.c_void_p),
+                ("aux", C.c_void_p), ("rgba8", C.c_void_p)]
+
+
+assert C.sizeof(ProgramMarchDesc) == 88
+
 PROTOTYPES = {
     "sdfv_raymarch_ex": (C.c_int, [C.POINTER(MarchDesc), C.c_void_p]),
     "sdfv_abi_version": (C.c_uint32, []),
@@ -183,6 +194,8 @@ PROTOTYPES = {
     "sdfv_program_sample_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "sdfv_program_fill_grid_commit": (C.c_int, [C.c_void_p, C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),
+    "sdfv_program_raymarch": (C.c_int, [C.POINTER(ProgramMarchDesc), C.c_void_p]),
+    "sdfv_program_raymarch_check": (C.c_int, [C.POINTER(ProgramMarchDesc), C.POINTER(ProgramMarchDesc), C.POINTER(C.c_float)]),
 }
 LIGHT_AMBIENT, LIGHT_DIRECTIONAL, MAX_LIGHTS = 0, 1, 4
 

@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include "march_shade.h"
+
 namespace sdfv {
 namespace {
 
@@ -41,7 +43,7 @@ __device__ __forceinline__ V3 normalize(V3 a) {
     float l = length(a);
     return mk(a.x / l, a.y / l, a.z / l);
 }
-__device__ __forceinline__ float mixf(float a, float b, float t) { return a * (1.0f - t) + b * t; }
+// (mixf, shade() and the depth formula: march_shade.h, shared with the direct march of SDF programs)
 
 // GL MIRRORED_REPEAT on a texel index (general form).
 __device__ __forceinline__ uint32_t mirror_index(int i, int n) {
@@ -643,55 +645,6 @@ __device__ __forceinline__ void march_asm(const RaymarchArgs& a, const float* __
     }
 }
 
-// pow and division of the shading tail the way a GLSL compiler emits them for a GPU: exp2(y * log2(x)) and a * rcp(b) on
-// the hardware's transcendental unit (v_log_f32 / v_exp_f32 / v_rcp_f32, 1 ulp each).  The results feed outColor only, whose
-// gate is 1e-4 against the CPU restatement (libm powf, IEEE divide): measured distance 2.4e-7 at most (1.2e-7 with the
-// scene's ACES + sRGB defaults, as with ocml's powf before).  x >= 0 here;
-// x == 0 gives exp2(-inf) = 0 like powf.
-__device__ __forceinline__ float shader_pow(float x, float y) {
-    return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));
-}
-__device__ __forceinline__ float shader_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
-
-// three-d 0.18.2 tone_mapping / color_mapping (material.frag:167-168) [not vendored in the reference]
-__device__ __forceinline__ float tone_map(uint32_t type, float c) {
-    if (type == 1) c = shader_div(c, c + 1.0f);
-    else if (type == 2) c = shader_div(c * (2.51f * c + 0.03f), c * (2.43f * c + 0.59f) + 0.14f);
-    else if (type == 3) {
-        float x = fmaxf(0.0f, c - 0.004f);
-        c = shader_div(x * (6.2f * x + 0.5f), x * (6.2f * x + 1.7f) + 0.06f);
-        c = shader_pow(c, 2.2f);
-    }
-    return fminf(fmaxf(c, 0.0f), 1.0f);
-}
-__device__ __forceinline__ float color_map(uint32_t type, float c) {
-    if (type != 1) return c;
-    float ginv = 1.0f / 2.4f;
-    float select = c >= 0.0031308f ? 1.0f : 0.0f;
-    float lo = c * 12.92f;
-    float hi = 1.055f * shader_pow(c, ginv) - 0.055f;
-    return mixf(lo, hi, select);
-}
-
-// material.frag:158-173 with the scene's single ambient light (scene/mod.rs:106-110)
-__device__ __forceinline__ float4 shade(const RaymarchArgs& a, float4 raw0, float4 raw1) {
-    float metallic = raw1.x, occlusion = raw1.z;
-    float albedo[3] = {raw0.y * a.rp.tint[0], raw0.z * a.rp.tint[1], raw0.w * a.rp.tint[2]};
-    float out[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float lit = occlusion * a.rp.ambient[c] * mixf(albedo[c], 0.0f, metallic);
-        // further ambient lights of the light list: calculate_lighting sums the lights' contributions
-        for (uint32_t l = 0; l < a.rp.n_lights; ++l)
-            lit += occlusion * (a.rp.lights[l].intensity * a.rp.lights[l].color[c]) * mixf(albedo[c], 0.0f, metallic);
-        lit = tone_map(a.rp.tone_mapping, lit);
-        lit = color_map(a.rp.color_mapping, lit);
-        if (a.rp.gamma > 0.0f) lit = shader_pow(lit, a.rp.gamma);
-        out[c] = lit;
-    }
-    return make_float4(out[0], out[1], out[2], a.rp.tint[3]);
-}
-
 // outColor is written once and never re-read by this kernel: a streaming store keeps it from evicting the
 // texels the march is re-reading out of L2.
 __device__ __forceinline__ void store_rgba(float4* dst, float4 v) {
@@ -699,15 +652,11 @@ __device__ __forceinline__ void store_rgba(float4* dst, float4 v) {
     v4f t = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(dst));
 }
-// float -> 8-bit UNORM as a GL framebuffer converts it: clamp to [0, 1], scale by 255, round to nearest (even); NaN -> 0
-__device__ __forceinline__ uint32_t unorm8(float c) {
-    return (uint32_t)__float2uint_rn(fminf(fmaxf(c, 0.0f), 1.0f) * 255.0f);
-}
 // outColor into whichever output planes the caller asked for (wave-uniform pointers)
 __device__ __forceinline__ void store_color(const RaymarchArgs& a, uint64_t out_index, float4 v) {
     if (a.rgba) store_rgba(a.rgba + out_index, v);
     if (a.rgba8)
-        __builtin_nontemporal_store(unorm8(v.x) | unorm8(v.y) << 8 | unorm8(v.z) << 16 | unorm8(v.w) << 24, a.rgba8 + out_index);
+        __builtin_nontemporal_store(rgba_unorm8(v), a.rgba8 + out_index);
 }
 
 __device__ __forceinline__ void aux_clear(sdfv_march_aux& aux) {
@@ -968,12 +917,9 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
         V3 pos1 = ray_pos;
         asm volatile("" : "+v"(pos1.x) : "v"(raw0.x), "v"(raw0.y), "v"(raw0.z), "v"(raw0.w));  // same value, after raw0
         const float4 raw1 = sample_rgba<LINEAR, XF, FAST>(a, tex1, pos1);  // material.frag:154
-        rgba = shade(a, raw0, raw1);
+        rgba = shade(a.rp, raw0, raw1);
         if (a.depth) {  // gl_FragDepth, material.frag:180-181
-            const float* m = cam.bvp;
-            const float hz = m[2] * ray_pos.x + m[6] * ray_pos.y + m[10] * ray_pos.z + m[14];
-            const float hw = m[3] * ray_pos.x + m[7] * ray_pos.y + m[11] * ray_pos.z + m[15];
-            frag_depth = hz / hw;
+            frag_depth = frag_depth_of(cam.bvp, ray_pos.x, ray_pos.y, ray_pos.z);
         }
         if (NORMAL) {
             // sdfNormal, material.frag:73-80
@@ -1004,14 +950,10 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
             }
             const V3 n = normalize(mk(d1 + -d2 + -d3 + d4, -d1 + -d2 + d3 + d4, -d1 + d2 + -d3 + d4));
             if (AUX) {
-                // gl_FragDepth, material.frag:180-181
-                const float* m = cam.bvp;
-                const float hz = m[2] * ray_pos.x + m[6] * ray_pos.y + m[10] * ray_pos.z + m[14];
-                const float hw = m[3] * ray_pos.x + m[7] * ray_pos.y + m[11] * ray_pos.z + m[15];
                 aux.raw0[0] = raw0.x; aux.raw0[1] = raw0.y; aux.raw0[2] = raw0.z; aux.raw0[3] = raw0.w;
                 aux.raw1[0] = raw1.x; aux.raw1[1] = raw1.y; aux.raw1[2] = raw1.z; aux.raw1[3] = raw1.w;
                 aux.normal[0] = n.x; aux.normal[1] = n.y; aux.normal[2] = n.z;
-                aux.depth = hz / hw;
+                aux.depth = frag_depth_of(cam.bvp, ray_pos.x, ray_pos.y, ray_pos.z);  // gl_FragDepth, material.frag:180-181
             } else {
                 // keep the normal live when nobody stores it: the shader text computes it per hit
                 asm volatile("" ::"v"(n.x), "v"(n.y), "v"(n.z));
@@ -1222,7 +1164,7 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
     if (status == 1) {
         raw0 = fetch_rgba(a.tex0, hit_fp);  // == the march's last sample
         raw1 = fetch_rgba(a.tex1, hit_fp);  // material.frag:154
-        rgba = shade(a, raw0, raw1);
+        rgba = shade(a.rp, raw0, raw1);
     }
     a.rgba[pixel] = rgba;
     if (AUX) {
@@ -1233,12 +1175,9 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
         aux.hit_pos[0] = ray_pos.x; aux.hit_pos[1] = ray_pos.y; aux.hit_pos[2] = ray_pos.z;
         aux.t = dist_from_origin;
         if (status == 1) {
-            const float* m = cam.bvp;  // gl_FragDepth, material.frag:180-181
-            const float hz = m[2] * ray_pos.x + m[6] * ray_pos.y + m[10] * ray_pos.z + m[14];
-            const float hw = m[3] * ray_pos.x + m[7] * ray_pos.y + m[11] * ray_pos.z + m[15];
             aux.raw0[0] = raw0.x; aux.raw0[1] = raw0.y; aux.raw0[2] = raw0.z; aux.raw0[3] = raw0.w;
             aux.raw1[0] = raw1.x; aux.raw1[1] = raw1.y; aux.raw1[2] = raw1.z; aux.raw1[3] = raw1.w;
-            aux.depth = hz / hw;
+            aux.depth = frag_depth_of(cam.bvp, ray_pos.x, ray_pos.y, ray_pos.z);  // gl_FragDepth, material.frag:180-181
             // sdfNormal (material.frag:73-80): four taps h away from the hit; each needs the two slices around its own
             // floor(w), which can be one slice further than the march's fetch -- resident only with a second upper ghost
             // slice (or at the ends of the grid).  Without it the normal stays (0, 0, 0).

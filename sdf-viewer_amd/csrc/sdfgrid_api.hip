@@ -24,6 +24,7 @@
 #include "mesh_kernels.h"
 #include "points_kernels.h"
 #include "program_kernels.h"
+#include "program_march_kernels.h"
 #include "raymarch_kernels.h"
 
 namespace {
@@ -1671,6 +1672,76 @@ int sdfv_program_fill_grid_commit(const sdfv_program* p, const sdfv_grid* grid, 
     if ((uint64_t)a.H * a.slab_d > 0x7fffffffull || a.W > 0x7fffffffu)
         return fail(SDFV_ERR_INVALID_ARGUMENT, "slab of %u x %u rows is too large for one launch", a.H, a.slab_d);
     SDFV_HIP(sdfv::launch_program_fill(a, (hipStream_t)stream));
+    return SDFV_OK;
+}
+
+int sdfv_program_raymarch_check(const sdfv_program_march_desc* desc, sdfv_program_march_desc* checked, float* normal_h) {
+    if (!desc) return fail(SDFV_ERR_INVALID_ARGUMENT, "desc is NULL");
+    // size-prefixed like sdfv_march_desc: read what the caller's header knew, take the rest as 0 / NULL
+    constexpr size_t first_version = offsetof(sdfv_program_march_desc, rgba8) + sizeof(uint32_t*);
+    if (desc->size < first_version)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_program_march_desc.size = %u is smaller than the descriptor's first version (%zu)",
+                    desc->size, first_version);
+    sdfv_program_march_desc d;
+    memset(&d, 0, sizeof(d));
+    memcpy(&d, desc, desc->size < sizeof(d) ? desc->size : sizeof(d));
+    if (d.reserved != 0) return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_program_march_desc: reserved must be 0");
+    for (uint32_t i = (uint32_t)sizeof(d); i < desc->size; ++i)
+        if (reinterpret_cast<const unsigned char*>(desc)[i] != 0)
+            return fail(SDFV_ERR_INVALID_ARGUMENT,
+                        "sdfv_program_march_desc.size = %u: this library knows %zu bytes and byte %u beyond them is not 0", desc->size,
+                        sizeof(d), i);
+    if (!d.program) return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_program_march_desc.program is NULL");
+    if (!d.rp) return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_program_march_desc.rp is NULL");
+    if (!d.rgba && !d.rgba8) return fail(SDFV_ERR_INVALID_ARGUMENT, "no colour output: rgba and rgba8 are both NULL");
+    if (int rc = check_lights(d.rp)) return rc;
+    if ((uintptr_t)d.rgba & 15) return fail(SDFV_ERR_INVALID_ARGUMENT, "rgba must be 16-byte aligned");
+    if ((uintptr_t)d.depth & 3 || (uintptr_t)d.aux & 3 || (uintptr_t)d.rgba8 & 3)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "depth, aux and rgba8 must be 4-byte aligned");
+    if (d.n_cameras && !d.cameras) return fail(SDFV_ERR_INVALID_ARGUMENT, "cameras is NULL");
+    if (d.y0 > d.y1 || d.y1 > d.height) return fail(SDFV_ERR_INVALID_ARGUMENT, "rows [%u,%u) outside height %u", d.y0, d.y1, d.height);
+    if (!(d.normal_h >= 0.0f) || !std::isfinite(d.normal_h))
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "normal_h = %g: a distance > 0, or 0 to derive it from rp->tex_size", d.normal_h);
+    const float h = sdfv::pmarch::normal_tap_distance(*d.rp, d.normal_h);
+    if (!(h > 0.0f) || !std::isfinite(h))
+        return fail(SDFV_ERR_INVALID_ARGUMENT,
+                    "normal_h is 0 and rp->tex_size = %u x %u x %u with lod_dist_between_samples = %g gives no tap distance: set "
+                    "normal_h, or tex_size to the grid whose normals this render is compared with",
+                    d.rp->tex_size[0], d.rp->tex_size[1], d.rp->tex_size[2], d.rp->lod_dist_between_samples);
+    if (checked) *checked = d;
+    if (normal_h) *normal_h = h;
+    return SDFV_OK;
+}
+
+int sdfv_program_raymarch(const sdfv_program_march_desc* desc, void* stream) {
+    sdfv_program_march_desc d;
+    float h = 0.0f;
+    if (int rc = sdfv_program_raymarch_check(desc, &d, &h)) return rc;
+    if (int rc = need_device()) return rc;
+    if (d.n_cameras == 0 || d.width == 0 || d.y0 == d.y1) return SDFV_OK;
+    sdfv::ProgramMarchArgs a;
+    memset(&a, 0, sizeof(a));
+    if (int rc = program_device_ops(d.program, &a.f.ops)) return rc;
+    a.f.n_ops = (uint32_t)d.program->ops.size();
+    a.f.width = d.width;
+    a.f.height = d.height;
+    a.f.normal_h = h;
+    a.f.air_dist = air_dist();
+    a.f.srgb_round = g_options.ext_srgb_quant;
+    a.f.rp = *d.rp;
+    a.y0 = d.y0;
+    a.y1 = d.y1;
+    const uint64_t pixels_per_cam = (uint64_t)(d.y1 - d.y0) * d.width;
+    for (uint32_t c0 = 0; c0 < d.n_cameras; c0 += sdfv::kProgramMarchCameras) {  // the cameras ride in the kernel arguments
+        const uint32_t nc = d.n_cameras - c0 < sdfv::kProgramMarchCameras ? d.n_cameras - c0 : sdfv::kProgramMarchCameras;
+        a.n_cameras = nc;
+        memcpy(a.cameras, d.cameras + c0, nc * sizeof(sdfv_camera));
+        a.rgba = d.rgba ? reinterpret_cast<float4*>(d.rgba) + c0 * pixels_per_cam : nullptr;
+        a.rgba8 = d.rgba8 ? d.rgba8 + c0 * pixels_per_cam : nullptr;
+        a.aux = d.aux ? d.aux + c0 * pixels_per_cam : nullptr;
+        a.depth = d.depth ? d.depth + c0 * pixels_per_cam : nullptr;
+        SDFV_HIP(sdfv::launch_program_march(a, (hipStream_t)stream));
+    }
     return SDFV_OK;
 }
 

@@ -2,11 +2,14 @@
 // Built with -ffp-contract=off like the kernels: csrc/program_eval.h then rounds every step as the device does.
 #include "program_sdf.hpp"
 
+#include <atomic>
 #include <cstring>
 #include <stdexcept>
 
 #include "../../include/sdfprogram.h"
 #include "../csrc/program_eval.h"
+#include "../csrc/program_march.h"
+#include "worker_pool.hpp"
 
 namespace sdfviewer {
 namespace {
@@ -90,7 +93,67 @@ void ProgramSDF::sample_batch_device(const float* points_dev, size_t n, sdfv_sam
         throw std::runtime_error(sdfv_last_error());
 }
 
+void ProgramSDF::raymarch(const sdfv_program_march_desc& d, float normal_h, bool srgb_round, int n_threads) const {
+    sdfv::pmarch::Frame f;
+    f.ops = ops_;
+    f.n_ops = (uint32_t)n_ops_;
+    f.width = d.width;
+    f.height = d.height;
+    f.normal_h = normal_h;
+    f.air_dist = sdfv_air_dist();
+    f.srgb_round = srgb_round ? 1u : 0u;
+    f.rp = *d.rp;
+    const uint32_t rows = d.y1 - d.y0;
+    const uint64_t n_rows = (uint64_t)rows * d.n_cameras;
+    if (n_rows == 0 || d.width == 0) return;
+    // rows are dealt out one at a time: a row across the object costs many times a row of background
+    std::atomic<uint64_t> next{0};
+    const auto work = [&](unsigned) {
+        for (uint64_t r = next.fetch_add(1, std::memory_order_relaxed); r < n_rows; r = next.fetch_add(1, std::memory_order_relaxed)) {
+            const uint32_t c = (uint32_t)(r / rows), row = (uint32_t)(r % rows);
+            for (uint32_t x = 0; x < d.width; ++x) {
+                const uint64_t o = ((uint64_t)c * rows + row) * d.width + x;
+                float4 rgba;
+                sdfv_march_aux aux;
+                sdfv::pmarch::march_pixel_program(f, d.cameras[c], x, d.y0 + row, true, sdfv::kSrgbToLinear, rgba, aux);
+                if (d.rgba) {
+                    float* out = d.rgba + o * 4;
+                    out[0] = rgba.x; out[1] = rgba.y; out[2] = rgba.z; out[3] = rgba.w;
+                }
+                if (d.rgba8) d.rgba8[o] = sdfv::rgba_unorm8(rgba);
+                if (d.depth) d.depth[o] = aux.depth;
+                if (d.aux) d.aux[o] = aux;
+            }
+        }
+    };
+    unsigned n = n_threads > 0 ? (unsigned)n_threads : WorkerPool::usable_cpus();
+    if ((uint64_t)n > n_rows) n = (unsigned)n_rows;
+    WorkerPool pool;
+    pool.begin(n);
+    try {
+        pool.run(n, work);
+    } catch (...) {
+        pool.end();
+        throw;
+    }
+    pool.end();
+}
+
 }  // namespace sdfviewer
+
+extern "C" int sdfv_program_raymarch_host(const sdfv_program_march_desc* desc, int n_threads) {
+    sdfv_program_march_desc d;
+    float h = 0.0f;
+    if (int rc = sdfv_program_raymarch_check(desc, &d, &h)) return rc;
+    uint64_t srgb_round = 0;
+    if (int rc = sdfv_get_option(SDFV_OPT_EXT_SRGB_QUANT, &srgb_round)) return rc;
+    try {  // nothing crosses the C boundary
+        sdfviewer::ProgramSDF(d.program).raymarch(d, h, srgb_round != 0, n_threads);
+    } catch (...) {
+        return SDFV_ERR_INVALID_ARGUMENT;
+    }
+    return SDFV_OK;
+}
 
 // (libsdfviewer_host.so is built with default visibility: exported there, hidden in the test and provider libraries)
 extern "C" int sdfv_program_as_surface(const sdfv_program* p, sdfv_surface* out) {

@@ -21,6 +21,11 @@ class ProgramSDF final : public SDFSurface {
     bool has_device_sampler() const override;
     void sample_batch_device(const float* points_dev, size_t n, sdfv_sample* out_dev, void* stream) const override;
 
+    // The direct march on the host (include/sdfprogram.h, sdfv_program_raymarch_host): `checked` and `normal_h` as
+    // sdfv_program_raymarch_check hands them out, outputs in HOST memory; csrc/program_march.h per pixel, rows dealt to
+    // n_threads workers (<= 0: the CPUs this process may use).  srgb_round: SDFV_OPT_EXT_SRGB_QUANT.
+    void raymarch(const sdfv_program_march_desc& checked, float normal_h, bool srgb_round, int n_threads) const;
+
     const sdfv_program* program() const { return program_; }
 
    private:

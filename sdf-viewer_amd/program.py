@@ -10,6 +10,7 @@
     prog.fill_grid(grid, t0, t1)                       # the dense fill, one launch
     records = prog.sample_points(points)               # [n, 3] CUDA tensor -> [n, 7]
     viewer.update(prog.as_surface())                   # progressive load through sdf-viewer_amd.viewer
+    rgba = prog.render(camera, 1920, 1080)             # sphere-traced directly per pixel: no grid
 
 The builder only appends instructions; sdfv_program_create validates them (build() raises SdfvError with the message that
 names the offending instruction).
@@ -166,6 +167,72 @@ class CompiledProgram:
         from . import _dev_ptr, _stream_ptr
         check(lib.sdfv_program_fill_grid_commit(self.h, C.byref(grid), _dev_ptr(tex0, "tex0"), _dev_ptr(tex1, "tex1"),
                                                 None if dist is None else _dev_ptr(dist, "dist"), int(flags), _stream_ptr(stream)))
+
+    def march_desc(self, cameras, width, height, rp=None, normal_h=0.0, y0=0, y1=None):
+        """An sdfv_program_march_desc over this program without outputs (and what keeps its pointers alive).  cameras: a
+        Camera or a sequence of them; rp: RenderParams (default: the library's defaults for a 256^3 grid over the program's
+        box -- the bounds, and the grid whose normal taps normal_h == 0 stands for)."""
+        from . import default_render_params, make_grid
+        cams = list(cameras) if isinstance(cameras, (list, tuple)) else [cameras]
+        arr = (_capi.Camera * max(len(cams), 1))(*cams)
+        if rp is None:
+            _, bb = self.ops()
+            rp = default_render_params(make_grid((256, 256, 256), bb[:3], bb[3:]))
+        d = _capi.ProgramMarchDesc()
+        d.size = C.sizeof(d)
+        d.program = self.h
+        d.rp = C.pointer(rp)
+        d.cameras = C.cast(arr, C.POINTER(_capi.Camera))
+        d.n_cameras, d.width, d.height = len(cams), int(width), int(height)
+        d.y0, d.y1 = int(y0), int(height if y1 is None else y1)
+        d.normal_h = float(normal_h)
+        return d, (arr, rp)
+
+    def render(self, cameras, width, height, rp=None, normal_h=0.0, want_aux=False, want_depth=False, rgba8=False, stream=None,
+               y0=0, y1=None):
+        """sdfv_program_raymarch: rows [y0, y1) of n_cameras width x height images sphere-traced directly on the device.
+        Returns the colour -- [n, rows, width, 4] float32, or [n, rows, width] uint32-as-int32 packed RGBA8 with rgba8=True -- or a
+        tuple (colour[, aux: [n, rows, width, 18] float32 view of sdfv_march_aux][, depth: [n, rows, width]])."""
+        import torch
+        d, keep = self.march_desc(cameras, width, height, rp, normal_h, y0, y1)
+        shape = (d.n_cameras, d.y1 - d.y0, d.width)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        colour = torch.empty(shape if rgba8 else shape + (4,), dtype=torch.int32 if rgba8 else torch.float32, device=dev)
+        aux = torch.empty(shape + (18,), dtype=torch.float32, device=dev) if want_aux else None
+        depth = torch.empty(shape, dtype=torch.float32, device=dev) if want_depth else None
+        if rgba8:
+            d.rgba8 = colour.data_ptr()
+        else:
+            d.rgba = colour.data_ptr()
+        d.aux = aux.data_ptr() if want_aux else None
+        d.depth = depth.data_ptr() if want_depth else None
+        from . import _stream_ptr
+        check(lib.sdfv_program_raymarch(C.byref(d), _stream_ptr(stream)))
+        out = (colour,) + ((aux,) if want_aux else ()) + ((depth,) if want_depth else ())
+        return out[0] if len(out) == 1 else out
+
+    def render_host(self, cameras, width, height, rp=None, normal_h=0.0, want_aux=False, want_depth=False, rgba8=False, threads=0,
+                    y0=0, y1=None):
+        """sdfv_program_raymarch_host: the same render on the host (numpy arrays, same shapes; aux as a [..., 18] float32 view),
+        by the per-pixel source the kernel is built from; needs no device."""
+        import numpy as np
+        from . import viewer
+        fn = viewer.lib.sdfv_program_raymarch_host
+        fn.restype, fn.argtypes = C.c_int, [C.POINTER(_capi.ProgramMarchDesc), C.c_int]
+        d, keep = self.march_desc(cameras, width, height, rp, normal_h, y0, y1)
+        shape = (d.n_cameras, d.y1 - d.y0, d.width)
+        colour = np.empty(shape if rgba8 else shape + (4,), np.uint32 if rgba8 else np.float32)
+        aux = np.empty(shape + (18,), np.float32) if want_aux else None
+        depth = np.empty(shape, np.float32) if want_depth else None
+        if rgba8:
+            d.rgba8 = colour.ctypes.data
+        else:
+            d.rgba = colour.ctypes.data
+        d.aux = aux.ctypes.data if want_aux else None
+        d.depth = depth.ctypes.data if want_depth else None
+        check(fn(C.byref(d), int(threads)))
+        out = (colour,) + ((aux,) if want_aux else ()) + ((depth,) if want_depth else ())
+        return out[0] if len(out) == 1 else out
 
     def as_surface(self, device_route=True):
         """A viewer.Surface over this program (sdfv_program_as_surface); device_route=False clears sample_batch_device, so
