@@ -22,9 +22,8 @@ __device__ __forceinline__ void program_march(const ProgramMarchArgs& a) {
     const LdsLut lut = stage_srgb_lut(s_lut);
     __syncthreads();
 
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t px = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-    const uint32_t row = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);  // row of the output
+    uint32_t px, row;  // row of the output
+    march::tile_pixel(blockIdx.x, blockIdx.y, px, row);
     const uint32_t py = a.y0 + row;
     const uint32_t cam_idx = blockIdx.z;
     const bool in_image = px < a.f.width && py < a.y1;
@@ -35,11 +34,7 @@ __device__ __forceinline__ void program_march(const ProgramMarchArgs& a) {
     sdfv_march_aux aux;
     pmarch::march_pixel_program(a.f, cam, px, py, in_image, lut, rgba, aux);
     if (!in_image) return;
-    if (a.rgba) {
-        const v4f t = {rgba.x, rgba.y, rgba.z, rgba.w};
-        __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(a.rgba + out_index));
-    }
-    if (a.rgba8) __builtin_nontemporal_store(rgba_unorm8(rgba), a.rgba8 + out_index);
+    march::store_color(a, out_index, rgba);
     if (a.depth) a.depth[out_index] = aux.depth;
     if (AUX) a.aux[out_index] = aux;
 }

@@ -27,23 +27,13 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
-#include "march_shade.h"
+#include "march_common.h"
 
 namespace sdfv {
 namespace {
 
-struct V3 {
-    float x, y, z;
-};
-__device__ __forceinline__ V3 mk(float x, float y, float z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 madd(V3 a, V3 d, float t) { return mk(a.x + d.x * t, a.y + d.y * t, a.z + d.z * t); }
-__device__ __forceinline__ float length(V3 a) { return sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }
-__device__ __forceinline__ V3 normalize(V3 a) {
-    float l = length(a);
-    return mk(a.x / l, a.y / l, a.z / l);
-}
-// (mixf, shade() and the depth formula: march_shade.h, shared with the direct march of SDF programs)
+using namespace march;  // V3, the ray set-up, the taps, the record and the stores: march_common.h, shared with the direct
+                        // march of SDF programs (mixf, shade() and the depth formula: march_shade.h)
 
 // GL MIRRORED_REPEAT on a texel index (general form).
 __device__ __forceinline__ uint32_t mirror_index(int i, int n) {
@@ -172,10 +162,7 @@ __device__ __forceinline__ float oob_dist(const RaymarchArgs& a, V3 p) {
         return fmaxf(fabsf(p.x) - a.rp.bounds_max[0],
                      fmaxf(fabsf(p.y) - a.rp.bounds_max[1], fabsf(p.z) - a.rp.bounds_max[2]));
     }
-    float ox = fmaxf(a.rp.bounds_min[0] - p.x, p.x - a.rp.bounds_max[0]);
-    float oy = fmaxf(a.rp.bounds_min[1] - p.y, p.y - a.rp.bounds_max[1]);
-    float oz = fmaxf(a.rp.bounds_min[2] - p.z, p.z - a.rp.bounds_max[2]);
-    return fmaxf(ox, fmaxf(oy, oz));
+    return march::oob_dist(a.rp, p);
 }
 
 // sdfRaycast's loop (material.frag:97-126) for the LINEAR filter, with everything the loop does not need
@@ -645,30 +632,6 @@ __device__ __forceinline__ void march_asm(const RaymarchArgs& a, const float* __
     }
 }
 
-// outColor is written once and never re-read by this kernel: a streaming store keeps it from evicting the
-// texels the march is re-reading out of L2.
-__device__ __forceinline__ void store_rgba(float4* dst, float4 v) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    v4f t = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(dst));
-}
-// outColor into whichever output planes the caller asked for (wave-uniform pointers)
-__device__ __forceinline__ void store_color(const RaymarchArgs& a, uint64_t out_index, float4 v) {
-    if (a.rgba) store_rgba(a.rgba + out_index, v);
-    if (a.rgba8)
-        __builtin_nontemporal_store(rgba_unorm8(v), a.rgba8 + out_index);
-}
-
-__device__ __forceinline__ void aux_clear(sdfv_march_aux& aux) {
-    aux.status = 0; aux.steps = 0;
-    aux.hit_pos[0] = aux.hit_pos[1] = aux.hit_pos[2] = 0.0f;
-    aux.t = 0.0f;
-    aux.raw0[0] = aux.raw0[1] = aux.raw0[2] = aux.raw0[3] = 0.0f;
-    aux.raw1[0] = aux.raw1[1] = aux.raw1[2] = aux.raw1[3] = 0.0f;
-    aux.normal[0] = aux.normal[1] = aux.normal[2] = 0.0f;
-    aux.depth = 1.0f;
-}
-
 #ifdef SDFV_TUNING
 __device__ __forceinline__ void stamp_wave(const RaymarchArgs& a, uint32_t bx, uint32_t by, uint32_t wave,
                                            unsigned long long t_start, unsigned long long t_start_rt, int iterations,
@@ -686,33 +649,17 @@ __device__ __forceinline__ void stamp_wave(const RaymarchArgs& a, uint32_t bx, u
 }
 #endif
 
-// Primary ray through the centre of pixel (px, py) (image row 0 = top), not yet normalised.
 __device__ __forceinline__ V3 pixel_ray_raw(const RaymarchArgs& a, const sdfv_camera& cam, uint32_t px, uint32_t py) {
-    const float ndc_x = (((float)px + 0.5f) / (float)a.width) * 2.0f - 1.0f;
-    const float ndc_y = 1.0f - (((float)py + 0.5f) / (float)a.height) * 2.0f;
-    const float sx = ndc_x * cam.aspect * cam.tan_half_fovy;
-    const float sy = ndc_y * cam.tan_half_fovy;
-    return mk(cam.forward[0] + cam.right[0] * sx + cam.up[0] * sy,
-              cam.forward[1] + cam.right[1] * sx + cam.up[1] * sy,
-              cam.forward[2] + cam.right[2] * sx + cam.up[2] * sy);
+    return march::pixel_ray_raw(a.width, a.height, cam, px, py);
 }
 
-// The bbox fragment of that ray (slab test standing in for the rasterised cube, scene/sdf/mod.rs:254-282) and
-// main()'s ray set-up, material.frag:133-139.  Returns whether the pixel is covered by the box.
+// The bbox fragment of that ray and main()'s ray set-up (march_common.h).  Returns whether the pixel is covered by the box.
 __device__ __forceinline__ bool box_fragment_ray(const RaymarchArgs& a, V3 eye, V3 d_raw, bool in_image,
                                                  V3& ray_origin, V3& ray_dir) {
     const V3 d0 = normalize(d_raw);
-    const float tx1 = (a.rp.bounds_min[0] - eye.x) / d0.x, tx2 = (a.rp.bounds_max[0] - eye.x) / d0.x;
-    const float ty1 = (a.rp.bounds_min[1] - eye.y) / d0.y, ty2 = (a.rp.bounds_max[1] - eye.y) / d0.y;
-    const float tz1 = (a.rp.bounds_min[2] - eye.z) / d0.z, tz2 = (a.rp.bounds_max[2] - eye.z) / d0.z;
-    const float tnear = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2));
-    const float tfar = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
-    const bool covered = in_image && (tfar >= tnear && tfar > 0.0f);
-    const float tfrag = tnear > 0.0f ? tnear : tfar;
-    const V3 pos = madd(eye, d0, tfrag);
-    ray_origin = pos;
-    ray_dir = normalize(sub(ray_origin, eye));
-    if (oob_dist<false>(a, madd(ray_origin, ray_dir, 0.2f)) > 0.0f) ray_origin = madd(eye, ray_dir, 0.2f);
+    float tfrag;
+    const bool covered = box_slab_test(a.rp, eye, d0, in_image, tfrag);
+    fragment_ray(a.rp, eye, d0, tfrag, ray_origin, ray_dir);
     return covered;
 }
 
@@ -732,8 +679,9 @@ template <int MODE, bool LINEAR, int XF, bool SYMM, bool AUX, bool ASM = false, 
 __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(RaymarchArgs a) {
     constexpr bool FAST = MODE != 0;
     static_assert(NORMAL || !AUX, "the aux record carries the normal");
-    // 8x8 pixel tile per wave, 2x2 waves per workgroup
+#ifdef SDFV_TUNING
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#endif
     uint32_t bx = blockIdx.x, by = blockIdx.y;
 #ifdef SDFV_TUNING
     if (a.tile_order) {  // 1-D launch over the tiles, in the order given
@@ -792,8 +740,8 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
         by = (gy << g) + (t >> g);
         if (bx >= a.tiles_x || by >= a.tiles_y) return;  // padding of the last groups
     }
-    const uint32_t px = bx * 16 + (wave & 1) * 8 + (lane & 7);
-    const uint32_t row = by * 16 + (wave >> 1) * 8 + (lane >> 3);  // row of the output: within [y0, y1), or of the bands
+    uint32_t px, row;  // row of the output: within [y0, y1), or of the bands
+    tile_pixel(bx, by, px, row);
     const uint32_t py = a.y0 + row + (row >> a.band_shift) * a.band_skip;  // band k of the set = rows [k << shift, ...) of the output
     const uint32_t cam_idx = blockIdx.z;
     const bool in_image = px < a.width && py < a.y1;
@@ -900,12 +848,7 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
     sdfv_march_aux aux;
     if (AUX) {
         aux_clear(aux);
-        if (covered) {
-            aux.status = status;
-            aux.steps = steps;
-            aux.hit_pos[0] = ray_pos.x; aux.hit_pos[1] = ray_pos.y; aux.hit_pos[2] = ray_pos.z;
-            aux.t = dist_from_origin;
-        }
+        if (covered) aux_set_march(aux, status, steps, ray_pos, dist_from_origin);
     }
     if (status == 1) {
         // The fast kernels know the hit point is within 1e-4 of the box; the normal's taps are h further out,
@@ -923,14 +866,8 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
         }
         if (NORMAL) {
             // sdfNormal, material.frag:73-80
-            const float sxn = (float)tex0.w / a.rp.lod_dist_between_samples;
-            const float syn = (float)tex0.h / a.rp.lod_dist_between_samples;
-            const float szn = (float)tex0.d / a.rp.lod_dist_between_samples;
-            const float h = 1.0f / sqrtf(sxn * sxn + syn * syn + szn * szn);
-            const V3 p1 = mk(ray_pos.x + h, ray_pos.y - h, ray_pos.z - h);  // k.xyy
-            const V3 p2 = mk(ray_pos.x - h, ray_pos.y - h, ray_pos.z + h);  // k.yyx
-            const V3 p3 = mk(ray_pos.x - h, ray_pos.y + h, ray_pos.z - h);  // k.yxy
-            const V3 p4 = mk(ray_pos.x + h, ray_pos.y + h, ray_pos.z + h);  // k.xxx
+            const float h = tap_distance((float)tex0.w, (float)tex0.h, (float)tex0.d, a.rp.lod_dist_between_samples);
+            const V3 p1 = normal_tap(ray_pos, h, 0), p2 = normal_tap(ray_pos, h, 1), p3 = normal_tap(ray_pos, h, 2), p4 = normal_tap(ray_pos, h, 3);
             float d1, d2, d3, d4;
             if (MODE >= 2 && a.dist && a.fast_normal) {  // the taps read the compact distance volume too
                 d1 = sample_r_linear<XF, true, 1>(a, a.dist, tex0, p1) - 1e-1f;
@@ -948,12 +885,9 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
                 d3 = sample_r<LINEAR, XF, false>(a, tex0, p3) - 1e-1f;
                 d4 = sample_r<LINEAR, XF, false>(a, tex0, p4) - 1e-1f;
             }
-            const V3 n = normalize(mk(d1 + -d2 + -d3 + d4, -d1 + -d2 + d3 + d4, -d1 + d2 + -d3 + d4));
+            const V3 n = normal_of_taps(d1, d2, d3, d4);
             if (AUX) {
-                aux.raw0[0] = raw0.x; aux.raw0[1] = raw0.y; aux.raw0[2] = raw0.z; aux.raw0[3] = raw0.w;
-                aux.raw1[0] = raw1.x; aux.raw1[1] = raw1.y; aux.raw1[2] = raw1.z; aux.raw1[3] = raw1.w;
-                aux.normal[0] = n.x; aux.normal[1] = n.y; aux.normal[2] = n.z;
-                aux.depth = frag_depth_of(cam.bvp, ray_pos.x, ray_pos.y, ray_pos.z);  // gl_FragDepth, material.frag:180-181
+                aux_set_hit(aux, raw0, raw1, n, frag_depth_of(cam.bvp, ray_pos.x, ray_pos.y, ray_pos.z));
             } else {
                 // keep the normal live when nobody stores it: the shader text computes it per hit
                 asm volatile("" ::"v"(n.x), "v"(n.y), "v"(n.z));
@@ -1170,24 +1104,16 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
     if (AUX) {
         sdfv_march_aux aux;
         aux_clear(aux);
-        aux.status = status;
-        aux.steps = steps;
-        aux.hit_pos[0] = ray_pos.x; aux.hit_pos[1] = ray_pos.y; aux.hit_pos[2] = ray_pos.z;
-        aux.t = dist_from_origin;
+        aux_set_march(aux, status, steps, ray_pos, dist_from_origin);
         if (status == 1) {
-            aux.raw0[0] = raw0.x; aux.raw0[1] = raw0.y; aux.raw0[2] = raw0.z; aux.raw0[3] = raw0.w;
-            aux.raw1[0] = raw1.x; aux.raw1[1] = raw1.y; aux.raw1[2] = raw1.z; aux.raw1[3] = raw1.w;
-            aux.depth = frag_depth_of(cam.bvp, ray_pos.x, ray_pos.y, ray_pos.z);  // gl_FragDepth, material.frag:180-181
+            const float depth = frag_depth_of(cam.bvp, ray_pos.x, ray_pos.y, ray_pos.z);
+            aux_set_hit(aux, raw0, raw1, mk(0.0f, 0.0f, 0.0f), depth);
             // sdfNormal (material.frag:73-80): four taps h away from the hit; each needs the two slices around its own
             // floor(w), which can be one slice further than the march's fetch -- resident only with a second upper ghost
             // slice (or at the ends of the grid).  Without it the normal stays (0, 0, 0).
             if (a.fast_normal) {
-                const float sxn = (float)tex.w / a.rp.lod_dist_between_samples;
-                const float syn = (float)tex.h / a.rp.lod_dist_between_samples;
-                const float szn = (float)tex.d / a.rp.lod_dist_between_samples;
-                const float h = 1.0f / sqrtf(sxn * sxn + syn * syn + szn * szn);
-                const V3 taps[4] = {mk(ray_pos.x + h, ray_pos.y - h, ray_pos.z - h), mk(ray_pos.x - h, ray_pos.y - h, ray_pos.z + h),
-                                    mk(ray_pos.x - h, ray_pos.y + h, ray_pos.z - h), mk(ray_pos.x + h, ray_pos.y + h, ray_pos.z + h)};
+                const float h = tap_distance((float)tex.w, (float)tex.h, (float)tex.d, a.rp.lod_dist_between_samples);
+                const V3 taps[4] = {normal_tap(ray_pos, h, 0), normal_tap(ray_pos, h, 1), normal_tap(ray_pos, h, 2), normal_tap(ray_pos, h, 3)};
                 float d[4];
                 bool resident = true;
 #pragma unroll
@@ -1206,10 +1132,7 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
                                        dist_r[(uint64_t)f.o011 * 4], dist_r[(uint64_t)f.o111 * 4], f.ax, f.ay, f.az) - 1e-1f;
                     }
                 }
-                if (resident) {
-                    const V3 n = normalize(mk(d[0] + -d[1] + -d[2] + d[3], -d[0] + -d[1] + d[2] + d[3], -d[0] + d[1] + -d[2] + d[3]));
-                    aux.normal[0] = n.x; aux.normal[1] = n.y; aux.normal[2] = n.z;
-                }
+                if (resident) aux_set_hit(aux, raw0, raw1, normal_of_taps(d[0], d[1], d[2], d[3]), depth);
             }
         }
         a.aux[pixel] = aux;

@@ -325,12 +325,11 @@ void derive_raymarch_args(const sdfv_render_params* rp, sdfv::RaymarchArgs& a) {
     a.pow2_size = 1;
     a.symmetric_box = 1;
     a.fast_normal = 1;
-    float inv_h2 = 0.0f, radius2 = 0.0f;
-    for (int i = 0; i < 3; ++i) {
-        const float s = (float)rp->tex_size[i] / rp->lod_dist_between_samples;
-        inv_h2 += s * s;
-    }
-    const float h_world = 1.0f / sqrtf(inv_h2);  // sdfNormal's tap offset, material.frag:74
+    float radius2 = 0.0f;
+    // sdfNormal's tap offset as the kernels take it (march_common.h): ((sx^2 + sy^2) + sz^2), the order of the loop that stood
+    // here -- whose leading 0 + sx^2 was exact -- and unchecked, so that fast_normal is what it was for every input
+    const float h_world = sdfv::march::tap_distance((float)rp->tex_size[0], (float)rp->tex_size[1], (float)rp->tex_size[2],
+                                                    rp->lod_dist_between_samples);
     for (int i = 0; i < 3; ++i) {
         a.bsize[i] = rp->bounds_max[i] - rp->bounds_min[i];
         a.inv_bsize[i] = 1.0f / a.bsize[i];
@@ -369,6 +368,33 @@ int check_lights(const sdfv_render_params* rp) {
             return fail(SDFV_ERR_INVALID_ARGUMENT, "lights[%u] has unknown kind %u", i, rp->lights[i].kind);
     }
     return SDFV_OK;
+}
+
+// A size-prefixed descriptor: read what the caller's header knew, take the rest as 0 / NULL (a binder built against an older
+// header).  A NEWER caller's descriptor: fields this library does not know may only be zero (0 / NULL = "not used" by the
+// descriptors' rule); anything else would be dropped silently.  The caller checks `reserved` next.
+template <typename Desc>
+int read_sized_desc(const Desc* desc, size_t first_version_bytes, const char* type, Desc& d) {
+    if (!desc) return fail(SDFV_ERR_INVALID_ARGUMENT, "desc is NULL");
+    if (desc->size < first_version_bytes)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "%s.size = %u is smaller than the descriptor's first version (%zu)", type, desc->size,
+                    first_version_bytes);
+    memset(&d, 0, sizeof(d));
+    memcpy(&d, desc, desc->size < sizeof(d) ? desc->size : sizeof(d));
+    for (uint32_t i = (uint32_t)sizeof(d); i < desc->size; ++i)
+        if (reinterpret_cast<const unsigned char*>(desc)[i] != 0)
+            return fail(SDFV_ERR_INVALID_ARGUMENT, "%s.size = %u: this library knows %zu bytes and byte %u beyond them is not 0", type,
+                        desc->size, sizeof(d), i);
+    return SDFV_OK;
+}
+
+// The four output planes of an argument block (RaymarchArgs, ProgramMarchArgs) at camera c0 of the caller's.
+template <typename Args>
+void point_outputs_at(Args& a, uint64_t pixels_per_cam, uint32_t c0, float* rgba, uint32_t* rgba8, sdfv_march_aux* aux, float* depth) {
+    a.rgba = rgba ? reinterpret_cast<float4*>(rgba) + c0 * pixels_per_cam : nullptr;
+    a.rgba8 = rgba8 ? rgba8 + c0 * pixels_per_cam : nullptr;
+    a.aux = aux ? aux + c0 * pixels_per_cam : nullptr;
+    a.depth = depth ? depth + c0 * pixels_per_cam : nullptr;
 }
 
 }  // namespace
@@ -498,10 +524,140 @@ int fill_boundary_slices(const sdfv_demo_params* params, uint32_t sdf_id, const 
 }  // namespace sdfv
 
 #pragma GCC visibility push(default)
-static int raymarch_rows(const sdfv_render_params* rp, const float* tex0, const float* tex1, const float* dist,
-                         const float* pairs, const float* ilv, const sdfv_camera* cameras, uint32_t n_cameras, uint32_t width,
-                         uint32_t height, uint32_t y0, uint32_t y1, uint32_t band_step, uint32_t band_height, float* rgba, float* depth,
-                         sdfv_march_aux* aux, uint32_t* rgba8, void* stream);
+// Rows [y0, y1) of the image (band_step 1), or the 16-row bands y0 / 16, y0 / 16 + band_step, ... below y1 == height.
+static int raymarch_rows(const sdfv_march_desc& d, uint32_t y0, uint32_t y1, uint32_t band_step, uint32_t band_height, void* stream) {
+    const sdfv_render_params* rp = d.rp;
+    const uint32_t n_cameras = d.n_cameras, width = d.width, height = d.height;
+    const sdfv_camera* cameras = d.cameras;
+    if (!rp || !d.tex0 || !d.tex1) return fail(SDFV_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!d.rgba && !d.rgba8) return fail(SDFV_ERR_INVALID_ARGUMENT, "no colour output: rgba and rgba8 are both NULL");
+    if (int rc = check_lights(rp)) return rc;
+    if (int rc = check_texel_alignment(d.tex0, d.tex1, d.rgba)) return rc;
+    if ((uintptr_t)d.dist & 3 || (uintptr_t)d.depth & 3 || (uintptr_t)d.aux & 3 || (uintptr_t)d.rgba8 & 3)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "dist, depth, aux and rgba8 must be 4-byte aligned");
+    if (((uintptr_t)d.pairs | (uintptr_t)d.ilv) & 7) return fail(SDFV_ERR_INVALID_ARGUMENT, "pairs and ilv must be 8-byte aligned");
+    if (n_cameras && !cameras) return fail(SDFV_ERR_INVALID_ARGUMENT, "cameras is NULL");
+    if (y0 > y1 || y1 > height) return fail(SDFV_ERR_INVALID_ARGUMENT, "rows [%u,%u) outside height %u", y0, y1, height);
+    if (rp->tex_size[0] == 0 || rp->tex_size[1] == 0 || rp->tex_size[2] == 0)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "empty texture");
+    if (!(rp->lod_dist_between_samples >= 1.0f)) return fail(SDFV_ERR_INVALID_ARGUMENT, "lod_dist_between_samples < 1");
+    if ((uint64_t)rp->tex_size[0] * rp->tex_size[1] * rp->tex_size[2] >= (1ull << 32))
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "texture too large for 32-bit texel indexing");
+    if (int rc = need_device()) return rc;
+    sdfv::RaymarchArgs a;
+    derive_raymarch_args(rp, a);
+    a.dist = d.dist;
+    a.pairs = d.pairs;
+    a.ilv = d.ilv;
+    a.tex0 = reinterpret_cast<const float4*>(d.tex0);
+    a.tex1 = reinterpret_cast<const float4*>(d.tex1);
+    a.width = width;
+    a.height = height;
+    a.y0 = y0;
+    a.y1 = y1;
+    a.band_skip = band_height * (band_step - 1u);
+    a.band_shift = band_height == 8u ? 3u : 4u;
+    a.rows_out = band_step > 1 ? sdfv_band_rows_ex(height, y0 / band_height, band_step, band_height) : y1 - y0;
+    // sdfNormal's result only feeds calculate_lighting (material.frag:155,163), and the one AmbientLight the scene
+    // configures (scene/mod.rs:106-112) does not read it: dead code a GLSL compiler removes.  It is evaluated when the
+    // aux record asks for it; SDFV_OPT_RAYMARCH_KEEP_NORMAL evaluates it per hit regardless (what it would cost once a
+    // directional light uses it).
+    a.compute_normal = g_options.raymarch_keep_normal ? 1u : 0u;
+    // tile order: auto = for a single frame the launcher's XCD-aware choice (groups of 2 x 2 tiles, those under the projected
+    // bounding box first; profiles/r02/box_first_*.json, EXPERIMENTS R2-R3), launch order for batches of cameras, which
+    // lose 3-8 % with any grouping
+    // w waves per SIMD = w workgroups per CU: each asks for a w-th of the CU's 160 KB of LDS (less a little for rounding)
+    const uint32_t w = g_options.raymarch_waves_per_simd;
+    a.waves_per_simd = w;  // 0 = the launcher's occupancy rule (launch_raymarch), 7 = never cap, 2..6 = that cap
+    a.box_first = g_options.raymarch_box_first;
+    // The device's facts gate what is machine- or topology-specific: the hand-written loop is gfx950 code (anything else
+    // takes the compiler's loop, bit-identical), and the XCD-aware tile orders assume the observed workgroup -> XCD
+    // placement L % 8 of an eight-XCD part (speed only; launch order elsewhere).
+    const DeviceFacts& dev = device_facts();
+    if (!dev.gfx950) a.asm_loop = 0;
+    a.wave_slots_per_simd_unit = dev.cus * 4u;  // SIMDs: resident waves at w per SIMD = w * this
+    a.last_level_cache_bytes = dev.last_level_cache_bytes;
+    const bool xcd_order_ok = dev.xcds == 8;
+    a.group_shift = g_options.raymarch_tile_group == 0 ? (n_cameras == 1 && xcd_order_ok ? sdfv::kGroupAuto : 0u)
+                                                       : (g_options.raymarch_tile_group == 1 ? 0u : g_options.raymarch_tile_group - 1u);
+    // launches that keep launch order (batches, tile bands): tile columns rotated by row and camera, so that the XCDs' static
+    // shares balance (auto only: SDFV_OPT_RAYMARCH_TILE_GROUP 1 is the plain launch order, for A/B runs)
+    a.rotate_columns = g_options.raymarch_tile_group == 0 && xcd_order_ok ? 1u : 0u;
+#ifdef SDFV_TUNING
+    a.wave_timing = reinterpret_cast<unsigned long long*>(g_options.wave_timing);  // 32 B per wave, or 0
+    a.priority_map = reinterpret_cast<const unsigned char*>(g_options.priority_map);
+    a.tile_order = n_cameras == 1 ? reinterpret_cast<const uint32_t*>(g_options.tile_order) : nullptr;
+#endif
+    const uint64_t pixels_per_cam = (uint64_t)a.rows_out * width;
+    hipStream_t main = (hipStream_t)stream;
+    // Cameras.  Up to kInlineCameras ride in the kernel-argument block.  A larger batch is read from device memory, so that
+    // kMaxCamerasPerLaunch of them still make ONE launch: the caller's own array if that is where it lies, else a slot of the
+    // camera ring per launch (CameraRing).  While the stream is being captured (the ring's events do not belong in somebody's
+    // graph), with the option off, or if the ring cannot be had, the batch goes out as launches of kInlineCameras instead
+    // (same pixels).
+    a.camera_list = nullptr;
+    const sdfv_camera* device_cameras = nullptr;
+    bool ring = false;
+    // (asked for ANY count -- ADVICE r04: a device array of <= kInlineCameras cameras, e.g. a rank's share of a resident batch,
+    // used to be memcpy'd from on the host; the kernel reads camera_list for any count)
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, cameras) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged)) {
+        device_cameras = cameras;
+    } else {
+        (void)hipGetLastError();
+        if (n_cameras > sdfv::kInlineCameras) {
+            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(main, &capturing) != hipSuccess) (void)hipGetLastError();
+            ring = capturing == hipStreamCaptureStatusNone && g_options.raymarch_camera_staging &&
+                   g_camera_ring.ensure(current_device()) == hipSuccess;
+        }
+    }
+    const uint32_t per_launch = device_cameras || ring ? sdfv::kMaxCamerasPerLaunch : sdfv::kInlineCameras;
+    // several launches, each small (tools/split_balance.py: a launch of 17 000 workgroups gains 34 % from overlapping with its
+    // siblings, one of 35 000 11 %, one of 65 000 nothing, one of 130 000 loses 4 %): side streams, see BatchStreams
+    const uint64_t groups_per_launch = (uint64_t)((width + 15) / 16) * ((a.rows_out + 15) / 16) * per_launch;
+    const bool overlap = n_cameras > per_launch && groups_per_launch <= 40000 && g_options.raymarch_batch_streams;
+    uint32_t used = 0;  // side streams that carry a launch of this call
+    int rc = SDFV_OK;
+    auto hip_ok = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && rc == SDFV_OK) rc = hip_fail(e, what);
+        return e == hipSuccess;
+    };
+    if (overlap) hip_ok(g_batch_streams.ensure(current_device()), "batch streams") && hip_ok(hipEventRecord(g_batch_streams.fork, main), "hipEventRecord");
+    uint32_t launch = 0;
+    for (uint32_t c0 = 0; c0 < n_cameras && rc == SDFV_OK; c0 += per_launch, ++launch) {
+        const uint32_t nc = n_cameras - c0 < per_launch ? n_cameras - c0 : per_launch;
+        a.n_cameras = nc;
+        if (device_cameras) a.camera_list = device_cameras + c0;
+        else if (!ring) memcpy(a.cameras, cameras + c0, nc * sizeof(sdfv_camera));
+        point_outputs_at(a, pixels_per_cam, c0, d.rgba, d.rgba8, d.aux, d.depth);
+        hipStream_t on = main;
+        const uint32_t lane = launch % (BatchStreams::kSide + 1);  // 0 = the caller's stream
+        if (overlap && lane != 0) {
+            on = g_batch_streams.side[lane - 1];
+            if (lane > used) {
+                if (!hip_ok(hipStreamWaitEvent(on, g_batch_streams.fork, 0), "hipStreamWaitEvent")) break;
+                used = lane;
+            }
+        }
+        if (ring) {
+            CameraRing& r = g_camera_ring;
+            const uint32_t slot = r.next++ % CameraRing::kSlots;
+            sdfv_camera* at = r.base + (size_t)slot * sdfv::kMaxCamerasPerLaunch;
+            if (r.recorded[slot] && !hip_ok(hipStreamWaitEvent(on, r.read[slot], 0), "hipStreamWaitEvent")) break;
+            if (!hip_ok(sdfv::launch_store_cameras(cameras + c0, nc, at, on), "store_cameras")) break;
+            a.camera_list = at;
+            hip_ok(sdfv::launch_raymarch(a, on), "launch_raymarch") && hip_ok(hipEventRecord(r.read[slot], on), "hipEventRecord");
+            r.recorded[slot] = true;  // (a failed record leaves the event as it was: waiting on it is harmless)
+            continue;
+        }
+        hip_ok(sdfv::launch_raymarch(a, on), "launch_raymarch");
+    }
+    for (uint32_t i = 0; i < used; ++i)  // (joined even after an error: the side streams must not run on behind the caller's)
+        hip_ok(hipEventRecord(g_batch_streams.join[i], g_batch_streams.side[i]), "hipEventRecord") &&
+            hip_ok(hipStreamWaitEvent(main, g_batch_streams.join[i], 0), "hipStreamWaitEvent");
+    return rc;
+}
 
 extern "C" {
 
@@ -1099,31 +1255,17 @@ int sdfv_march_volume_advice(const sdfv_grid* grid, uint32_t* kind) {
 }
 
 int sdfv_raymarch_ex(const sdfv_march_desc* desc, void* stream) {
-    if (!desc) return fail(SDFV_ERR_INVALID_ARGUMENT, "desc is NULL");
-    // size-prefixed: read what the caller's header knew, take the rest as 0 / NULL (a binder built against an older header)
-    if (desc->size < offsetof(sdfv_march_desc, depth))
-        return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_march_desc.size = %u is smaller than the descriptor's first version (%zu)",
-                    desc->size, offsetof(sdfv_march_desc, depth));
     sdfv_march_desc d;
-    memset(&d, 0, sizeof(d));
-    memcpy(&d, desc, desc->size < sizeof(d) ? desc->size : sizeof(d));
+    if (int rc = read_sized_desc(desc, offsetof(sdfv_march_desc, depth), "sdfv_march_desc", d)) return rc;
     if (d.reserved != 0) return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_march_desc: reserved fields must be 0");
-    // a NEWER caller's descriptor: fields this library does not know may only be zero (0 / NULL = "not used" by the
-    // descriptor's rule); anything else would be dropped silently
-    for (uint32_t i = (uint32_t)sizeof(d); i < desc->size; ++i)
-        if (reinterpret_cast<const unsigned char*>(desc)[i] != 0)
-            return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_march_desc.size = %u: this library knows %zu bytes and byte %u beyond them is not 0",
-                        desc->size, sizeof(d), i);
     if (d.band_step == 0 && d.band_height != 0)
         return fail(SDFV_ERR_INVALID_ARGUMENT, "band_height %u with band_step 0: a band set needs band_step >= 1 (0 = rows [y0, y1))", d.band_height);
     if (d.band_step == 0)
-        return raymarch_rows(d.rp, d.tex0, d.tex1, d.dist, d.pairs, d.ilv, d.cameras, d.n_cameras, d.width, d.height, d.y0, d.y1, 1, 16,
-                             d.rgba, d.depth, d.aux, d.rgba8, stream);
+        return raymarch_rows(d, d.y0, d.y1, 1, 16, stream);
     const uint32_t B = d.band_height ? d.band_height : 16u;
     if (B != 8u && B != 16u) return fail(SDFV_ERR_INVALID_ARGUMENT, "band_height %u: 8 or 16 (0 = 16)", d.band_height);
     if (sdfv_band_rows_ex(d.height, d.band_first, d.band_step, B) == 0) return SDFV_OK;  // a band set below the image: nothing to render
-    return raymarch_rows(d.rp, d.tex0, d.tex1, d.dist, d.pairs, d.ilv, d.cameras, d.n_cameras, d.width, d.height, d.band_first * B,
-                         d.height, d.band_step, B, d.rgba, d.depth, d.aux, d.rgba8, stream);
+    return raymarch_rows(d, d.band_first * B, d.height, d.band_step, B, stream);
 }
 
 uint32_t sdfv_band_rows_ex(uint32_t height, uint32_t band_first, uint32_t band_step, uint32_t band_height) {
@@ -1138,145 +1280,6 @@ uint32_t sdfv_band_rows(uint32_t height, uint32_t band_first, uint32_t band_step
     return sdfv_band_rows_ex(height, band_first, band_step, 16u);
 }
 
-}  // extern "C"
-// Rows [y0, y1) of the image (band_step 1), or the 16-row bands y0 / 16, y0 / 16 + band_step, ... below y1 == height.
-static int raymarch_rows(const sdfv_render_params* rp, const float* tex0, const float* tex1, const float* dist,
-                         const float* pairs, const float* ilv, const sdfv_camera* cameras, uint32_t n_cameras, uint32_t width,
-                         uint32_t height, uint32_t y0, uint32_t y1, uint32_t band_step, uint32_t band_height, float* rgba, float* depth,
-                         sdfv_march_aux* aux, uint32_t* rgba8, void* stream) {
-    if (!rp || !tex0 || !tex1) return fail(SDFV_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!rgba && !rgba8) return fail(SDFV_ERR_INVALID_ARGUMENT, "no colour output: rgba and rgba8 are both NULL");
-    if (int rc = check_lights(rp)) return rc;
-    if (int rc = check_texel_alignment(tex0, tex1, rgba)) return rc;
-    if ((uintptr_t)dist & 3 || (uintptr_t)depth & 3 || (uintptr_t)aux & 3 || (uintptr_t)rgba8 & 3)
-        return fail(SDFV_ERR_INVALID_ARGUMENT, "dist, depth, aux and rgba8 must be 4-byte aligned");
-    if (((uintptr_t)pairs | (uintptr_t)ilv) & 7) return fail(SDFV_ERR_INVALID_ARGUMENT, "pairs and ilv must be 8-byte aligned");
-    if (n_cameras && !cameras) return fail(SDFV_ERR_INVALID_ARGUMENT, "cameras is NULL");
-    if (y0 > y1 || y1 > height) return fail(SDFV_ERR_INVALID_ARGUMENT, "rows [%u,%u) outside height %u", y0, y1, height);
-    if (rp->tex_size[0] == 0 || rp->tex_size[1] == 0 || rp->tex_size[2] == 0)
-        return fail(SDFV_ERR_INVALID_ARGUMENT, "empty texture");
-    if (!(rp->lod_dist_between_samples >= 1.0f)) return fail(SDFV_ERR_INVALID_ARGUMENT, "lod_dist_between_samples < 1");
-    if ((uint64_t)rp->tex_size[0] * rp->tex_size[1] * rp->tex_size[2] >= (1ull << 32))
-        return fail(SDFV_ERR_INVALID_ARGUMENT, "texture too large for 32-bit texel indexing");
-    if (int rc = need_device()) return rc;
-    sdfv::RaymarchArgs a;
-    derive_raymarch_args(rp, a);
-    a.dist = dist;
-    a.pairs = pairs;
-    a.ilv = ilv;
-    a.tex0 = reinterpret_cast<const float4*>(tex0);
-    a.tex1 = reinterpret_cast<const float4*>(tex1);
-    a.width = width;
-    a.height = height;
-    a.y0 = y0;
-    a.y1 = y1;
-    a.band_skip = band_height * (band_step - 1u);
-    a.band_shift = band_height == 8u ? 3u : 4u;
-    a.rows_out = band_step > 1 ? sdfv_band_rows_ex(height, y0 / band_height, band_step, band_height) : y1 - y0;
-    // sdfNormal's result only feeds calculate_lighting (material.frag:155,163), and the one AmbientLight the scene
-    // configures (scene/mod.rs:106-112) does not read it: dead code a GLSL compiler removes.  It is evaluated when the
-    // aux record asks for it; SDFV_OPT_RAYMARCH_KEEP_NORMAL evaluates it per hit regardless (what it would cost once a
-    // directional light uses it).
-    a.compute_normal = g_options.raymarch_keep_normal ? 1u : 0u;
-    // tile order: auto = for a single frame the launcher's XCD-aware choice (groups of 2 x 2 tiles, those under the projected
-    // bounding box first; profiles/r02/box_first_*.json, EXPERIMENTS R2-R3), launch order for batches of cameras, which
-    // lose 3-8 % with any grouping
-    // w waves per SIMD = w workgroups per CU: each asks for a w-th of the CU's 160 KB of LDS (less a little for rounding)
-    const uint32_t w = g_options.raymarch_waves_per_simd;
-    a.waves_per_simd = w;  // 0 = the launcher's occupancy rule (launch_raymarch), 7 = never cap, 2..6 = that cap
-    a.box_first = g_options.raymarch_box_first;
-    // The device's facts gate what is machine- or topology-specific: the hand-written loop is gfx950 code (anything else
-    // takes the compiler's loop, bit-identical), and the XCD-aware tile orders assume the observed workgroup -> XCD
-    // placement L % 8 of an eight-XCD part (speed only; launch order elsewhere).
-    const DeviceFacts& dev = device_facts();
-    if (!dev.gfx950) a.asm_loop = 0;
-    a.wave_slots_per_simd_unit = dev.cus * 4u;  // SIMDs: resident waves at w per SIMD = w * this
-    a.last_level_cache_bytes = dev.last_level_cache_bytes;
-    const bool xcd_order_ok = dev.xcds == 8;
-    a.group_shift = g_options.raymarch_tile_group == 0 ? (n_cameras == 1 && xcd_order_ok ? sdfv::kGroupAuto : 0u)
-                                                       : (g_options.raymarch_tile_group == 1 ? 0u : g_options.raymarch_tile_group - 1u);
-    // launches that keep launch order (batches, tile bands): tile columns rotated by row and camera, so that the XCDs' static
-    // shares balance (auto only: SDFV_OPT_RAYMARCH_TILE_GROUP 1 is the plain launch order, for A/B runs)
-    a.rotate_columns = g_options.raymarch_tile_group == 0 && xcd_order_ok ? 1u : 0u;
-#ifdef SDFV_TUNING
-    a.wave_timing = reinterpret_cast<unsigned long long*>(g_options.wave_timing);  // 32 B per wave, or 0
-    a.priority_map = reinterpret_cast<const unsigned char*>(g_options.priority_map);
-    a.tile_order = n_cameras == 1 ? reinterpret_cast<const uint32_t*>(g_options.tile_order) : nullptr;
-#endif
-    const uint64_t pixels_per_cam = (uint64_t)a.rows_out * width;
-    hipStream_t main = (hipStream_t)stream;
-    // Cameras.  Up to kInlineCameras ride in the kernel-argument block.  A larger batch is read from device memory, so that
-    // kMaxCamerasPerLaunch of them still make ONE launch: the caller's own array if that is where it lies, else a slot of the
-    // camera ring per launch (CameraRing).  While the stream is being captured (the ring's events do not belong in somebody's
-    // graph), with the option off, or if the ring cannot be had, the batch goes out as launches of kInlineCameras instead
-    // (same pixels).
-    a.camera_list = nullptr;
-    const sdfv_camera* device_cameras = nullptr;
-    bool ring = false;
-    // (asked for ANY count -- ADVICE r04: a device array of <= kInlineCameras cameras, e.g. a rank's share of a resident batch,
-    // used to be memcpy'd from on the host; the kernel reads camera_list for any count)
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, cameras) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged)) {
-        device_cameras = cameras;
-    } else {
-        (void)hipGetLastError();
-        if (n_cameras > sdfv::kInlineCameras) {
-            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(main, &capturing) != hipSuccess) (void)hipGetLastError();
-            ring = capturing == hipStreamCaptureStatusNone && g_options.raymarch_camera_staging &&
-                   g_camera_ring.ensure(current_device()) == hipSuccess;
-        }
-    }
-    const uint32_t per_launch = device_cameras || ring ? sdfv::kMaxCamerasPerLaunch : sdfv::kInlineCameras;
-    // several launches, each small (tools/split_balance.py: a launch of 17 000 workgroups gains 34 % from overlapping with its
-    // siblings, one of 35 000 11 %, one of 65 000 nothing, one of 130 000 loses 4 %): side streams, see BatchStreams
-    const uint64_t groups_per_launch = (uint64_t)((width + 15) / 16) * ((a.rows_out + 15) / 16) * per_launch;
-    const bool overlap = n_cameras > per_launch && groups_per_launch <= 40000 && g_options.raymarch_batch_streams;
-    uint32_t used = 0;  // side streams that carry a launch of this call
-    int rc = SDFV_OK;
-    auto hip_ok = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == SDFV_OK) rc = hip_fail(e, what);
-        return e == hipSuccess;
-    };
-    if (overlap) hip_ok(g_batch_streams.ensure(current_device()), "batch streams") && hip_ok(hipEventRecord(g_batch_streams.fork, main), "hipEventRecord");
-    uint32_t launch = 0;
-    for (uint32_t c0 = 0; c0 < n_cameras && rc == SDFV_OK; c0 += per_launch, ++launch) {
-        const uint32_t nc = n_cameras - c0 < per_launch ? n_cameras - c0 : per_launch;
-        a.n_cameras = nc;
-        if (device_cameras) a.camera_list = device_cameras + c0;
-        else if (!ring) memcpy(a.cameras, cameras + c0, nc * sizeof(sdfv_camera));
-        a.rgba = rgba ? reinterpret_cast<float4*>(rgba) + c0 * pixels_per_cam : nullptr;
-        a.rgba8 = rgba8 ? rgba8 + c0 * pixels_per_cam : nullptr;
-        a.aux = aux ? aux + c0 * pixels_per_cam : nullptr;
-        a.depth = depth ? depth + c0 * pixels_per_cam : nullptr;
-        hipStream_t on = main;
-        const uint32_t lane = launch % (BatchStreams::kSide + 1);  // 0 = the caller's stream
-        if (overlap && lane != 0) {
-            on = g_batch_streams.side[lane - 1];
-            if (lane > used) {
-                if (!hip_ok(hipStreamWaitEvent(on, g_batch_streams.fork, 0), "hipStreamWaitEvent")) break;
-                used = lane;
-            }
-        }
-        if (ring) {
-            CameraRing& r = g_camera_ring;
-            const uint32_t slot = r.next++ % CameraRing::kSlots;
-            sdfv_camera* at = r.base + (size_t)slot * sdfv::kMaxCamerasPerLaunch;
-            if (r.recorded[slot] && !hip_ok(hipStreamWaitEvent(on, r.read[slot], 0), "hipStreamWaitEvent")) break;
-            if (!hip_ok(sdfv::launch_store_cameras(cameras + c0, nc, at, on), "store_cameras")) break;
-            a.camera_list = at;
-            hip_ok(sdfv::launch_raymarch(a, on), "launch_raymarch") && hip_ok(hipEventRecord(r.read[slot], on), "hipEventRecord");
-            r.recorded[slot] = true;  // (a failed record leaves the event as it was: waiting on it is harmless)
-            continue;
-        }
-        hip_ok(sdfv::launch_raymarch(a, on), "launch_raymarch");
-    }
-    for (uint32_t i = 0; i < used; ++i)  // (joined even after an error: the side streams must not run on behind the caller's)
-        hip_ok(hipEventRecord(g_batch_streams.join[i], g_batch_streams.side[i]), "hipEventRecord") &&
-            hip_ok(hipStreamWaitEvent(main, g_batch_streams.join[i], 0), "hipStreamWaitEvent");
-    return rc;
-}
-extern "C" {
 
 // Argument checks and RaymarchArgs / SlabMarchArgs shared by the two forms of a round of the sharded march.
 static int slab_round_args(const sdfv_render_params* rp, const sdfv_grid* slab, uint32_t ghost_lo, uint32_t ghost_hi,
@@ -1676,21 +1679,10 @@ int sdfv_program_fill_grid_commit(const sdfv_program* p, const sdfv_grid* grid, 
 }
 
 int sdfv_program_raymarch_check(const sdfv_program_march_desc* desc, sdfv_program_march_desc* checked, float* normal_h) {
-    if (!desc) return fail(SDFV_ERR_INVALID_ARGUMENT, "desc is NULL");
-    // size-prefixed like sdfv_march_desc: read what the caller's header knew, take the rest as 0 / NULL
-    constexpr size_t first_version = offsetof(sdfv_program_march_desc, rgba8) + sizeof(uint32_t*);
-    if (desc->size < first_version)
-        return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_program_march_desc.size = %u is smaller than the descriptor's first version (%zu)",
-                    desc->size, first_version);
     sdfv_program_march_desc d;
-    memset(&d, 0, sizeof(d));
-    memcpy(&d, desc, desc->size < sizeof(d) ? desc->size : sizeof(d));
+    constexpr size_t first_version = offsetof(sdfv_program_march_desc, rgba8) + sizeof(uint32_t*);
+    if (int rc = read_sized_desc(desc, first_version, "sdfv_program_march_desc", d)) return rc;
     if (d.reserved != 0) return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_program_march_desc: reserved must be 0");
-    for (uint32_t i = (uint32_t)sizeof(d); i < desc->size; ++i)
-        if (reinterpret_cast<const unsigned char*>(desc)[i] != 0)
-            return fail(SDFV_ERR_INVALID_ARGUMENT,
-                        "sdfv_program_march_desc.size = %u: this library knows %zu bytes and byte %u beyond them is not 0", desc->size,
-                        sizeof(d), i);
     if (!d.program) return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_program_march_desc.program is NULL");
     if (!d.rp) return fail(SDFV_ERR_INVALID_ARGUMENT, "sdfv_program_march_desc.rp is NULL");
     if (!d.rgba && !d.rgba8) return fail(SDFV_ERR_INVALID_ARGUMENT, "no colour output: rgba and rgba8 are both NULL");
@@ -1702,7 +1694,7 @@ int sdfv_program_raymarch_check(const sdfv_program_march_desc* desc, sdfv_progra
     if (d.y0 > d.y1 || d.y1 > d.height) return fail(SDFV_ERR_INVALID_ARGUMENT, "rows [%u,%u) outside height %u", d.y0, d.y1, d.height);
     if (!(d.normal_h >= 0.0f) || !std::isfinite(d.normal_h))
         return fail(SDFV_ERR_INVALID_ARGUMENT, "normal_h = %g: a distance > 0, or 0 to derive it from rp->tex_size", d.normal_h);
-    const float h = sdfv::pmarch::normal_tap_distance(*d.rp, d.normal_h);
+    const float h = sdfv::march::normal_tap_distance(*d.rp, d.normal_h);
     if (!(h > 0.0f) || !std::isfinite(h))
         return fail(SDFV_ERR_INVALID_ARGUMENT,
                     "normal_h is 0 and rp->tex_size = %u x %u x %u with lod_dist_between_samples = %g gives no tap distance: set "
@@ -1736,10 +1728,7 @@ int sdfv_program_raymarch(const sdfv_program_march_desc* desc, void* stream) {
         const uint32_t nc = d.n_cameras - c0 < sdfv::kProgramMarchCameras ? d.n_cameras - c0 : sdfv::kProgramMarchCameras;
         a.n_cameras = nc;
         memcpy(a.cameras, d.cameras + c0, nc * sizeof(sdfv_camera));
-        a.rgba = d.rgba ? reinterpret_cast<float4*>(d.rgba) + c0 * pixels_per_cam : nullptr;
-        a.rgba8 = d.rgba8 ? d.rgba8 + c0 * pixels_per_cam : nullptr;
-        a.aux = d.aux ? d.aux + c0 * pixels_per_cam : nullptr;
-        a.depth = d.depth ? d.depth + c0 * pixels_per_cam : nullptr;
+        point_outputs_at(a, pixels_per_cam, c0, d.rgba, d.rgba8, d.aux, d.depth);
         SDFV_HIP(sdfv::launch_program_march(a, (hipStream_t)stream));
     }
     return SDFV_OK;

@@ -117,3 +117,30 @@ def test_a_render_behind_a_fill_on_the_same_stream_leaves_both_intact(pkg, PM):
     assert torch.equal(t0.view(torch.int32), want0.view(torch.int32)) and torch.equal(t1.view(torch.int32), want1.view(torch.int32))
     assert torch.equal(aux.view(torch.int32), alone_aux.view(torch.int32)) and torch.equal(rgba.view(torch.int32), alone_rgba.view(torch.int32))
     assert (M.aux_view(aux.cpu().numpy())["status"] == 1).sum() > 1000
+
+
+def test_both_routes_cover_the_same_pixels(pkg, PM):
+    """The grid march (sdfv_raymarch_ex over a 16^3 fill of `single`) and the direct march of the same program, same render
+    parameters, 40 x 36 (the right and bottom tiles have lanes beyond the image): aux.status == 0 -- the pixel's ray is off
+    the box -- on exactly the same pixels.  Cameras: the scene's orbit camera and one that looks past the box, which puts it
+    across the image's right and bottom edges (the outside pair: each has pixels on the box and off it), and the scene's
+    camera inside the box, where every ray leaves through a face: no pixel of it is off the box, in either route."""
+    w, h = 40, 36
+    lo, hi = M.SCENES["single"][:2]
+    g = pkg.make_grid((16, 16, 16), lo, hi)
+    rp = pkg.default_render_params(g)
+    prog = M.builders(PM)["single"].build()
+    t0, t1 = pkg.alloc_textures(g)
+    prog.fill_grid(g, t0, t1)
+    orbit, inside = M.cameras(pkg, "single", w, h)
+    past = pkg.camera_look_at(eye=M.CLOSE, target=(-1.0, 0.9, 0.0), aspect=w / h)
+    cams = [orbit, past, inside]
+    _, grid_aux = pkg.raymarch(rp, t0, t1, cams, w, h, want_aux=True)
+    _, prog_aux = prog.render(cams, w, h, rp=rp, want_aux=True)
+    torch.cuda.synchronize()
+    off_grid = M.aux_view(grid_aux.cpu().numpy())["status"] == 0
+    off_prog = M.aux_view(prog_aux.cpu().numpy())["status"] == 0
+    assert off_grid.shape == (3, h, w) and (off_grid == off_prog).all(), np.argwhere(off_grid != off_prog)[:4].tolist()
+    for i in (0, 1):
+        assert 0 < off_grid[i].sum() < w * h, (i, int(off_grid[i].sum()))
+    assert not off_grid[2].any()
