@@ -66,6 +66,12 @@ struct RaymarchArgs {
     sdfv_camera cameras[16];
 };
 
+// raymarch_kernel's MODE = what the march loop reads: kMarchGeneral the shader's nested loop over tex0 (any filter, any extents,
+// full MirroredRepeat); the others the fast march (LINEAR, clamp for mirror) over tex0.r in place, the compact distance volume
+// (sdfv_commit_distance), the y-pair volume (sdfv_commit_pairs; two 16-byte gathers per cell) and the y-interleaved volume
+// (sdfv_commit_interleaved; 4 B/voxel, 2 or 4 lines per cell) -- the last two are read by the hand-written loop only.
+constexpr int kMarchGeneral = 0, kMarchTex0 = 1, kMarchDist = 2, kMarchPairs = 3, kMarchIlv = 4;
+
 constexpr uint32_t kInlineCameras = 16;
 // One launch for BASELINE config 5's 64-camera batch (1.59 -> 1.48 ms against four launches of 16, and a rank's share of it
 // is one launch too); larger batches are several launches of this many (small ones overlap on side streams).
@@ -94,8 +100,10 @@ struct SlabMarchArgs {
 hipError_t launch_raymarch_slab(const RaymarchArgs& a, const SlabMarchArgs& s, hipStream_t stream);
 
 hipError_t launch_raymarch(const RaymarchArgs& a, hipStream_t stream);
-// would the launcher march over a pair (kind 3) / y-interleaved (kind 4) volume for these arguments, pointers apart?
+// would the launcher march over a pair (kind kMarchPairs) / y-interleaved (kind kMarchIlv) volume for these arguments, pointers apart?
 bool march_volume_applicable(const RaymarchArgs& a, int kind);
+// the launcher's choice among the volumes taken as present: kMarchIlv, kMarchPairs, or 0 = neither (dist / tex0.r is marched)
+int march_volume_choice(const RaymarchArgs& a, bool have_dist, bool have_pairs, bool have_ilv);
 // n cameras from a HOST array into DEVICE memory, stream-ordered, without a copy engine: launches that carry 32 cameras each
 // in their kernel arguments (the host array is free again on return)
 hipError_t launch_store_cameras(const sdfv_camera* host, uint32_t n, sdfv_camera* device, hipStream_t stream);

@@ -46,7 +46,8 @@ __device__ __forceinline__ uint32_t mirror_index(int i, int n) {
 
 struct Tex {
     const float4* data;
-    int w, h, d;
+    int w, h, d;  // size of the WHOLE texture
+    int z_lo;     // first slice that `data` holds (kClampSlab; 0 everywhere else)
 };
 
 struct Footprint {  // the 8 texel offsets and 3 weights of one LINEAR fetch
@@ -54,9 +55,13 @@ struct Footprint {  // the 8 texel offsets and 3 weights of one LINEAR fetch
     float ax, ay, az;
 };
 
-// FAST: floor(u) is known to be in [-1, N-1] on every axis, where MirroredRepeat == clamp.
-template <bool FAST>
-__device__ __forceinline__ Footprint footprint(const Tex& t, V3 p01) {
+// How a LINEAR fetch turns texel indices into offsets: kMirror = GL MirroredRepeat in full; kClamp = floor(u) is known to be
+// in [-1, N-1] on every axis, where MirroredRepeat == clamp; kClampSlab = clamp, z rebased to the first resident slice.
+constexpr int kMirror = 0, kClamp = 1, kClampSlab = 2;
+
+// k0c (the clamp policies): clamp(floor(w), 0, D - 1), the slice that owns the cell -- what the march over z-slabs goes by.
+template <int POLICY>
+__device__ __forceinline__ Footprint footprint(const Tex& t, V3 p01, int& k0c) {
     float u = p01.x * (float)t.w - 0.5f, v = p01.y * (float)t.h - 0.5f, w = p01.z * (float)t.d - 0.5f;
     float fu = floorf(u), fv = floorf(v), fw = floorf(w);
     Footprint f;
@@ -64,14 +69,17 @@ __device__ __forceinline__ Footprint footprint(const Tex& t, V3 p01) {
     int i0 = (int)fu, j0 = (int)fv, k0 = (int)fw;
     uint32_t i0m, i1m, j0m, j1m, k0m, k1m;
     const uint32_t sy = (uint32_t)t.w, sz = (uint32_t)t.w * (uint32_t)t.h;
-    if (FAST) {
-        i0m = (uint32_t)max(i0, 0); i1m = (uint32_t)min(i0 + 1, t.w - 1);
-        j0m = (uint32_t)max(j0, 0) * sy; j1m = (uint32_t)min(j0 + 1, t.h - 1) * sy;
-        k0m = (uint32_t)max(k0, 0) * sz; k1m = (uint32_t)min(k0 + 1, t.d - 1) * sz;
-    } else {
+    k0c = 0;
+    if (POLICY == kMirror) {
         i0m = mirror_index(i0, t.w); i1m = mirror_index(i0 + 1, t.w);
         j0m = mirror_index(j0, t.h) * sy; j1m = mirror_index(j0 + 1, t.h) * sy;
         k0m = mirror_index(k0, t.d) * sz; k1m = mirror_index(k0 + 1, t.d) * sz;
+    } else {
+        const int z0 = POLICY == kClampSlab ? t.z_lo : 0;
+        i0m = (uint32_t)max(i0, 0); i1m = (uint32_t)min(i0 + 1, t.w - 1);
+        j0m = (uint32_t)max(j0, 0) * sy; j1m = (uint32_t)min(j0 + 1, t.h - 1) * sy;
+        k0c = min(max(k0, 0), t.d - 1);
+        k0m = (uint32_t)(max(k0, 0) - z0) * sz; k1m = (uint32_t)(min(k0 + 1, t.d - 1) - z0) * sz;
     }
     f.o000 = k0m + j0m + i0m; f.o100 = k0m + j0m + i1m;
     f.o010 = k0m + j1m + i0m; f.o110 = k0m + j1m + i1m;
@@ -85,6 +93,33 @@ __device__ __forceinline__ float trilerp(float t000, float t100, float t010, flo
     float c00 = mixf(t000, t100, ax), c10 = mixf(t010, t110, ax);
     float c01 = mixf(t001, t101, ax), c11 = mixf(t011, t111, ax);
     return mixf(mixf(c00, c10, ay), mixf(c01, c11, ay), az);
+}
+
+template <int POLICY>
+__device__ __forceinline__ Footprint footprint(const Tex& t, V3 p01) {
+    int k0c;
+    return footprint<POLICY>(t, p01, k0c);
+}
+
+// The eight-corner gather of one component, filtered: `stride` floats per texel (4 = tex0.r in place, 1 = the compact
+// distance volume).
+__device__ __forceinline__ float gather_r(const float* base, uint32_t stride, const Footprint& f) {
+    const float t000 = base[(uint64_t)f.o000 * stride], t100 = base[(uint64_t)f.o100 * stride];
+    const float t010 = base[(uint64_t)f.o010 * stride], t110 = base[(uint64_t)f.o110 * stride];
+    const float t001 = base[(uint64_t)f.o001 * stride], t101 = base[(uint64_t)f.o101 * stride];
+    const float t011 = base[(uint64_t)f.o011 * stride], t111 = base[(uint64_t)f.o111 * stride];
+    return trilerp(t000, t100, t010, t110, t001, t101, t011, t111, f.ax, f.ay, f.az);
+}
+
+__device__ __forceinline__ float4 gather_rgba(const float4* data, const Footprint& f) {
+    const float4 t000 = data[f.o000], t100 = data[f.o100], t010 = data[f.o010], t110 = data[f.o110];
+    const float4 t001 = data[f.o001], t101 = data[f.o101], t011 = data[f.o011], t111 = data[f.o111];
+    float4 r;
+    r.x = trilerp(t000.x, t100.x, t010.x, t110.x, t001.x, t101.x, t011.x, t111.x, f.ax, f.ay, f.az);
+    r.y = trilerp(t000.y, t100.y, t010.y, t110.y, t001.y, t101.y, t011.y, t111.y, f.ax, f.ay, f.az);
+    r.z = trilerp(t000.z, t100.z, t010.z, t110.z, t001.z, t101.z, t011.z, t111.z, f.ax, f.ay, f.az);
+    r.w = trilerp(t000.w, t100.w, t010.w, t110.w, t001.w, t101.w, t011.w, t111.w, f.ax, f.ay, f.az);
+    return r;
 }
 
 // p01 = (p - sdfBoundsMin) / (sdfBoundsMax - sdfBoundsMin), material.frag:44.  XF >= 1: every extent is an
@@ -109,47 +144,19 @@ __device__ __forceinline__ uint32_t nearest_offset(const RaymarchArgs& a, const 
     return (mirror_index(k, t.d) * (uint32_t)t.h + mirror_index(j, t.h)) * (uint32_t)t.w + mirror_index(i, t.w);
 }
 
-// sdfSampleRawInterp(.., p).r only -- what the march and the normal need.  material.frag:42-53
-template <bool LINEAR, int XF, bool FAST>
-__device__ __forceinline__ float sample_r(const RaymarchArgs& a, const Tex& t, V3 p) {
+// sdfSampleRawInterp(.., p).r only -- what the march and the normal need.  material.frag:42-53.  `base`, `stride`: tex0 itself
+// (4 floats per texel) or, LINEAR only, the compact distance volume (1).
+template <bool LINEAR, int XF, int POLICY>
+__device__ __forceinline__ float sample_r(const RaymarchArgs& a, const float* __restrict__ base, uint32_t stride, const Tex& t, V3 p) {
     V3 q = to_p01<XF>(a, p);
-    const float* base = reinterpret_cast<const float*>(t.data);
-    if (LINEAR) {
-        Footprint f = footprint<FAST>(t, q);
-        float t000 = base[(uint64_t)f.o000 * 4], t100 = base[(uint64_t)f.o100 * 4];
-        float t010 = base[(uint64_t)f.o010 * 4], t110 = base[(uint64_t)f.o110 * 4];
-        float t001 = base[(uint64_t)f.o001 * 4], t101 = base[(uint64_t)f.o101 * 4];
-        float t011 = base[(uint64_t)f.o011 * 4], t111 = base[(uint64_t)f.o111 * 4];
-        return trilerp(t000, t100, t010, t110, t001, t101, t011, t111, f.ax, f.ay, f.az);
-    }
-    return base[(uint64_t)nearest_offset(a, t, q) * 4];
+    if (LINEAR) return gather_r(base, stride, footprint<POLICY>(t, q));
+    return base[(uint64_t)nearest_offset(a, t, q) * stride];
 }
 
-// LINEAR tex0.r read from either tex0 itself (STRIDE 4) or the compact distance volume (STRIDE 1).
-template <int XF, bool FAST, int STRIDE>
-__device__ __forceinline__ float sample_r_linear(const RaymarchArgs& a, const float* __restrict__ vol, const Tex& t, V3 p) {
-    const Footprint f = footprint<FAST>(t, to_p01<XF>(a, p));
-    const float t000 = vol[(uint64_t)f.o000 * STRIDE], t100 = vol[(uint64_t)f.o100 * STRIDE];
-    const float t010 = vol[(uint64_t)f.o010 * STRIDE], t110 = vol[(uint64_t)f.o110 * STRIDE];
-    const float t001 = vol[(uint64_t)f.o001 * STRIDE], t101 = vol[(uint64_t)f.o101 * STRIDE];
-    const float t011 = vol[(uint64_t)f.o011 * STRIDE], t111 = vol[(uint64_t)f.o111 * STRIDE];
-    return trilerp(t000, t100, t010, t110, t001, t101, t011, t111, f.ax, f.ay, f.az);
-}
-
-template <bool LINEAR, int XF, bool FAST>
+template <bool LINEAR, int XF, int POLICY>
 __device__ __forceinline__ float4 sample_rgba(const RaymarchArgs& a, const Tex& t, V3 p) {
     V3 q = to_p01<XF>(a, p);
-    if (LINEAR) {
-        Footprint f = footprint<FAST>(t, q);
-        float4 t000 = t.data[f.o000], t100 = t.data[f.o100], t010 = t.data[f.o010], t110 = t.data[f.o110];
-        float4 t001 = t.data[f.o001], t101 = t.data[f.o101], t011 = t.data[f.o011], t111 = t.data[f.o111];
-        float4 r;
-        r.x = trilerp(t000.x, t100.x, t010.x, t110.x, t001.x, t101.x, t011.x, t111.x, f.ax, f.ay, f.az);
-        r.y = trilerp(t000.y, t100.y, t010.y, t110.y, t001.y, t101.y, t011.y, t111.y, f.ax, f.ay, f.az);
-        r.z = trilerp(t000.z, t100.z, t010.z, t110.z, t001.z, t101.z, t011.z, t111.z, f.ax, f.ay, f.az);
-        r.w = trilerp(t000.w, t100.w, t010.w, t110.w, t001.w, t101.w, t011.w, t111.w, f.ax, f.ay, f.az);
-        return r;
-    }
+    if (LINEAR) return gather_rgba(t.data, footprint<POLICY>(t, q));
     return t.data[nearest_offset(a, t, q)];
 }
 
@@ -163,6 +170,12 @@ __device__ __forceinline__ float oob_dist(const RaymarchArgs& a, V3 p) {
                      fmaxf(fabsf(p.y) - a.rp.bounds_max[1], fabsf(p.z) - a.rp.bounds_max[2]));
     }
     return march::oob_dist(a.rp, p);
+}
+
+// The volume a fast march (MODE != kMarchGeneral) reads its distances from.
+template <int MODE>
+__device__ __forceinline__ const float* march_volume(const RaymarchArgs& a) {
+    return MODE == kMarchTex0 ? reinterpret_cast<const float*>(a.tex0) : MODE == kMarchDist ? a.dist : MODE == kMarchPairs ? a.pairs : a.ilv;
 }
 
 // sdfRaycast's loop (material.frag:97-126) for the LINEAR filter, with everything the loop does not need
@@ -180,14 +193,16 @@ __device__ __forceinline__ float oob_dist(const RaymarchArgs& a, V3 p) {
 //  * No per-iteration status/step counters: a stopped lane's ray_pos no longer moves, so afterwards
 //    "out of bounds" is re-derived from it (oob(ray_pos) > 1e-4 <=> it stopped on that test), and the
 //    step count is 1 + the last iteration the lane sampled in.
-//  * STRIDE = 4 reads tex0.r in place, STRIDE = 1 the compact distance volume (sdfv_commit_distance), where
+//  * kMarchTex0 (STRIDE 4) reads tex0.r in place, kMarchDist (STRIDE 1) the compact distance volume (sdfv_commit_distance), where
 //    x-neighbours are adjacent floats and each (y, z) pair of corners is ONE 8-byte load.
 //  * T: accumulate distanceFromOrigin (only the aux record consumes it).
 // Values and operation order are exactly those of sample_r() / the oracle; only redundant work is skipped.
-template <int XF, bool SYMM, int STRIDE, bool T>
-__device__ __forceinline__ void march_fast(const RaymarchArgs& a, const float* __restrict__ vol, const Tex& t,
-                                           V3 ray_dir, bool covered, V3& ray_pos, float& dist_from_origin,
-                                           int& status, int& steps, int& iterations) {
+template <int MODE, int XF, bool SYMM, bool T>
+__device__ __forceinline__ void march_fast(const RaymarchArgs& a, const Tex& t, V3 ray_dir, bool covered, V3& ray_pos,
+                                           float& dist_from_origin, int& status, int& steps, int& iterations) {
+    static_assert(MODE == kMarchTex0 || MODE == kMarchDist, "the pair and interleaved volumes are read by the hand-written loop only");
+    constexpr int STRIDE = MODE == kMarchTex0 ? 4 : 1;
+    const float* __restrict__ vol = march_volume<MODE>(a);
     const float fw_ = (float)t.w, fh_ = (float)t.h, fd_ = (float)t.d;
     const float kx = a.inv_bsize[0] * fw_, ky = a.inv_bsize[1] * fh_, kz = a.inv_bsize[2] * fd_;  // exact if XF == 2
     const int wm1 = t.w - 1, hm1 = t.h - 1, dm1 = t.d - 1;
@@ -275,8 +290,8 @@ __device__ __forceinline__ void march_fast(const RaymarchArgs& a, const float* _
 // 40 instructions per iteration on the common path (42 for a non-cubic box).  Every arithmetic instruction is the one the C++ form performs, in
 // the same order on the same operands (no fma, no reassociation): results are bit-identical, which the parity tests
 // check against the oracle for every pixel.  Covers: LINEAR filter, power-of-two extents and texture sizes (XF == 2),
-// symmetric box, clamp-for-mirror (fast_index); STRIDE 1 = compact distance volume (one 8-byte load per corner row),
-// STRIDE 4 = tex0.r in place.  Byte offsets are 32-bit: the launcher checks the volume's size.
+// symmetric box, clamp-for-mirror (fast_index); every MODE but kMarchGeneral (kMarchDist: one 8-byte load per corner row,
+// kMarchTex0: tex0.r in place).  Byte offsets are 32-bit: the launcher checks the volume's size (volume_fits_loop).
 // Registers: v24-v71 (less v41, v45, v49, v69) and s64-s87 are this block's (declared as clobbers; low enough that the kernel stays at 96
 // VGPRs = 5 waves per SIMD); operands stay where hipcc put them.
 #ifdef SDFV_TUNING
@@ -457,7 +472,7 @@ __device__ __forceinline__ void march_fast(const RaymarchArgs& a, const float* _
     "global_load_dword v65, v26, %[base]\n global_load_dword v67, v27, %[base]\n"                                  \
     "s_waitcnt vmcnt(0)\n"                                                                                          \
     "s_branch .Lcached_%=\n"
-// STRIDE 1: x-neighbours are adjacent floats: one 8-byte load per (y, z) row at b = clamp(i0, 0, W - 2); where the clamp
+// The distance volume: x-neighbours are adjacent floats: one 8-byte load per (y, z) row at b = clamp(i0, 0, W - 2); where the clamp
 // folds the two x-corners together both come from the same half (lo_is_x / hi_is_y).
 #define SDFV_MARCH_ASM_FETCH_DIST                                                                                   \
     "v_min_i32_e32 v36, s75, v35\n"                          /* b = min(i0c, W - 2) */                               \
@@ -480,7 +495,7 @@ __device__ __forceinline__ void march_fast(const RaymarchArgs& a, const float* _
     "s_waitcnt vmcnt(0)\n"                                                                                          \
     "v_cndmask_b32_e64 v65, v31, v30, s[80:81]\n v_cndmask_b32_e32 v67, v30, v31, vcc\n" /* t011, t111 */          \
     "s_branch .Lcached_%=\n"
-// STRIDE 4: tex0.r out of 16-byte texels, one dword load per corner.
+// tex0.r out of 16-byte texels, one dword load per corner.
 #define SDFV_MARCH_ASM_FETCH_TEX0                                                                                   \
     "v_lshlrev_b32_e32 v35, 4, v35\n v_lshlrev_b32_e32 v32, 4, v32\n"   /* i0c, i1c as byte offsets */               \
     "v_mad_u32_u24 v24, v28, s83, v35\n v_mad_u32_u24 v25, v28, s83, v32\n"                                          \
@@ -544,10 +559,10 @@ __device__ __forceinline__ void march_fast(const RaymarchArgs& a, const float* _
         "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68",   \
         "v70", "v71"
 
-template <bool SYMM_UNUSED, int STRIDE, bool T>
-__device__ __forceinline__ void march_asm(const RaymarchArgs& a, const float* __restrict__ vol, const Tex& t,
-                                          V3 ray_dir, bool covered, V3& ray_pos, float& dist_from_origin,
-                                          int& status, int& steps, int& iterations) {
+template <int MODE, bool T>
+__device__ __forceinline__ void march_asm(const RaymarchArgs& a, const Tex& t, V3 ray_dir, bool covered, V3& ray_pos,
+                                          float& dist_from_origin, int& status, int& steps, int& iterations) {
+    const float* __restrict__ vol = march_volume<MODE>(a);
     // float multiplies are VALU work on gfx950: the (uniform) products are moved to scalar registers explicitly
     auto uniform = [](float f) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(f))); };
     const float kx = uniform(a.inv_bsize[0] * (float)t.w), ky = uniform(a.inv_bsize[1] * (float)t.h),
@@ -586,37 +601,28 @@ __device__ __forceinline__ void march_asm(const RaymarchArgs& a, const float* __
                  : [px] "+v"(px), [py] "+v"(py), [pz] "+v"(pz), [ran] "=&s"(ran_out), [left] "=&s"(left)            \
                  : SDFV_MARCH_ASM_OPERANDS                                                                          \
                  : SDFV_MARCH_ASM_CLOBBERS)
+// each volume's row-bytes register, interior fetch and border fetch
+#define SDFV_MARCH_ASM_VOL_TEX0 "s83", SDFV_MARCH_ASM_INTERIOR_TEX0, SDFV_MARCH_ASM_FETCH_TEX0
+#define SDFV_MARCH_ASM_VOL_DIST "s82", SDFV_MARCH_ASM_INTERIOR_DIST, SDFV_MARCH_ASM_FETCH_DIST
+#define SDFV_MARCH_ASM_VOL_PAIRS "s85", SDFV_MARCH_ASM_INTERIOR_PAIRS, SDFV_MARCH_ASM_FETCH_PAIRS
+#define SDFV_MARCH_ASM_VOL_ILV "s82", SDFV_MARCH_ASM_INTERIOR_ILV, SDFV_MARCH_ASM_FETCH_ILV
+#define SDFV_MARCH_ASM_PER_BOX(RUN, ...)                                                                            \
+    if (cube) RUN(__VA_ARGS__, SDFV_MARCH_ASM_OOB_CUBE);                                                            \
+    else RUN(__VA_ARGS__, SDFV_MARCH_ASM_OOB_BOX)
+#define SDFV_MARCH_ASM_PER_VOLUME(RUN)                                                                              \
+    if (MODE == kMarchIlv) { SDFV_MARCH_ASM_PER_BOX(RUN, SDFV_MARCH_ASM_VOL_ILV); }                                 \
+    else if (MODE == kMarchPairs) { SDFV_MARCH_ASM_PER_BOX(RUN, SDFV_MARCH_ASM_VOL_PAIRS); }                        \
+    else if (MODE == kMarchDist) { SDFV_MARCH_ASM_PER_BOX(RUN, SDFV_MARCH_ASM_VOL_DIST); }                          \
+    else { SDFV_MARCH_ASM_PER_BOX(RUN, SDFV_MARCH_ASM_VOL_TEX0); }
     const bool cube = a.cube_box != 0;  // wave-uniform: one scalar branch per kernel
     if (T) {
         float tt = dist_from_origin;
         int n = 0;
-        if (STRIDE == 3) {
-            if (cube) SDFV_MARCH_ASM_RUN_AUX("s82", SDFV_MARCH_ASM_INTERIOR_ILV, SDFV_MARCH_ASM_FETCH_ILV, SDFV_MARCH_ASM_OOB_CUBE);
-            else SDFV_MARCH_ASM_RUN_AUX("s82", SDFV_MARCH_ASM_INTERIOR_ILV, SDFV_MARCH_ASM_FETCH_ILV, SDFV_MARCH_ASM_OOB_BOX);
-        } else if (STRIDE == 2) {
-            if (cube) SDFV_MARCH_ASM_RUN_AUX("s85", SDFV_MARCH_ASM_INTERIOR_PAIRS, SDFV_MARCH_ASM_FETCH_PAIRS, SDFV_MARCH_ASM_OOB_CUBE);
-            else SDFV_MARCH_ASM_RUN_AUX("s85", SDFV_MARCH_ASM_INTERIOR_PAIRS, SDFV_MARCH_ASM_FETCH_PAIRS, SDFV_MARCH_ASM_OOB_BOX);
-        } else if (STRIDE == 1) {
-            if (cube) SDFV_MARCH_ASM_RUN_AUX("s82", SDFV_MARCH_ASM_INTERIOR_DIST, SDFV_MARCH_ASM_FETCH_DIST, SDFV_MARCH_ASM_OOB_CUBE);
-            else SDFV_MARCH_ASM_RUN_AUX("s82", SDFV_MARCH_ASM_INTERIOR_DIST, SDFV_MARCH_ASM_FETCH_DIST, SDFV_MARCH_ASM_OOB_BOX);
-        } else {
-            if (cube) SDFV_MARCH_ASM_RUN_AUX("s83", SDFV_MARCH_ASM_INTERIOR_TEX0, SDFV_MARCH_ASM_FETCH_TEX0, SDFV_MARCH_ASM_OOB_CUBE);
-            else SDFV_MARCH_ASM_RUN_AUX("s83", SDFV_MARCH_ASM_INTERIOR_TEX0, SDFV_MARCH_ASM_FETCH_TEX0, SDFV_MARCH_ASM_OOB_BOX);
-        }
+        SDFV_MARCH_ASM_PER_VOLUME(SDFV_MARCH_ASM_RUN_AUX)
         dist_from_origin = tt;
         steps = n;
-    } else if (STRIDE == 3) {
-        if (cube) SDFV_MARCH_ASM_RUN("s82", SDFV_MARCH_ASM_INTERIOR_ILV, SDFV_MARCH_ASM_FETCH_ILV, SDFV_MARCH_ASM_OOB_CUBE);
-        else SDFV_MARCH_ASM_RUN("s82", SDFV_MARCH_ASM_INTERIOR_ILV, SDFV_MARCH_ASM_FETCH_ILV, SDFV_MARCH_ASM_OOB_BOX);
-    } else if (STRIDE == 2) {
-        if (cube) SDFV_MARCH_ASM_RUN("s85", SDFV_MARCH_ASM_INTERIOR_PAIRS, SDFV_MARCH_ASM_FETCH_PAIRS, SDFV_MARCH_ASM_OOB_CUBE);
-        else SDFV_MARCH_ASM_RUN("s85", SDFV_MARCH_ASM_INTERIOR_PAIRS, SDFV_MARCH_ASM_FETCH_PAIRS, SDFV_MARCH_ASM_OOB_BOX);
-    } else if (STRIDE == 1) {
-        if (cube) SDFV_MARCH_ASM_RUN("s82", SDFV_MARCH_ASM_INTERIOR_DIST, SDFV_MARCH_ASM_FETCH_DIST, SDFV_MARCH_ASM_OOB_CUBE);
-        else SDFV_MARCH_ASM_RUN("s82", SDFV_MARCH_ASM_INTERIOR_DIST, SDFV_MARCH_ASM_FETCH_DIST, SDFV_MARCH_ASM_OOB_BOX);
     } else {
-        if (cube) SDFV_MARCH_ASM_RUN("s83", SDFV_MARCH_ASM_INTERIOR_TEX0, SDFV_MARCH_ASM_FETCH_TEX0, SDFV_MARCH_ASM_OOB_CUBE);
-        else SDFV_MARCH_ASM_RUN("s83", SDFV_MARCH_ASM_INTERIOR_TEX0, SDFV_MARCH_ASM_FETCH_TEX0, SDFV_MARCH_ASM_OOB_BOX);
+        SDFV_MARCH_ASM_PER_VOLUME(SDFV_MARCH_ASM_RUN)
     }
 #ifdef SDFV_TUNING  // left = (iterations that ran the fetch block) << 16 | the down-counter at exit
     iterations = cov ? (min(255, 255 - (int)(short)(left & 0xffff)) | (left & 0xffff0000)) : 0;
@@ -649,10 +655,6 @@ __device__ __forceinline__ void stamp_wave(const RaymarchArgs& a, uint32_t bx, u
 }
 #endif
 
-__device__ __forceinline__ V3 pixel_ray_raw(const RaymarchArgs& a, const sdfv_camera& cam, uint32_t px, uint32_t py) {
-    return march::pixel_ray_raw(a.width, a.height, cam, px, py);
-}
-
 // The bbox fragment of that ray and main()'s ray set-up (march_common.h).  Returns whether the pixel is covered by the box.
 __device__ __forceinline__ bool box_fragment_ray(const RaymarchArgs& a, V3 eye, V3 d_raw, bool in_image,
                                                  V3& ray_origin, V3& ray_dir) {
@@ -663,10 +665,7 @@ __device__ __forceinline__ bool box_fragment_ray(const RaymarchArgs& a, V3 eye, 
     return covered;
 }
 
-// MODE: 0 = general kernel (any filter, any extents: the shader's nested loop with full MirroredRepeat);
-//       1 = fast march over tex0.r; 2 = fast march over the compact distance volume (both LINEAR only);
-//       3 = the hand-written loop over the y-pair volume (sdfv_commit_pairs; two 16-byte gathers per cell);
-//       4 = ... over the y-interleaved volume (sdfv_commit_interleaved; 4 B/voxel, 2 or 4 lines per cell).
+// MODE: kMarchGeneral .. kMarchIlv = 0 .. 4, what the march loop reads (raymarch_kernels.h).
 // XF:   0 = IEEE divide, 1 = exact power-of-two reciprocal, 2 = power-of-two extents and texture sizes.
 // AUX:  the per-pixel march record is stored (and distanceFromOrigin accumulated).
 #ifndef SDFV_RM_MIN_WAVES
@@ -757,7 +756,7 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
 #endif
 
     const V3 eye = mk(cam.eye[0], cam.eye[1], cam.eye[2]);
-    const V3 d_raw = pixel_ray_raw(a, cam, px, py);
+    const V3 d_raw = pixel_ray_raw(a.width, a.height, cam, px, py);
 
     // Conservative tile cull (the reference gets it from rasterising the box).  A ray that misses the box's
     // bounding sphere inflated by 1 % cannot be covered; if no lane of the wave can be covered, the wave
@@ -786,8 +785,9 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
         }
     }
 
-    const Tex tex0{a.tex0, (int)a.rp.tex_size[0], (int)a.rp.tex_size[1], (int)a.rp.tex_size[2]};
-    const Tex tex1{a.tex1, tex0.w, tex0.h, tex0.d};
+    const Tex tex0{a.tex0, (int)a.rp.tex_size[0], (int)a.rp.tex_size[1], (int)a.rp.tex_size[2], 0};
+    const Tex tex1{a.tex1, tex0.w, tex0.h, tex0.d, 0};
+    const float* tex0_r = reinterpret_cast<const float*>(a.tex0);
     V3 ray_origin, ray_dir;
     const bool covered = box_fragment_ray(a, eye, d_raw, in_image, ray_origin, ray_dir);
 
@@ -800,22 +800,10 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
 #ifdef SDFV_TUNING
     const unsigned long long t_loop0 = a.wave_timing ? __builtin_readcyclecounter() : 0ull;
 #endif
-#define SDFV_MARCH march_fast  // the C++ loop, where the hand-written one's specialisation does not apply
-    if (ASM && MODE == 1) {
-        march_asm<SYMM, 4, AUX>(a, reinterpret_cast<const float*>(a.tex0), tex0, ray_dir, covered, ray_pos, dist_from_origin,
-                                status, steps, iterations);
-    } else if (ASM && MODE == 2) {
-        march_asm<SYMM, 1, AUX>(a, a.dist, tex0, ray_dir, covered, ray_pos, dist_from_origin, status, steps, iterations);
-    } else if (ASM && MODE == 3) {
-        march_asm<SYMM, 2, AUX>(a, a.pairs, tex0, ray_dir, covered, ray_pos, dist_from_origin, status, steps, iterations);
-    } else if (ASM && MODE == 4) {
-        march_asm<SYMM, 3, AUX>(a, a.ilv, tex0, ray_dir, covered, ray_pos, dist_from_origin, status, steps, iterations);
-    } else if (MODE == 1) {
-        SDFV_MARCH<XF, SYMM, 4, AUX>(a, reinterpret_cast<const float*>(a.tex0), tex0, ray_dir, covered, ray_pos,
-                                     dist_from_origin, status, steps, iterations);
-    } else if (MODE >= 2) {  // (MODE 3 is only ever launched with the hand-written loop)
-        SDFV_MARCH<XF, SYMM, 1, AUX>(a, a.dist, tex0, ray_dir, covered, ray_pos, dist_from_origin, status, steps,
-                                     iterations);
+    if constexpr (FAST && ASM) {
+        march_asm<MODE, AUX>(a, tex0, ray_dir, covered, ray_pos, dist_from_origin, status, steps, iterations);
+    } else if constexpr (FAST) {  // the C++ loop, where the hand-written one's specialisation does not apply
+        march_fast<MODE, XF, SYMM, AUX>(a, tex0, ray_dir, covered, ray_pos, dist_from_origin, status, steps, iterations);
     } else {
         bool marching = covered;
         for (int i = 0; i < 255; ++i) {
@@ -826,7 +814,7 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
                     status = -2;
                     marching = false;
                 } else {
-                    float sample_dist = sample_r<LINEAR, XF, false>(a, tex0, ray_pos) - 1e-1f;
+                    float sample_dist = sample_r<LINEAR, XF, kMirror>(a, tex0_r, 4, tex0, ray_pos) - 1e-1f;
                     ++steps;
                     if (sample_dist < 1e-5f) {
                         status = 1;
@@ -853,13 +841,13 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
     if (status == 1) {
         // The fast kernels know the hit point is within 1e-4 of the box; the normal's taps are h further out,
         // a.fast_normal says whether floor(u) still stays in [-1, N-1] for them.
-        const float4 raw0 = sample_rgba<LINEAR, XF, FAST>(a, tex0, ray_pos);  // == the march's last sample
+        const float4 raw0 = sample_rgba<LINEAR, XF, FAST ? kClamp : kMirror>(a, tex0, ray_pos);  // == the march's last sample
         // one texture's eight 16-byte corners at a time: both sets in flight together cost 6 more VGPRs (78: one wave per
         // SIMD less) and buy nothing even for single frames, which are not occupancy-limited -- measured 1 % SLOWER on
         // every view at 1080p / 256^3 and 4K / 512^3 (round 3 A/B, profiles/r03_hit_path_ab.json)
         V3 pos1 = ray_pos;
         asm volatile("" : "+v"(pos1.x) : "v"(raw0.x), "v"(raw0.y), "v"(raw0.z), "v"(raw0.w));  // same value, after raw0
-        const float4 raw1 = sample_rgba<LINEAR, XF, FAST>(a, tex1, pos1);  // material.frag:154
+        const float4 raw1 = sample_rgba<LINEAR, XF, FAST ? kClamp : kMirror>(a, tex1, pos1);  // material.frag:154
         rgba = shade(a.rp, raw0, raw1);
         if (a.depth) {  // gl_FragDepth, material.frag:180-181
             frag_depth = frag_depth_of(cam.bvp, ray_pos.x, ray_pos.y, ray_pos.z);
@@ -869,21 +857,21 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
             const float h = tap_distance((float)tex0.w, (float)tex0.h, (float)tex0.d, a.rp.lod_dist_between_samples);
             const V3 p1 = normal_tap(ray_pos, h, 0), p2 = normal_tap(ray_pos, h, 1), p3 = normal_tap(ray_pos, h, 2), p4 = normal_tap(ray_pos, h, 3);
             float d1, d2, d3, d4;
-            if (MODE >= 2 && a.dist && a.fast_normal) {  // the taps read the compact distance volume too
-                d1 = sample_r_linear<XF, true, 1>(a, a.dist, tex0, p1) - 1e-1f;
-                d2 = sample_r_linear<XF, true, 1>(a, a.dist, tex0, p2) - 1e-1f;
-                d3 = sample_r_linear<XF, true, 1>(a, a.dist, tex0, p3) - 1e-1f;
-                d4 = sample_r_linear<XF, true, 1>(a, a.dist, tex0, p4) - 1e-1f;
+            if (MODE >= kMarchDist && a.dist && a.fast_normal) {  // the taps read the compact distance volume too
+                d1 = sample_r<true, XF, kClamp>(a, a.dist, 1, tex0, p1) - 1e-1f;
+                d2 = sample_r<true, XF, kClamp>(a, a.dist, 1, tex0, p2) - 1e-1f;
+                d3 = sample_r<true, XF, kClamp>(a, a.dist, 1, tex0, p3) - 1e-1f;
+                d4 = sample_r<true, XF, kClamp>(a, a.dist, 1, tex0, p4) - 1e-1f;
             } else if (FAST && a.fast_normal) {
-                d1 = sample_r<LINEAR, XF, true>(a, tex0, p1) - 1e-1f;
-                d2 = sample_r<LINEAR, XF, true>(a, tex0, p2) - 1e-1f;
-                d3 = sample_r<LINEAR, XF, true>(a, tex0, p3) - 1e-1f;
-                d4 = sample_r<LINEAR, XF, true>(a, tex0, p4) - 1e-1f;
+                d1 = sample_r<LINEAR, XF, kClamp>(a, tex0_r, 4, tex0, p1) - 1e-1f;
+                d2 = sample_r<LINEAR, XF, kClamp>(a, tex0_r, 4, tex0, p2) - 1e-1f;
+                d3 = sample_r<LINEAR, XF, kClamp>(a, tex0_r, 4, tex0, p3) - 1e-1f;
+                d4 = sample_r<LINEAR, XF, kClamp>(a, tex0_r, 4, tex0, p4) - 1e-1f;
             } else {
-                d1 = sample_r<LINEAR, XF, false>(a, tex0, p1) - 1e-1f;
-                d2 = sample_r<LINEAR, XF, false>(a, tex0, p2) - 1e-1f;
-                d3 = sample_r<LINEAR, XF, false>(a, tex0, p3) - 1e-1f;
-                d4 = sample_r<LINEAR, XF, false>(a, tex0, p4) - 1e-1f;
+                d1 = sample_r<LINEAR, XF, kMirror>(a, tex0_r, 4, tex0, p1) - 1e-1f;
+                d2 = sample_r<LINEAR, XF, kMirror>(a, tex0_r, 4, tex0, p2) - 1e-1f;
+                d3 = sample_r<LINEAR, XF, kMirror>(a, tex0_r, 4, tex0, p3) - 1e-1f;
+                d4 = sample_r<LINEAR, XF, kMirror>(a, tex0_r, 4, tex0, p4) - 1e-1f;
             }
             const V3 n = normal_of_taps(d1, d2, d3, d4);
             if (AUX) {
@@ -912,41 +900,6 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
 // Same arithmetic, same order as the MODE 0 loop above (hence as the oracle); what differs is WHO executes an
 // iteration: the rank whose slab holds the ray's cell.  Texel z-indices are clamped (the launcher requires the
 // fast_index condition) and rebased to the first resident slice.
-struct SlabTex {
-    const float4* data;
-    int w, h, d;    // GLOBAL texture size
-    int z_lo;       // first resident slice
-};
-
-__device__ __forceinline__ Footprint footprint_slab(const SlabTex& t, V3 p01, int& k0c) {
-    float u = p01.x * (float)t.w - 0.5f, v = p01.y * (float)t.h - 0.5f, w = p01.z * (float)t.d - 0.5f;
-    float fu = floorf(u), fv = floorf(v), fw = floorf(w);
-    Footprint f;
-    f.ax = u - fu; f.ay = v - fv; f.az = w - fw;
-    const int i0 = (int)fu, j0 = (int)fv, k0 = (int)fw;
-    const uint32_t sy = (uint32_t)t.w, sz = (uint32_t)t.w * (uint32_t)t.h;
-    const uint32_t i0m = (uint32_t)max(i0, 0), i1m = (uint32_t)min(i0 + 1, t.w - 1);
-    const uint32_t j0m = (uint32_t)max(j0, 0) * sy, j1m = (uint32_t)min(j0 + 1, t.h - 1) * sy;
-    k0c = min(max(k0, 0), t.d - 1);
-    const uint32_t k0m = (uint32_t)(max(k0, 0) - t.z_lo) * sz, k1m = (uint32_t)(min(k0 + 1, t.d - 1) - t.z_lo) * sz;
-    f.o000 = k0m + j0m + i0m; f.o100 = k0m + j0m + i1m;
-    f.o010 = k0m + j1m + i0m; f.o110 = k0m + j1m + i1m;
-    f.o001 = k1m + j0m + i0m; f.o101 = k1m + j0m + i1m;
-    f.o011 = k1m + j1m + i0m; f.o111 = k1m + j1m + i1m;
-    return f;
-}
-
-__device__ __forceinline__ float4 fetch_rgba(const float4* data, const Footprint& f) {
-    const float4 t000 = data[f.o000], t100 = data[f.o100], t010 = data[f.o010], t110 = data[f.o110];
-    const float4 t001 = data[f.o001], t101 = data[f.o101], t011 = data[f.o011], t111 = data[f.o111];
-    float4 r;
-    r.x = trilerp(t000.x, t100.x, t010.x, t110.x, t001.x, t101.x, t011.x, t111.x, f.ax, f.ay, f.az);
-    r.y = trilerp(t000.y, t100.y, t010.y, t110.y, t001.y, t101.y, t011.y, t111.y, f.ax, f.ay, f.az);
-    r.z = trilerp(t000.z, t100.z, t010.z, t110.z, t001.z, t101.z, t011.z, t111.z, f.ax, f.ay, f.az);
-    r.w = trilerp(t000.w, t100.w, t010.w, t110.w, t001.w, t101.w, t011.w, t111.w, f.ax, f.ay, f.az);
-    return r;
-}
-
 template <int XF, bool AUX>
 __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, SlabMarchArgs s) {
     const bool device_counts = s.in_count[0] != nullptr || s.in_count[1] != nullptr;
@@ -988,8 +941,8 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
     const uint32_t pixel = py * a.width + px;
     const V3 eye = mk(cam.eye[0], cam.eye[1], cam.eye[2]);
     V3 ray_origin, ray_dir;
-    const bool covered = box_fragment_ray(a, eye, pixel_ray_raw(a, cam, px, py), live, ray_origin, ray_dir);
-    const SlabTex tex{a.tex0, (int)a.rp.tex_size[0], (int)a.rp.tex_size[1], (int)a.rp.tex_size[2], (int)s.z_lo};
+    const bool covered = box_fragment_ray(a, eye, pixel_ray_raw(a.width, a.height, cam, px, py), live, ray_origin, ray_dir);
+    const Tex tex{a.tex0, (int)a.rp.tex_size[0], (int)a.rp.tex_size[1], (int)a.rp.tex_size[2], (int)s.z_lo};
     const float* dist_r = reinterpret_cast<const float*>(a.tex0);
 
     bool marching = live && covered;
@@ -1007,7 +960,7 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
         }
         // a ray that starts in another rank's slab is that rank's to begin
         int k0c;
-        (void)footprint_slab(tex, to_p01<XF>(a, ray_pos), k0c);
+        (void)footprint<kClampSlab>(tex, to_p01<XF>(a, ray_pos), k0c);
         marching = marching && k0c >= (int)s.own_begin && k0c < (int)s.own_end;
     }
     const bool mine = marching;  // this rank reports the ray's end unless it hands the ray over
@@ -1030,7 +983,7 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
             continue;
         }
         int k0c;
-        const Footprint f = footprint_slab(tex, to_p01<XF>(a, ray_pos), k0c);
+        const Footprint f = footprint<kClampSlab>(tex, to_p01<XF>(a, ray_pos), k0c);
         if (k0c < (int)s.own_begin || k0c >= (int)s.own_end) {
             // the cell belongs to a z-neighbour: hand the ray over exactly as it is -- after the loop, a wave at a time
             export_dir = k0c < (int)s.own_begin ? 0 : 1;
@@ -1096,8 +1049,8 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
     float4 rgba = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 raw0 = rgba, raw1 = rgba;
     if (status == 1) {
-        raw0 = fetch_rgba(a.tex0, hit_fp);  // == the march's last sample
-        raw1 = fetch_rgba(a.tex1, hit_fp);  // material.frag:154
+        raw0 = gather_rgba(a.tex0, hit_fp);  // == the march's last sample
+        raw1 = gather_rgba(a.tex1, hit_fp);  // material.frag:154
         rgba = shade(a.rp, raw0, raw1);
     }
     a.rgba[pixel] = rgba;
@@ -1118,7 +1071,6 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
                 bool resident = true;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    int kc;
                     const V3 q = to_p01<XF>(a, taps[k]);
                     const float w = q.z * (float)tex.d - 0.5f;
                     const int k0 = (int)floorf(w);
@@ -1126,10 +1078,7 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
                     resident = resident && lo >= (int)s.z_lo && hi < (int)(s.z_lo + s.z_count);
                     d[k] = 0.0f;
                     if (resident) {  // only then are the eight texels inside this rank's allocation
-                        const Footprint f = footprint_slab(tex, q, kc);
-                        d[k] = trilerp(dist_r[(uint64_t)f.o000 * 4], dist_r[(uint64_t)f.o100 * 4], dist_r[(uint64_t)f.o010 * 4],
-                                       dist_r[(uint64_t)f.o110 * 4], dist_r[(uint64_t)f.o001 * 4], dist_r[(uint64_t)f.o101 * 4],
-                                       dist_r[(uint64_t)f.o011 * 4], dist_r[(uint64_t)f.o111 * 4], f.ax, f.ay, f.az) - 1e-1f;
+                        d[k] = gather_r(dist_r, 4, footprint<kClampSlab>(tex, q)) - 1e-1f;
                     }
                 }
                 if (resident) aux_set_hit(aux, raw0, raw1, normal_of_taps(d[0], d[1], d[2], d[3]), depth);
@@ -1139,45 +1088,56 @@ __global__ __launch_bounds__(256) void raymarch_slab_kernel(RaymarchArgs a, Slab
     }
 }
 
-// unused dynamic LDS per workgroup (SDFV_OPT_RAYMARCH_WAVES_PER_SIMD): 160 KB per CU, one wave of a workgroup per SIMD
-#define SDFV_RM_LDS(a) ((a).lds_cap_bytes)
-template <int MODE, bool LINEAR, int XF, bool SYMM>
-void launch_aux(const RaymarchArgs& a, dim3 grid, hipStream_t stream) {
-    if (a.aux)
-        hipLaunchKernelGGL((raymarch_kernel<MODE, LINEAR, XF, SYMM, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-    else if (a.compute_normal)
-        hipLaunchKernelGGL((raymarch_kernel<MODE, LINEAR, XF, SYMM, false, false, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-    else
-        hipLaunchKernelGGL((raymarch_kernel<MODE, LINEAR, XF, SYMM, false>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-}
-
 // The hand-written loop addresses rows and slices by 24-bit multiplies (v_mad_u32_u24: full rate, any size -- not only powers
 // of two): row numbers k * H + j and the bytes of a row (16 * W for tex0) must stay below 2^24.
-static bool asm_addressing_ok(const RaymarchArgs& a) {
+bool asm_addressing_ok(const RaymarchArgs& a) {
     return a.rp.tex_size[0] < (1u << 20) && (uint64_t)a.rp.tex_size[1] * a.rp.tex_size[2] < (1ull << 24);
 }
 
-template <int MODE>
-void launch_fast(const RaymarchArgs& a, dim3 grid, hipStream_t stream) {
-    const int xf = a.pow2_extent ? (a.pow2_size ? 2 : 1) : 0;
-    const bool symm = a.symmetric_box != 0;
-    // the hand-written loop: its specialisation (power-of-two extents and sizes, symmetric box) and 32-bit byte offsets
+// Does the hand-written loop's specialisation apply to these render parameters?  LINEAR filter, clamp for mirror, the fused
+// scale (power-of-two extents, N below 2^24), symmetric box, the loop switched on (gfx950 only: the API layer clears asm_loop
+// elsewhere), at least two texels in x (its 8-byte border fetch) and its 24-bit addressing.
+bool hand_written_loop_applies(const RaymarchArgs& a) {
+    return a.rp.lod_dist_between_samples == 1.0f && a.fast_index && a.pow2_extent && a.pow2_size && a.symmetric_box && a.asm_loop &&
+           a.rp.tex_size[0] >= 2 && asm_addressing_ok(a);
+}
+
+// Does a volume of this MODE fit the loop's 32-bit byte offsets?  16 B/texel of tex0 and 8 B/texel of pairs reach 2^28 texels
+// with the loop's shifts, 4 B/voxel of dist and ilv 2^30.  The interleaved volume pairs rows: H even (and not 0).
+bool volume_fits_loop(const RaymarchArgs& a, int mode) {
     const uint64_t texels = (uint64_t)a.rp.tex_size[0] * a.rp.tex_size[1] * a.rp.tex_size[2];
-    if (xf == 2 && symm && a.asm_loop && a.rp.tex_size[0] >= 2 && asm_addressing_ok(a) && texels <= (MODE == 2 ? (1ull << 30) : (1ull << 28))) {
-        if (a.aux) hipLaunchKernelGGL((raymarch_kernel<MODE, true, 2, true, true, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-        else if (a.compute_normal)
-            hipLaunchKernelGGL((raymarch_kernel<MODE, true, 2, true, false, true, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-        else hipLaunchKernelGGL((raymarch_kernel<MODE, true, 2, true, false, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-        return;
+    switch (mode) {
+    case kMarchTex0:
+    case kMarchPairs: return texels <= (1ull << 28);
+    case kMarchDist: return texels <= (1ull << 30);
+    case kMarchIlv: return a.rp.tex_size[1] >= 2 && (a.rp.tex_size[1] & 1u) == 0 && texels <= (1ull << 30);
+    default: return false;
     }
-    if (xf == 2 && symm) launch_aux<MODE, true, 2, true>(a, grid, stream);
-    else if (xf == 2) launch_aux<MODE, true, 2, false>(a, grid, stream);
-    else if (xf == 1 && symm) launch_aux<MODE, true, 1, true>(a, grid, stream);
-    else if (xf == 1) launch_aux<MODE, true, 1, false>(a, grid, stream);
-    else launch_aux<MODE, true, 0, false>(a, grid, stream);
 }
 
 }  // namespace
+
+// Pointers apart, everything march_volume_choice decides on for `kind` -- asked BEFORE a volume exists (the advice
+// once checked less than the launcher, so a host could be advised a layout no march would ever read and then gather 16-byte
+// tex0 texels instead of its 4-byte distance volume).
+bool march_volume_applicable(const RaymarchArgs& a, int kind) {
+    return (kind == kMarchPairs || kind == kMarchIlv) && hand_written_loop_applies(a) && volume_fits_loop(a, kind);
+}
+
+// Which volume the hand-written loop marches over, of those at hand: kMarchIlv, kMarchPairs, or 0 for neither (the loop's
+// specialisation does not apply, or neither is there).  With both: the pair volume while its 8 B/voxel fit the last-level
+// cache (fewest gathers), the interleaved one beyond (half the footprint) -- profiles/r03_pairs_bench.json.
+int march_volume_choice(const RaymarchArgs& a, bool have_dist, bool have_pairs, bool have_ilv) {
+    const uint64_t texels = (uint64_t)a.rp.tex_size[0] * a.rp.tex_size[1] * a.rp.tex_size[2];
+    // a non-cubic grid never takes the loop's interior fetch (one compare for all three cell indices), and the border fetch of
+    // these two volumes is eight single loads against the distance volume's four 8-byte ones: with `dist` at hand, use it
+    const bool cubic = a.rp.tex_size[0] == a.rp.tex_size[1] && a.rp.tex_size[1] == a.rp.tex_size[2];
+    if (!cubic && have_dist) return 0;
+    const bool pairs_ok = have_pairs && march_volume_applicable(a, kMarchPairs);
+    const bool ilv_ok = have_ilv && march_volume_applicable(a, kMarchIlv);
+    if (pairs_ok && ilv_ok) return (a.last_level_cache_bytes && texels * 8u > a.last_level_cache_bytes) ? kMarchIlv : kMarchPairs;
+    return ilv_ok ? kMarchIlv : (pairs_ok ? kMarchPairs : 0);
+}
 
 namespace {
 constexpr uint32_t kStoreChunk = 32;  // 32 x 120 B + the two scalars: 3 856 B of kernel arguments
@@ -1220,7 +1180,78 @@ hipError_t launch_raymarch_slab(const RaymarchArgs& a, const SlabMarchArgs& s, h
     return hipGetLastError();
 }
 
-static hipError_t launch_raymarch_grid(const RaymarchArgs& a, dim3 grid, hipStream_t stream);
+namespace {
+
+int march_volume_mode(const RaymarchArgs& a) { return march_volume_choice(a, a.dist != nullptr, a.pairs != nullptr, a.ilv != nullptr); }
+
+// The kernel a launch takes (DESIGN.md 3.3 has this as a table).  The pair / interleaved volumes are acceleration structures
+// of the hand-written loop only: wherever that loop's specialisation does not apply the march reads the distance volume /
+// tex0.r as before -- the same bits either way.
+struct MarchKernel {
+    int mode;                // kMarch*
+    bool linear;             // LINEAR filter (lod_dist_between_samples == 1), else sdfSampleRawNearest
+    int xf;                  // 0 = IEEE divide, 1 = exact power-of-two reciprocal, 2 = ... and the fused scale (fast march only)
+    bool symm;               // |p| - max for the out-of-bounds distance (fast march with xf >= 1 only)
+    bool hand_written_loop;  // ASM
+};
+
+MarchKernel select_march_kernel(const RaymarchArgs& a) {
+    MarchKernel k{kMarchGeneral, a.rp.lod_dist_between_samples == 1.0f, a.pow2_extent ? 1 : 0, false, false};
+    if (!k.linear || !a.fast_index) return k;
+    k.mode = march_volume_mode(a);
+    if (k.mode == 0) k.mode = a.dist ? kMarchDist : kMarchTex0;
+    if (a.pow2_extent && a.pow2_size) k.xf = 2;
+    k.symm = k.xf >= 1 && a.symmetric_box;
+    k.hand_written_loop = hand_written_loop_applies(a) && volume_fits_loop(a, k.mode);
+    return k;
+}
+
+// AUX: the record is stored (and carries the normal); else NORMAL only for SDFV_OPT_RAYMARCH_KEEP_NORMAL.  The dynamic LDS is
+// unused: it caps the resident waves (lds_cap_for).
+template <int MODE, bool LINEAR, int XF, bool SYMM, bool ASM>
+void launch_variant(const RaymarchArgs& a, dim3 grid, hipStream_t stream) {
+    if (a.aux)
+        hipLaunchKernelGGL((raymarch_kernel<MODE, LINEAR, XF, SYMM, true, ASM>), grid, dim3(256), a.lds_cap_bytes, stream, a);
+    else if (a.compute_normal)
+        hipLaunchKernelGGL((raymarch_kernel<MODE, LINEAR, XF, SYMM, false, ASM, true>), grid, dim3(256), a.lds_cap_bytes, stream, a);
+    else
+        hipLaunchKernelGGL((raymarch_kernel<MODE, LINEAR, XF, SYMM, false, ASM>), grid, dim3(256), a.lds_cap_bytes, stream, a);
+}
+
+constexpr int variant_key(int mode, bool linear, int xf, bool symm, bool hand_written_loop) {
+    return mode | (linear ? 8 : 0) | (xf << 4) | (symm ? 64 : 0) | (hand_written_loop ? 128 : 0);
+}
+
+// Every instantiated raymarch_kernel, one line per (MODE, LINEAR, XF, SYMM, ASM).
+hipError_t launch_selected(const MarchKernel& k, const RaymarchArgs& a, dim3 grid, hipStream_t stream) {
+#define SDFV_VARIANT(MODE, LINEAR, XF, SYMM, ASM) \
+    case variant_key(MODE, LINEAR, XF, SYMM, ASM): launch_variant<MODE, LINEAR, XF, SYMM, ASM>(a, grid, stream); break
+    switch (variant_key(k.mode, k.linear, k.xf, k.symm, k.hand_written_loop)) {
+        SDFV_VARIANT(kMarchIlv, true, 2, true, true);
+        SDFV_VARIANT(kMarchPairs, true, 2, true, true);
+        SDFV_VARIANT(kMarchDist, true, 2, true, true);
+        SDFV_VARIANT(kMarchDist, true, 2, true, false);
+        SDFV_VARIANT(kMarchDist, true, 2, false, false);
+        SDFV_VARIANT(kMarchDist, true, 1, true, false);
+        SDFV_VARIANT(kMarchDist, true, 1, false, false);
+        SDFV_VARIANT(kMarchDist, true, 0, false, false);
+        SDFV_VARIANT(kMarchTex0, true, 2, true, true);
+        SDFV_VARIANT(kMarchTex0, true, 2, true, false);
+        SDFV_VARIANT(kMarchTex0, true, 2, false, false);
+        SDFV_VARIANT(kMarchTex0, true, 1, true, false);
+        SDFV_VARIANT(kMarchTex0, true, 1, false, false);
+        SDFV_VARIANT(kMarchTex0, true, 0, false, false);
+        SDFV_VARIANT(kMarchGeneral, true, 1, false, false);
+        SDFV_VARIANT(kMarchGeneral, true, 0, false, false);
+        SDFV_VARIANT(kMarchGeneral, false, 1, false, false);
+        SDFV_VARIANT(kMarchGeneral, false, 0, false, false);
+    default: return hipErrorInvalidValue;  // select_march_kernel names no other
+    }
+#undef SDFV_VARIANT
+    return hipGetLastError();
+}
+
+}  // namespace
 
 // Screen rectangle (in groups of tiles) of the bounding box seen from camera 0, for the box-first launch order: the eight
 // corners through the same pinhole model as pixel_ray_raw, one pixel of margin.  Order only: any rectangle renders the same
@@ -1267,43 +1298,13 @@ static void box_first_rectangle(RaymarchArgs& ag, uint32_t groups_y) {
 // box (box-first order) in waves, the machine's wave slots, the volume's bytes.  Rule: cap at 4 when the rectangle holds
 // between 1x and 3.5x the slots at 7 per SIMD and the volume exceeds the last-level cache; no cap otherwise (camera
 // inside, box filling the image, batches of cameras, small volumes, a box of a few tiles).  Speed only.
-// Which volume the hand-written loop marches over, of those the caller handed in: 4 the y-interleaved volume, 3 the pair
-// volume, 0 neither (the loop's specialisation does not apply, or neither was given).  With both: the pair volume while its
-// 8 B/voxel fit the last-level cache (fewest gathers), the interleaved one beyond (half the footprint) --
-// profiles/r03_pairs_bench.json.
-// Does the hand-written loop's specialisation apply to these render parameters, and may it address a volume of `kind` (3 the
-// pair volume, 4 the y-interleaved one)?  Pointers apart, everything march_volume_mode decides on -- sdfv_march_volume_advice
-// asks the same question BEFORE a volume exists (the advice once checked less than the launcher, so a host could
-// be advised a layout no march would ever read and then gather 16-byte tex0 texels instead of its 4-byte distance volume).
-bool march_volume_applicable(const RaymarchArgs& a, int kind) {
-    const uint64_t texels = (uint64_t)a.rp.tex_size[0] * a.rp.tex_size[1] * a.rp.tex_size[2];
-    const bool loop_ok = a.rp.lod_dist_between_samples == 1.0f && a.fast_index && a.pow2_extent && a.pow2_size && a.symmetric_box &&
-                         a.asm_loop && a.rp.tex_size[0] >= 2 && asm_addressing_ok(a);
-    // 32-bit byte offsets: 8 B/texel of pairs reach 2^28 texels with the loop's shifts, 4 B/voxel of ilv 2^30 (like dist)
-    if (kind == 3) return loop_ok && texels <= (1ull << 28);
-    if (kind == 4) return loop_ok && a.rp.tex_size[1] >= 2 && (a.rp.tex_size[1] & 1u) == 0 && texels <= (1ull << 30);
-    return false;
-}
-
-static int march_volume_mode(const RaymarchArgs& a) {
-    const uint64_t texels = (uint64_t)a.rp.tex_size[0] * a.rp.tex_size[1] * a.rp.tex_size[2];
-    // a non-cubic grid never takes the loop's interior fetch (one compare for all three cell indices), and the border fetch of
-    // these two volumes is eight single loads against the distance volume's four 8-byte ones: with `dist` at hand, use it
-    const bool cubic = a.rp.tex_size[0] == a.rp.tex_size[1] && a.rp.tex_size[1] == a.rp.tex_size[2];
-    if (!cubic && a.dist) return 0;
-    const bool pairs_ok = a.pairs && march_volume_applicable(a, 3);
-    const bool ilv_ok = a.ilv && march_volume_applicable(a, 4);
-    if (pairs_ok && ilv_ok) return (a.last_level_cache_bytes && texels * 8u > a.last_level_cache_bytes) ? 4 : 3;
-    return ilv_ok ? 4 : (pairs_ok ? 3 : 0);
-}
-
 static uint32_t occupancy_rule(const RaymarchArgs& ag) {
     if (ag.waves_per_simd >= 2 && ag.waves_per_simd <= 6) return ag.waves_per_simd;  // the caller's cap
     if (ag.waves_per_simd == 7) return 7;
     if (ag.n_cameras != 1 || ag.first_w == 0 || ag.group_shift == 0 || ag.wave_slots_per_simd_unit == 0) return 7;
     const uint64_t texels = (uint64_t)ag.rp.tex_size[0] * ag.rp.tex_size[1] * ag.rp.tex_size[2];
     const int mode = march_volume_mode(ag);
-    const uint64_t volume_bytes = texels * (mode == 3 ? 8u : ((mode == 4 || ag.dist) ? 4u : 16u));
+    const uint64_t volume_bytes = texels * (mode == kMarchPairs ? 8u : ((mode == kMarchIlv || ag.dist) ? 4u : 16u));
     if (ag.last_level_cache_bytes == 0 || volume_bytes <= ag.last_level_cache_bytes) return 7;
     const uint64_t rect_waves = (uint64_t)ag.first_w * ag.first_h * (4ull << (2 * ag.group_shift));  // 4 waves per 16 x 16 tile
     const uint64_t slots7 = 7ull * ag.wave_slots_per_simd_unit;
@@ -1328,7 +1329,7 @@ hipError_t launch_raymarch(const RaymarchArgs& a, hipStream_t stream) {
     if (a.tile_order) {
         ag.group_shift = 0;
         ag.lds_cap_bytes = lds_cap_for(occupancy_rule(ag));  // no rectangle here: the caller's cap or none
-        return launch_raymarch_grid(ag, dim3(tiles.x * tiles.y, 1, 1), stream);
+        return launch_selected(select_march_kernel(ag), ag, dim3(tiles.x * tiles.y, 1, 1), stream);
     }
 #endif
     // the 1-D launch over groups of 2^shift x 2^shift tiles (padded to whole groups, a multiple of 8 of them), with the
@@ -1355,36 +1356,7 @@ hipError_t launch_raymarch(const RaymarchArgs& a, hipStream_t stream) {
         grouped(a.group_shift);
     }
     ag.lds_cap_bytes = lds_cap_for(occupancy_rule(ag));
-    return launch_raymarch_grid(ag, grid, stream);
-}
-
-static hipError_t launch_raymarch_grid(const RaymarchArgs& a, dim3 grid, hipStream_t stream) {
-    const bool linear = a.rp.lod_dist_between_samples == 1.0f;
-    if (linear && a.fast_index) {
-        // the pair / interleaved volumes are acceleration structures of the hand-written loop only: wherever that loop's
-        // specialisation does not apply the march reads the distance volume / tex0.r as before -- the same bits either way
-        const int mode = march_volume_mode(a);
-        const bool ilv_ok = mode == 4, pairs_ok = mode == 3;
-        if (ilv_ok) {
-            if (a.aux) hipLaunchKernelGGL((raymarch_kernel<4, true, 2, true, true, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-            else if (a.compute_normal)
-                hipLaunchKernelGGL((raymarch_kernel<4, true, 2, true, false, true, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-            else hipLaunchKernelGGL((raymarch_kernel<4, true, 2, true, false, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-        } else if (pairs_ok) {
-            if (a.aux) hipLaunchKernelGGL((raymarch_kernel<3, true, 2, true, true, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-            else if (a.compute_normal)
-                hipLaunchKernelGGL((raymarch_kernel<3, true, 2, true, false, true, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-            else hipLaunchKernelGGL((raymarch_kernel<3, true, 2, true, false, true>), grid, dim3(256), SDFV_RM_LDS(a), stream, a);
-        } else if (a.dist) launch_fast<2>(a, grid, stream);
-        else launch_fast<1>(a, grid, stream);
-    } else if (linear) {
-        if (a.pow2_extent) launch_aux<0, true, 1, false>(a, grid, stream);
-        else launch_aux<0, true, 0, false>(a, grid, stream);
-    } else {
-        if (a.pow2_extent) launch_aux<0, false, 1, false>(a, grid, stream);
-        else launch_aux<0, false, 0, false>(a, grid, stream);
-    }
-    return hipGetLastError();
+    return launch_selected(select_march_kernel(ag), ag, grid, stream);
 }
 
 }  // namespace sdfv

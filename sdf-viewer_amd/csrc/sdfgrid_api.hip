@@ -1230,8 +1230,6 @@ int sdfv_march_volume_advice(const sdfv_grid* grid, uint32_t* kind) {
     if (int rc = check_grid(grid)) return rc;
     if (!kind) return fail(SDFV_ERR_INVALID_ARGUMENT, "kind is NULL");
     if (int rc = need_device()) return rc;
-    const uint64_t n = (uint64_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
-    const uint64_t llc = device_facts().last_level_cache_bytes;
     // only the hand-written gfx950 loop reads these volumes -- on another device, or with that loop switched off, a
     // host would allocate 4-8 B/voxel and re-run the commit after every fill for a volume no march ever touches.  ADVICE r04:
     // and the loop's OTHER conditions (power-of-two extents, symmetric box, clamp-for-mirror, its addressing limits) are
@@ -1243,14 +1241,10 @@ int sdfv_march_volume_advice(const sdfv_grid* grid, uint32_t* kind) {
     sdfv::RaymarchArgs a;
     derive_raymarch_args(&rp, a);
     if (!device_facts().gfx950) a.asm_loop = 0;
-    const bool cubic = grid->dims[0] == grid->dims[1] && grid->dims[1] == grid->dims[2];
-    const bool pairs_ok = sdfv::march_volume_applicable(a, 3), ilv_ok = sdfv::march_volume_applicable(a, 4);
-    if (!cubic)
-        *kind = SDFV_MARCH_VOLUME_NONE;  // the two-gather cell fetch is the cubic grid's: the distance volume marches fastest here
-    else if (ilv_ok && (!pairs_ok || (llc && n * 8u > llc)))
-        *kind = SDFV_MARCH_VOLUME_INTERLEAVED;
-    else
-        *kind = pairs_ok ? SDFV_MARCH_VOLUME_PAIRS : SDFV_MARCH_VOLUME_NONE;
+    a.last_level_cache_bytes = device_facts().last_level_cache_bytes;
+    // the launcher's own choice with all three volumes at hand (a grid that is not cubic marches fastest over its distance volume)
+    const int mode = sdfv::march_volume_choice(a, true, true, true);
+    *kind = mode == sdfv::kMarchIlv ? SDFV_MARCH_VOLUME_INTERLEAVED : mode == sdfv::kMarchPairs ? SDFV_MARCH_VOLUME_PAIRS : SDFV_MARCH_VOLUME_NONE;
     return SDFV_OK;
 }
 
