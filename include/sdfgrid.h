@@ -524,6 +524,46 @@ int sdfv_mesh_free(sdfv_mesh *mesh);
  * camera ring (SDFV_OPT_RAYMARCH_CAMERA_STAGING). */
 int sdfv_mesh_trim(void);
 
+/* ---- SDF programs: meshing (the reference's `mesh` command, src/sdf/meshers/, meshes any SDFSurface) ----
+ * The same pipeline over an sdfv_program: Meshers::mesh -> Mesh::postproc.  Arithmetic as in the program table above: IEEE f32,
+ * every step rounded on its own, left to right as written; d(q) is the program's distance at q (sample(q, true)).
+ *
+ *   normal(p, eps) = normal_default_impl (defaults.rs:49-56; a program does not override `normal`)
+ *     e  = eps > 0 ? eps : 0.001
+ *     d1 = d(p.x + e,         p.y + -1.0f * e, p.z + -1.0f * e)
+ *     d2 = d(p.x + -1.0f * e, p.y + e,         p.z + -1.0f * e)
+ *     d3 = d(p.x + -1.0f * e, p.y + -1.0f * e, p.z + e)
+ *     d4 = d(p.x + e,         p.y + e,         p.z + e)
+ *     v  = (d1 + -d2 + -d3 + d4,  -d1 + d2 + -d3 + d4,  -d1 + -d2 + d3 + d4)     sums left to right
+ *     n  = v * (1 / sqrt(v.x*v.x + v.y*v.y + v.z*v.z))                          per component; a zero v gives NaNs
+ *   extraction = sdfv_mesh_extract's conventions
+ *     lattice    cells + 1 points per axis, cells = max_voxels_per_axis on every axis; point i of an axis lies at
+ *                u = (float)i / (float)cells of the unit cube, p = u * (bb_max - bb_min) + bb_min
+ *     inside     d < 0
+ *     vertices   one per lattice edge towards +x, +y, +z whose ends differ in `inside`, in lattice order (x fastest), then
+ *                axis order; on the edge from u0 to u1 with distances d0, d1: t = d0 / (d0 - d1),
+ *                u = u0 + t * (u1 - u0) on the edge's axis, then p as above; normal = normal(p, None)
+ *     triangles  csrc/mc_table.inc (tools/gen_mc_table.py), cell by cell, x fastest
+ *   postproc = Mesh::postproc (meshers/mesh.rs:22-33)
+ *     colour, metallic, roughness, occlusion = the six material fields of sample(position, false), as they are (not packed,
+ *     not clamped: a MATERIAL with colour 1.5 gives 1.5); normal = normal(position, None) only where
+ *     nx*nx + ny*ny + nz*nz < 1e-4, untouched elsewhere.
+ * NaN rules as above: bit for bit while no NaN arises.  Like the other device entry points of a program these return
+ * SDFV_ERR_NO_DEVICE and write nothing without a device; argument errors are reported first. */
+/* SDFSurface::normal(p, eps) of the program for n points; eps <= 0 means None.  points, out: DEVICE, n x 3 floats. */
+int sdfv_program_normal_points(const sdfv_program *p, const float *points, size_t n, float eps, float *out, void *stream);
+#define SDFV_MESH_WITH_MATERIALS 1u /* vertices leave as extract + postproc would make them, in one pass */
+/* sdfv_mesh_extract for a program: limits (1 <= max_voxels_per_axis <= 1024, marching cubes only: "Unsupported algorithm"
+ * otherwise), synchronisation and ownership (sdfv_mesh_free) are the same, and so is the per-thread scratch (ONE block, the one
+ * sdfv_mesh_trim releases).  bb_min, bb_max: both NULL for the program's own box, or both given.  flags: 0 or
+ * SDFV_MESH_WITH_MATERIALS; without it the material fields are zero (Vertex::default) until sdfv_program_mesh_postproc. */
+int sdfv_program_mesh_extract(const sdfv_program *p, const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis,
+                              uint32_t algorithm, uint32_t flags, sdfv_mesh *out, void *stream);
+/* Mesh::postproc in place.  vertices: DEVICE, n x sdfv_vertex, 4-byte aligned (16-byte aligned arrays take 16-byte accesses). */
+int sdfv_program_mesh_postproc(const sdfv_program *p, sdfv_vertex *vertices, size_t n, void *stream);
+/* host buffer, evaluated ON THE DEVICE, like the other *_host calls */
+int sdfv_program_mesh_postproc_host(const sdfv_program *p, sdfv_vertex *vertices_host, size_t n);
+
 /* ---- raymarch ----
  * ONE exported entry point, one descriptor: sdfv_raymarch_ex.  The forms earlier ABI versions exported one by one
  * (sdfv_raymarch, _accel, _depth, _pairs, _volumes, _bands) are header-only wrappers at the end of this file that fill the

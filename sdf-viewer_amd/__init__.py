@@ -215,6 +215,12 @@ def mesh_extract(params, max_voxels_per_axis=64, bb_min=(-1.0, -1.0, -1.0), bb_m
     m = _capi.Mesh()
     check(lib.sdfv_mesh_extract(C.byref(params), sdf_id, f3(bb_min), f3(bb_max), int(max_voxels_per_axis),
                                 int(algorithm), C.byref(m), _stream_ptr(stream)))
+    return mesh_tensors(m)
+
+
+def mesh_tensors(m):
+    """An sdfv_mesh the library has just filled -> (vertices [n, 12] float32, indices [n_indices] int32) as torch tensors of
+    their own; the library's copy is freed."""
     try:
         dev = torch.device("cuda", torch.cuda.current_device())
         if m.n_vertices:

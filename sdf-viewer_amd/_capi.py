@@ -196,7 +196,14 @@ PROTOTYPES = {
                                                 C.c_void_p]),
     "sdfv_program_raymarch": (C.c_int, [C.POINTER(ProgramMarchDesc), C.c_void_p]),
     "sdfv_program_raymarch_check": (C.c_int, [C.POINTER(ProgramMarchDesc), C.POINTER(ProgramMarchDesc), C.POINTER(C.c_float)]),
+    # ... meshing
+    "sdfv_program_normal_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
+    "sdfv_program_mesh_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.POINTER(Mesh), C.c_void_p]),
+    "sdfv_program_mesh_postproc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sdfv_program_mesh_postproc_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
 }
+MESH_WITH_MATERIALS = 1
 LIGHT_AMBIENT, LIGHT_DIRECTIONAL, MAX_LIGHTS = 0, 1, 4
 
 

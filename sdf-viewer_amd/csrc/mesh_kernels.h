@@ -25,11 +25,18 @@ struct MeshWork {           // device scratch of one extraction, sized by mesh_w
 };
 
 size_t mesh_scan_tmp_bytes(size_t n);
-// Phase 1: lattice distances, edge masks, both scans.  Leaves the totals in totals_dev[0] (vertices), [1] (triangles).
-hipError_t launch_mesh_count(const sdfv_demo_params& prm, uint32_t sdf_id, const MeshGrid& g, const MeshWork& w,
-                             uint32_t* totals_dev, hipStream_t stream);
-// Phase 2: vertices (position + HermiteSource normal, the rest zero) and triangle indices.
-hipError_t launch_mesh_emit(const sdfv_demo_params& prm, uint32_t sdf_id, const MeshGrid& g, const MeshWork& w,
-                            sdfv_vertex* vertices, uint32_t* indices, hipStream_t stream);
+// An extraction is five steps on one stream; the first and the fourth evaluate the SDF, the others do not and serve every kind
+// of SDF (the demo tree here, SDF programs in program_mesh_kernels.hip):
+// 1. lattice distances into w.dist (the demo tree's)
+hipError_t launch_mesh_lattice(const sdfv_demo_params& prm, uint32_t sdf_id, const MeshGrid& g, const MeshWork& w,
+                               hipStream_t stream);
+// 2. edge masks, triangle counts, both scans.  Leaves the totals in totals_dev[0] (vertices), [1] (triangles).
+hipError_t launch_mesh_count(const MeshGrid& g, const MeshWork& w, uint32_t* totals_dev, hipStream_t stream);
+// 3. (the host reads the totals and allocates)
+// 4. vertices: position + HermiteSource normal of the demo tree, the rest zero
+hipError_t launch_mesh_vertices(const sdfv_demo_params& prm, uint32_t sdf_id, const MeshGrid& g, const MeshWork& w,
+                                sdfv_vertex* vertices, hipStream_t stream);
+// 5. triangle indices
+hipError_t launch_mesh_triangles(const MeshGrid& g, const MeshWork& w, uint32_t* indices, hipStream_t stream);
 
 }  // namespace sdfv

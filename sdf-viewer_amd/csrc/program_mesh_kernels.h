@@ -1,0 +1,28 @@
+// program_mesh_kernels.h -- launch interface of the mesh pipeline's SDF-program kernels (see program_mesh_kernels.hip): the two
+// steps of an extraction that evaluate the SDF (mesh_kernels.h has the other three), the batched normal and Mesh::postproc.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/sdfgrid.h"
+#include "mesh_kernels.h"
+
+namespace sdfv {
+
+// ops: the DEVICE copy of the validated program.
+// step 1 of an extraction: the program's distance at every lattice point into w.dist
+hipError_t launch_program_mesh_lattice(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const MeshWork& w,
+                                       hipStream_t stream);
+// step 4: the n_vertices vertices the scans of step 2 counted -- positions from the lattice, then one thread per vertex for the
+// normal (and, with `materials`, the material fields Mesh::postproc would write; zero otherwise)
+hipError_t launch_program_mesh_vertices(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const MeshWork& w,
+                                        sdfv_vertex* vertices, size_t n_vertices, bool materials, hipStream_t stream);
+// normal_default_impl of the program at n points: 12 bytes in, 12 bytes out
+hipError_t launch_program_normal_points(const sdfv_prog_op* ops, uint32_t n_ops, const float* points, size_t n, float eps,
+                                        float* out, hipStream_t stream);
+// Mesh::postproc in place
+hipError_t launch_program_mesh_postproc(const sdfv_prog_op* ops, uint32_t n_ops, sdfv_vertex* vertices, size_t n,
+                                        hipStream_t stream);
+
+}  // namespace sdfv

@@ -25,6 +25,7 @@
 #include "points_kernels.h"
 #include "program_kernels.h"
 #include "program_march_kernels.h"
+#include "program_mesh_kernels.h"
 #include "raymarch_kernels.h"
 
 namespace {
@@ -1105,18 +1106,16 @@ int sdfv_mesh_postproc(const sdfv_demo_params* params, uint32_t sdf_id, sdfv_ver
     return SDFV_OK;
 }
 
-int sdfv_mesh_extract(const sdfv_demo_params* params, uint32_t sdf_id, const float bb_min[3], const float bb_max[3],
-                      uint32_t max_voxels_per_axis, uint32_t algorithm, sdfv_mesh* out, void* stream) {
-    if (!out) return fail(SDFV_ERR_INVALID_ARGUMENT, "out is NULL");
-    memset(out, 0, sizeof(*out));
-    if (int rc = check_params(params, sdf_id)) return rc;
-    if (!bb_min || !bb_max) return fail(SDFV_ERR_INVALID_ARGUMENT, "bounding box is NULL");
-    if (algorithm != SDFV_MESHER_MARCHING_CUBES)
-        return fail(SDFV_ERR_INVALID_ARGUMENT, "Unsupported algorithm %u", algorithm);  // isosurface.rs:49
-    if (max_voxels_per_axis < 1 || max_voxels_per_axis > 1024)
-        return fail(SDFV_ERR_INVALID_ARGUMENT, "max_voxels_per_axis %u is outside [1, 1024]", max_voxels_per_axis);
-    if (int rc = need_device()) return rc;
-    hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+
+// Meshers::mesh for any SDF the device can evaluate: the arguments are checked by the caller, `lattice(g, w, stream)` writes the
+// distances of the lattice points and `vertices(g, w, vertices, n, stream)` the vertices of the crossing edges; counting, the
+// scans and the triangles (mesh_kernels.h) do not depend on the SDF.  The scratch is the calling thread's one block.
+template <typename LatticeFn, typename VerticesFn>
+int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis, sdfv_mesh* out, hipStream_t st,
+                 LatticeFn&& lattice, VerticesFn&& vertices) {
     sdfv::MeshGrid g;
     for (int i = 0; i < 3; ++i) {
         g.cells[i] = max_voxels_per_axis;
@@ -1148,7 +1147,8 @@ int sdfv_mesh_extract(const sdfv_demo_params* params, uint32_t sdf_id, const flo
     w.point_mask = (uint8_t*)(base + o_mask);
     w.scan_tmp = base + o_tmp;
     struct { void* p; } totals{base + o_totals};
-    SDFV_HIP(sdfv::launch_mesh_count(*params, sdf_id, g, w, (uint32_t*)totals.p, st));
+    SDFV_HIP(lattice(g, w, st));
+    SDFV_HIP(sdfv::launch_mesh_count(g, w, (uint32_t*)totals.p, st));
     uint32_t n[2] = {0, 0};
     SDFV_HIP(hipMemcpyAsync(n, totals.p, 8, hipMemcpyDeviceToHost, st));
     SDFV_HIP(hipStreamSynchronize(st));
@@ -1163,7 +1163,8 @@ int sdfv_mesh_extract(const sdfv_demo_params* params, uint32_t sdf_id, const flo
             return hip_fail(e, "hipMalloc(indices)");
         }
     }
-    hipError_t e = sdfv::launch_mesh_emit(*params, sdf_id, g, w, m.vertices, m.indices, st);
+    hipError_t e = vertices(g, w, m.vertices, m.n_vertices, st);
+    if (e == hipSuccess) e = sdfv::launch_mesh_triangles(g, w, m.indices, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);  // the next extraction on this thread reuses the scratch
     if (e != hipSuccess) {
         (void)hipFree(m.vertices);
@@ -1172,6 +1173,31 @@ int sdfv_mesh_extract(const sdfv_demo_params* params, uint32_t sdf_id, const flo
     }
     *out = m;
     return SDFV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdfv_mesh_extract(const sdfv_demo_params* params, uint32_t sdf_id, const float bb_min[3], const float bb_max[3],
+                      uint32_t max_voxels_per_axis, uint32_t algorithm, sdfv_mesh* out, void* stream) {
+    if (!out) return fail(SDFV_ERR_INVALID_ARGUMENT, "out is NULL");
+    memset(out, 0, sizeof(*out));
+    if (int rc = check_params(params, sdf_id)) return rc;
+    if (!bb_min || !bb_max) return fail(SDFV_ERR_INVALID_ARGUMENT, "bounding box is NULL");
+    if (algorithm != SDFV_MESHER_MARCHING_CUBES)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "Unsupported algorithm %u", algorithm);  // isosurface.rs:49
+    if (max_voxels_per_axis < 1 || max_voxels_per_axis > 1024)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "max_voxels_per_axis %u is outside [1, 1024]", max_voxels_per_axis);
+    if (int rc = need_device()) return rc;
+    return extract_mesh(
+        bb_min, bb_max, max_voxels_per_axis, out, (hipStream_t)stream,
+        [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, hipStream_t st) {
+            return sdfv::launch_mesh_lattice(*params, sdf_id, g, w, st);
+        },
+        [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, sdfv_vertex* vertices, size_t, hipStream_t st) {
+            return sdfv::launch_mesh_vertices(*params, sdf_id, g, w, vertices, st);
+        });
 }
 
 int sdfv_mesh_trim(void) {
@@ -1644,6 +1670,70 @@ int sdfv_program_sample_points_host(const sdfv_program* p, const float* points_h
     return run_over_host_buffers(points_host, n * 12, out_host, n * sizeof(sdfv_sample), [&](void* in, void* out) {
         return sdfv_program_sample_points(p, (const float*)in, n, distance_only, (sdfv_sample*)out, nullptr);
     });
+}
+
+int sdfv_program_normal_points(const sdfv_program* p, const float* points, size_t n, float eps, float* out, void* stream) {
+    if (!p) return fail(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if (n && (!points || !out)) return fail(SDFV_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (((uintptr_t)points | (uintptr_t)out) & 3) return fail(SDFV_ERR_INVALID_ARGUMENT, "points and out must be 4-byte aligned");
+    if (int rc = need_device()) return rc;
+    if (n == 0) return SDFV_OK;
+    const sdfv_prog_op* dev_ops = nullptr;
+    if (int rc = program_device_ops(p, &dev_ops)) return rc;
+    SDFV_HIP(sdfv::launch_program_normal_points(dev_ops, (uint32_t)p->ops.size(), points, n, eps, out, (hipStream_t)stream));
+    return SDFV_OK;
+}
+
+int sdfv_program_mesh_extract(const sdfv_program* p, const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis,
+                              uint32_t algorithm, uint32_t flags, sdfv_mesh* out, void* stream) {
+    if (!out) return fail(SDFV_ERR_INVALID_ARGUMENT, "out is NULL");
+    memset(out, 0, sizeof(*out));
+    if (!p) return fail(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if ((bb_min == nullptr) != (bb_max == nullptr))
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "bounding box: bb_min and bb_max are both given or both NULL (the program's box)");
+    if (algorithm != SDFV_MESHER_MARCHING_CUBES)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "Unsupported algorithm %u", algorithm);  // isosurface.rs:49
+    if (max_voxels_per_axis < 1 || max_voxels_per_axis > 1024)
+        return fail(SDFV_ERR_INVALID_ARGUMENT, "max_voxels_per_axis %u is outside [1, 1024]", max_voxels_per_axis);
+    if (flags & ~SDFV_MESH_WITH_MATERIALS) return fail(SDFV_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
+    if (int rc = need_device()) return rc;
+    const sdfv_prog_op* dev_ops = nullptr;
+    if (int rc = program_device_ops(p, &dev_ops)) return rc;
+    const uint32_t n_ops = (uint32_t)p->ops.size();
+    const bool materials = (flags & SDFV_MESH_WITH_MATERIALS) != 0;
+    return extract_mesh(
+        bb_min ? bb_min : p->bb, bb_max ? bb_max : p->bb + 3, max_voxels_per_axis, out, (hipStream_t)stream,
+        [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, hipStream_t st) {
+            return sdfv::launch_program_mesh_lattice(dev_ops, n_ops, g, w, st);
+        },
+        [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, sdfv_vertex* vertices, size_t n, hipStream_t st) {
+            return sdfv::launch_program_mesh_vertices(dev_ops, n_ops, g, w, vertices, n, materials, st);
+        });
+}
+
+int sdfv_program_mesh_postproc(const sdfv_program* p, sdfv_vertex* vertices, size_t n, void* stream) {
+    if (!p) return fail(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if (n && !vertices) return fail(SDFV_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if ((uintptr_t)vertices & 3) return fail(SDFV_ERR_INVALID_ARGUMENT, "vertices must be 4-byte aligned");
+    if (int rc = need_device()) return rc;
+    if (n == 0) return SDFV_OK;
+    const sdfv_prog_op* dev_ops = nullptr;
+    if (int rc = program_device_ops(p, &dev_ops)) return rc;
+    SDFV_HIP(sdfv::launch_program_mesh_postproc(dev_ops, (uint32_t)p->ops.size(), vertices, n, (hipStream_t)stream));
+    return SDFV_OK;
+}
+
+int sdfv_program_mesh_postproc_host(const sdfv_program* p, sdfv_vertex* vertices_host, size_t n) {
+    if (!p) return fail(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if (n && !vertices_host) return fail(SDFV_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (int rc = need_device()) return rc;
+    if (n == 0) return SDFV_OK;
+    DeviceBuf dv;
+    SDFV_HIP(hipMalloc(&dv.p, n * sizeof(sdfv_vertex)));
+    SDFV_HIP(hipMemcpy(dv.p, vertices_host, n * sizeof(sdfv_vertex), hipMemcpyHostToDevice));
+    if (int rc = sdfv_program_mesh_postproc(p, (sdfv_vertex*)dv.p, n, nullptr)) return rc;
+    SDFV_HIP(hipMemcpy(vertices_host, dv.p, n * sizeof(sdfv_vertex), hipMemcpyDeviceToHost));
+    return SDFV_OK;
 }
 
 int sdfv_program_fill_grid_commit(const sdfv_program* p, const sdfv_grid* grid, float* tex0, float* tex1, float* dist,

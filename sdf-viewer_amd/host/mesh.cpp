@@ -25,14 +25,17 @@ std::optional<Mesh> mesh_sdf(Meshers mesher, const SDFSurface& sdf, const Mesher
         return std::nullopt;
     };
     const auto dev = sdf.device_sdf();
-    if (!dev) return fail("this SDF has no device form: it cannot be meshed on the GPU");
+    const sdfv_program* program = dev ? nullptr : sdf.device_program();
+    if (!dev && !program) return fail("this SDF has no device form: it cannot be meshed on the GPU");
     if (mesher != Meshers::MarchingCubes) return fail("Unsupported algorithm");  // isosurface.rs:49
     const BoundingBox bb = sdf.bounding_box();
     const float lo[3] = {bb[0].x, bb[0].y, bb[0].z}, hi[3] = {bb[1].x, bb[1].y, bb[1].z};
     sdfv_mesh m{};
-    if (sdfv_mesh_extract(&dev->params, dev->sdf_id, lo, hi, (uint32_t)cfg.max_voxels_per_axis,
-                          SDFV_MESHER_MARCHING_CUBES, &m, nullptr) != SDFV_OK)
-        return fail(sdfv_last_error());
+    const int rc = dev ? sdfv_mesh_extract(&dev->params, dev->sdf_id, lo, hi, (uint32_t)cfg.max_voxels_per_axis,
+                                           SDFV_MESHER_MARCHING_CUBES, &m, nullptr)
+                       : sdfv_program_mesh_extract(program, lo, hi, (uint32_t)cfg.max_voxels_per_axis,
+                                                   SDFV_MESHER_MARCHING_CUBES, 0, &m, nullptr);
+    if (rc != SDFV_OK) return fail(sdfv_last_error());
     Mesh out;
     out.vertices.resize(m.n_vertices);
     out.indices.resize(m.n_indices);
@@ -45,10 +48,10 @@ std::optional<Mesh> mesh_sdf(Meshers mesher, const SDFSurface& sdf, const Mesher
 }
 
 int Mesh::postproc(const SDFSurface& sdf) {
-    const auto dev = sdf.device_sdf();
-    if (!dev) return SDFV_ERR_INVALID_ARGUMENT;
-    return sdfv_mesh_postproc_host(&dev->params, dev->sdf_id, reinterpret_cast<sdfv_vertex*>(vertices.data()),
-                                   vertices.size());
+    sdfv_vertex* v = reinterpret_cast<sdfv_vertex*>(vertices.data());
+    if (const auto dev = sdf.device_sdf()) return sdfv_mesh_postproc_host(&dev->params, dev->sdf_id, v, vertices.size());
+    if (const sdfv_program* program = sdf.device_program()) return sdfv_program_mesh_postproc_host(program, v, vertices.size());
+    return SDFV_ERR_INVALID_ARGUMENT;
 }
 
 std::string format_f32(float v) {

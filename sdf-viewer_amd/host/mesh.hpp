@@ -1,9 +1,10 @@
 // mesh.hpp -- host mirror of the reference's mesh export (src/sdf/meshers/):
 //   struct Mesh / Vertex            meshers/mesh.rs:8-17,133-155
-//   Mesh::postproc                  meshers/mesh.rs:22-33     -> sdfv_mesh_postproc (device)
+//   Mesh::postproc                  meshers/mesh.rs:22-33     -> sdfv_mesh_postproc / sdfv_program_mesh_postproc (device)
 //   Mesh::serialize_ply             meshers/mesh.rs:37-129    (ASCII PLY through the un-vendored ply-rs crate)
-//   Config, Meshers, Mesher::mesh   meshers/mod.rs:92-149     -> sdfv_mesh_extract (device)
-// Only SDFs with a device form (SDFSurface::device_sdf) can be meshed: there is no CPU path.
+//   Config, Meshers, Mesher::mesh   meshers/mod.rs:92-149     -> sdfv_mesh_extract / sdfv_program_mesh_extract (device)
+// Only SDFs with a device form (SDFSurface::device_sdf, or SDFSurface::device_program: an SDF program) can be meshed: there is
+// no CPU path.
 #pragma once
 
 #include <cstdint>

@@ -26,6 +26,9 @@ class ProgramSDF final : public SDFSurface {
     // n_threads workers (<= 0: the CPUs this process may use).  srgb_round: SDFV_OPT_EXT_SRGB_QUANT.
     void raymarch(const sdfv_program_march_desc& checked, float normal_h, bool srgb_round, int n_threads) const;
 
+    // meshing on the device: sdfv_program_mesh_extract / sdfv_program_mesh_postproc through mesh_sdf() and Mesh::postproc()
+    const sdfv_program* device_program() const override { return program_; }
+
     const sdfv_program* program() const { return program_; }
 
    private:

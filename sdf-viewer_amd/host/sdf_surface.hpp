@@ -140,6 +140,11 @@ class SDFSurface {
     // synchronising.  SDFViewer::update then runs the reference's loop on the device (sdf_viewer_device.cpp).  A failure throws.
     virtual bool has_device_sampler() const { return false; }
     virtual void sample_batch_device(const float* /*points_dev*/, size_t /*n*/, sdfv_sample* /*out_dev*/, void* /*stream*/) const {}
+
+    // ============ the other device form (not in the reference) ============
+    // An SDF that IS an SDF program (include/sdfgrid.h, "SDF programs"): the handle the library's program entry points take.
+    // mesh_sdf() and Mesh::postproc() (mesh.hpp) take this route when device_sdf() is empty.  nullptr = not a program.
+    virtual const sdfv_program* device_program() const { return nullptr; }
 };
 
 // merge_bounding_boxes, defaults.rs:59-72

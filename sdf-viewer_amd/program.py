@@ -11,6 +11,7 @@
     records = prog.sample_points(points)               # [n, 3] CUDA tensor -> [n, 7]
     viewer.update(prog.as_surface())                   # progressive load through sdf-viewer_amd.viewer
     rgba = prog.render(camera, 1920, 1080)             # sphere-traced directly per pixel: no grid
+    vertices, indices = prog.mesh(128, materials=True) # marching cubes + Mesh::postproc: [V, 12], [3 * triangles]
 
 The builder only appends instructions; sdfv_program_create validates them (build() raises SdfvError with the message that
 names the offending instruction).
@@ -161,6 +162,35 @@ class CompiledProgram:
         out = np.empty((pts.shape[0], 7), np.float32)
         check(lib.sdfv_program_sample_points_host(self.h, pts.ctypes.data, pts.shape[0], int(bool(distance_only)), out.ctypes.data))
         return out
+
+    def mesh(self, n, bb=None, materials=False, stream=None):
+        """sdfv_program_mesh_extract: marching cubes over n^3 cells of `bb` (min.xyz + max.xyz; None: the program's box) ->
+        (vertices [V, 12] float32, indices [3 * triangles] int32), copied out of the library's buffers.  materials=True: the
+        vertices leave as mesh_postproc would make them (SDFV_MESH_WITH_MATERIALS)."""
+        from . import _stream_ptr, f3, mesh_tensors
+        m = _capi.Mesh()
+        lo, hi = (None, None) if bb is None else (f3(bb[:3]), f3(bb[3:]))
+        check(lib.sdfv_program_mesh_extract(self.h, lo, hi, int(n), 0, _capi.MESH_WITH_MATERIALS if materials else 0, C.byref(m),
+                                            _stream_ptr(stream)))
+        return mesh_tensors(m)
+
+    def normal_points(self, points, eps=0.0, stream=None):
+        """SDFSurface::normal(p, eps) of the program (eps <= 0: None): [n, 3] float32 CUDA tensor -> [n, 3]."""
+        import torch
+        from . import _dev_ptr, _stream_ptr
+        n = points.shape[0]
+        out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+        check(lib.sdfv_program_normal_points(self.h, _dev_ptr(points, "points") if n else None, n, float(eps),
+                                             C.c_void_p(out.data_ptr()) if n else None, _stream_ptr(stream)))
+        return out
+
+    def mesh_postproc(self, vertices, stream=None):
+        """Mesh::postproc in place over an [n, 12] float32 CUDA tensor of vertices; returns it."""
+        from . import VERTEX_FLOATS, _dev_ptr, _stream_ptr
+        assert vertices.dim() == 2 and vertices.shape[1] == VERTEX_FLOATS
+        n = vertices.shape[0]
+        check(lib.sdfv_program_mesh_postproc(self.h, _dev_ptr(vertices, "vertices") if n else None, n, _stream_ptr(stream)))
+        return vertices
 
     def fill_grid(self, grid, tex0, tex1, dist=None, flags=0, stream=None):
         """sdfv_program_fill_grid_commit; flags: _capi.PASS_VOLUME_INTERLEAVED when `dist` is the y-interleaved volume."""

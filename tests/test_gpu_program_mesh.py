@@ -1,0 +1,233 @@
+"""Meshing over SDF programs on the device (include/sdfgrid.h, "SDF programs: meshing") against the numpy restatement of
+tests/program_mesh_ref.py, bit for bit: extraction, the fused materials, Mesh::postproc's rule, the batched normal, the
+properties any correct extractor has, the one scratch pool, and the C++ host route.  The programs are program_ref.catalogue's."""
+import functools
+import importlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import program_mesh_ref as M
+import program_ref as R
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+
+
+@pytest.fixture(scope="module")
+def PM(pkg):
+    return importlib.import_module("sdf-viewer_amd.program")
+
+
+@pytest.fixture(scope="module")
+def cat(PM):
+    return R.catalogue(PM)
+
+
+@pytest.fixture(scope="module")
+def built(cat):
+    progs = {}
+
+    def get(name):
+        if name not in progs:
+            progs[name] = cat[name].build()
+        return progs[name]
+    return get
+
+
+@functools.lru_cache(maxsize=None)
+def _restated(name, n, materials, bb):
+    PM = importlib.import_module("sdf-viewer_amd.program")
+    b = R.catalogue(PM)[name]
+    return M.extract(b.ops, n, b.bb if bb is None else bb, materials)
+
+
+def restated(name, n, materials=False, bb=None):
+    """The restatement's (vertices, indices) for a catalogue program: computed once, shared, never modified."""
+    v, i, _ = _restated(name, n, materials, bb)
+    v.setflags(write=False)
+    i.setflags(write=False)
+    return v, i
+
+
+def host(v, i):
+    return v.cpu().numpy(), i.cpu().numpy().astype(np.int64)
+
+
+def assert_mesh_equal(got_v, got_i, want_v, want_i, what):
+    assert got_v.shape == want_v.shape and got_i.shape == want_i.shape, (what, got_v.shape, want_v.shape, got_i.shape, want_i.shape)
+    assert (M.bits(got_v[:, :3]) == M.bits(want_v[:, :3])).all(), (what, "positions")
+    assert (got_i == want_i).all(), (what, "indices")
+    assert (M.bits(got_v[:, 3:6]) == M.bits(want_v[:, 3:6])).all(), (what, "normals")
+    assert (M.bits(got_v[:, 6:]) == M.bits(want_v[:, 6:])).all(), (what, "material fields")
+
+
+# vertices the restatement gives (checked on the CPU); the three zeros are the empty-mesh cases
+COUNTS = {("single", 5): 24, ("anchor", 5): 0, ("no_material", 5): 0, ("all_ops", 5): 0, ("deep", 5): 26, ("ties", 5): 30,
+          ("single", 9): 144, ("anchor", 9): 360, ("no_material", 9): 80, ("all_ops", 9): 16, ("deep", 9): 95, ("ties", 9): 68,
+          ("single", 12): 222, ("anchor", 12): 840, ("no_material", 12): 128, ("all_ops", 12): 46, ("deep", 12): 173,
+          ("ties", 12): 162,
+          # 65 cells: a row of 66 points spans two waves, 287 k points, and the vertex counts leave a partial last block
+          ("single", 65): 7104, ("anchor", 65): 34776}
+
+
+@pytest.mark.parametrize("name,n", sorted(COUNTS))
+def test_extraction_is_the_restatement_bit_for_bit(built, name, n):
+    want_v, want_i = restated(name, n)
+    assert want_v.shape[0] == COUNTS[(name, n)]                       # so no comparison below passes vacuously
+    assert np.isfinite(want_v[:, 3:6]).all(), "every restated normal must be finite"
+    v, i = built(name).mesh(n)
+    if COUNTS[(name, n)] == 0:
+        assert tuple(v.shape) == (0, 12) and tuple(i.shape) == (0,)
+        return
+    got_v, got_i = host(v, i)
+    assert got_i.shape[0] > 0 and got_i.shape[0] % 3 == 0
+    assert_mesh_equal(got_v, got_i, want_v, want_i, (name, n))
+    assert (got_v[:, 6:] == 0).all()                                  # Vertex::default() without the flag
+
+
+# envelope: 256 instructions, 85 materials.  Its restatement has crossings at 12 cells (338 vertices) and none at 7, 9, 11, 13,
+# 17, 21 or 33 (checked on the CPU), so 12 it is.
+@pytest.mark.parametrize("name,n,bb", [("all_ops", 12, None), ("all_ops", 17, (-0.7, -0.7, -0.7, 0.7, 0.7, 0.7)), ("deep", 12, None),
+                                       ("late_material", 13, None), ("late_material", 7, None), ("envelope", 12, None)])
+def test_fused_materials_equal_extract_then_postproc_and_the_restatement(built, name, n, bb):
+    want_v, want_i = restated(name, n, True, bb)
+    assert want_v.shape[0] > 0 and np.isfinite(want_v).all()
+    assert len(np.unique(want_v[:, 6:], axis=0)) >= 2, "more than one material on the surface"
+    prog = built(name)
+    fv, fi = prog.mesh(n, bb=bb, materials=True)
+    pv, pi = prog.mesh(n, bb=bb)
+    assert (pv[:, 6:] == 0).all()
+    prog.mesh_postproc(pv)
+    torch.cuda.synchronize()
+    assert_mesh_equal(*host(fv, fi), want_v, want_i, (name, n, "fused"))
+    assert_mesh_equal(*host(pv, pi), want_v, want_i, (name, n, "extract + postproc"))
+
+
+def test_postproc_rule_and_raw_material_fields(pkg, built, cat):
+    """Hand-made vertices over program_ref.points(): normals above and below |n|^2 = 1e-4 mixed within every wave, then a whole
+    wave that needs none; kept normals are untouched bit for bit, the others equal the restatement.  all_ops: its out-of-range
+    material (colour 1.5, -0.2; occlusion -1) never lies ON its surface at the sizes tried (restatement, 9..33 cells), so it is
+    here, at arbitrary points, that those fields must arrive unclamped."""
+    ops = cat["all_ops"].ops
+    pts = R.points()
+    keep = np.isfinite(M.normals(ops, pts)).all(axis=1)                # no NaN normals among the compared vertices
+    pts = pts[keep][:1300]
+    n = len(pts)
+    assert n == 1300
+    rng = np.random.default_rng(5)
+    v = np.zeros((n, 12), F)
+    v[:, :3] = pts
+    v[:, 3:6] = rng.normal(size=(n, 3)).astype(F)
+    small = rng.random(n) < 0.5
+    small[256:320] = False                                             # one whole wave keeps its normals
+    small[320:384] = True                                              # ... and one recomputes them all
+    scale = np.where(rng.random(n) < 0.5, F(0.009), F(0.0))            # |n|^2 = 8.1e-5 * |g|^2-ish, or exactly zero
+    v[small, 3:6] = (v[small, 3:6] / np.linalg.norm(v[small, 3:6], axis=1, keepdims=True) * scale[small, None]).astype(F)
+    big = ~small
+    v[big, 3:6] = (v[big, 3:6] / np.linalg.norm(v[big, 3:6], axis=1, keepdims=True) * F(0.0101)).astype(F)   # 1.02e-4: kept
+    v[:, 6:] = 9.0
+    nn = v[:, 3] * v[:, 3] + v[:, 4] * v[:, 4] + v[:, 5] * v[:, 5]
+    assert ((nn < F(0.0001)) == small).all() and small[:256].any() and big[:256].any()
+    want = M.postproc(ops, v)
+    assert (want[:, 6] == F(1.5)).any() and (want[:, 11] == F(-1.0)).any() and (want[:, 7] == F(-0.2)).any()
+    assert (M.bits(want[big, 3:6]) == M.bits(v[big, 3:6])).all()
+    prog = built("all_ops")
+    for what, offset in (("aligned", 0), ("4-byte aligned", 1)):
+        buf = torch.zeros(n * 12 + 4, dtype=torch.float32, device="cuda")
+        t = buf[offset:offset + n * 12].view(n, 12)
+        assert t.data_ptr() % 16 == (0 if offset == 0 else 4)
+        t.copy_(torch.from_numpy(v))
+        prog.mesh_postproc(t)
+        got = t.cpu().numpy()
+        assert (M.bits(got) == M.bits(want)).all(), what
+        assert (buf[:offset] == 0).all() and (buf[offset + n * 12:] == 0).all(), what
+    # the host-buffer form
+    hv = v.copy()
+    assert pkg.lib.sdfv_program_mesh_postproc_host(prog.h, hv.ctypes.data, n) == 0
+    assert (M.bits(hv) == M.bits(want)).all()
+
+
+@pytest.mark.parametrize("eps", [0.0, 0.01])
+def test_normal_points_against_the_restatement(built, cat, eps):
+    pts = R.points()
+    for name in ("deep", "single"):
+        want = M.normals(cat[name].ops, pts, eps)
+        number = ~np.isnan(want)                                        # per component
+        assert np.isfinite(want).all(axis=1).sum() > 4000 and (~number).any()
+
+        def check(got, n, what):
+            w, k = want[:n], number[:n]
+            assert (M.bits(got)[k] == M.bits(w)[k]).all(), (name, what, "components that are numbers")
+            assert np.isnan(got[~k]).all(), (name, what, "components that are NaN")
+        prog = built(name)
+        dev = torch.from_numpy(pts).cuda()
+        for n in (1, 255, 257, 4099):
+            check(prog.normal_points(dev[:n].contiguous(), eps).cpu().numpy(), n, n)
+        # through a pointer offset by 4 bytes: the tail form does all of it
+        n = 4099
+        buf = torch.zeros(n * 3 + 4, dtype=torch.float32, device="cuda")
+        shifted = buf[1:1 + n * 3].view(n, 3)
+        shifted.copy_(dev[:n])
+        assert shifted.data_ptr() % 16 == 4
+        check(prog.normal_points(shifted, eps).cpu().numpy(), n, "offset by 4 bytes")
+
+
+@pytest.mark.parametrize("n", [16, 33])
+def test_the_sphere_is_a_closed_oriented_genus_0_surface_on_the_device(built, n):
+    v, i = host(*built("single").mesh(n))
+    M.assert_sphere_properties(v, i, n)
+
+
+def test_one_scratch_pool_serves_the_demo_and_programs(pkg, built):
+    prm = pkg.default_params()
+
+    def round_trip():
+        out = []
+        for step in (("demo", 24), ("single", 33), ("demo", 9), ("anchor", 12), ("single", 5), ("demo", 40), ("deep", 12)):
+            if step[0] == "demo":
+                v, i = pkg.mesh_extract(prm, step[1])
+            else:
+                v, i = built(step[0]).mesh(step[1])
+            out.append((v.cpu().numpy(), i.cpu().numpy()))
+        return out
+    before = round_trip()
+    for name, n, k in (("single", 33, 1), ("anchor", 12, 3), ("single", 5, 4), ("deep", 12, 6)):
+        want_v, want_i = restated(name, n)
+        assert_mesh_equal(before[k][0], before[k][1].astype(np.int64), want_v, want_i, (name, n))
+    assert pkg.lib.sdfv_mesh_trim() == 0 and pkg.lib.sdfv_mesh_trim() == 0
+    after = round_trip()
+    for (bv, bi), (av, ai) in zip(before, after):
+        assert bv.shape[0] > 0 and (M.bits(bv) == M.bits(av)).all() and (bi == ai).all()
+
+
+def test_cpp_host_meshes_a_program_like_the_python_route(pkg, built, cat, tmp_path):
+    """tests/c/program_mesh_host.cpp, linked against the product library: ProgramSDF -> mesh_sdf -> Mesh::postproc ->
+    serialize_ply; and mesh_sdf still refuses a surface with neither device form."""
+    lib = os.path.join(ROOT, "sdf-viewer_amd")
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    exe = tmp_path / "program_mesh_host"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__",
+                           "-I", os.path.join(rocm, "include"), "-I", os.path.join(lib, "host"),
+                           os.path.join(ROOT, "tests", "c", "program_mesh_host.cpp"), "-o", str(exe), "-L", lib, "-lsdfviewer_host",
+                           "-lsdfgrid", "-L", os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(rocm, "lib"),
+                           "-Wl,-rpath," + lib, "-ldl", "-pthread"])
+    b = cat["all_ops"]
+    assert tuple(F(x) for x in b.bb) == tuple(F(x) for x in (-1.0, -0.9, -0.8, 1.0, 0.9, 0.8))   # the driver's box
+    ops_file = tmp_path / "ops.bin"
+    ops_file.write_bytes(bytes(b.array())[:64 * len(b.ops)])
+    n = 12
+    r = subprocess.run([str(exe), str(ops_file), str(n), str(tmp_path / "v.bin"), str(tmp_path / "i.bin"), str(tmp_path / "m.ply")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "program_mesh_host ok" in r.stdout, (r.returncode, r.stdout, r.stderr)
+    got_v = np.fromfile(tmp_path / "v.bin", F).reshape(-1, 12)
+    got_i = np.fromfile(tmp_path / "i.bin", np.uint32).astype(np.int64)
+    pv, pi = host(*built("all_ops").mesh(n, materials=True))
+    assert pv.shape[0] == 46
+    assert_mesh_equal(got_v, got_i, pv, pi, "C++ host against the Python route")
+    ply = (tmp_path / "m.ply").read_text().split("\n")
+    assert ply[0] == "ply" and f"element vertex {pv.shape[0]}" in ply and f"element face {pi.shape[0] // 3}" in ply
