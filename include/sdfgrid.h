@@ -508,18 +508,22 @@ typedef struct sdfv_mesh {
     size_t       n_indices;
 } sdfv_mesh;
 #define SDFV_MESHER_MARCHING_CUBES 0u /* Meshers::MarchingCubes, meshers/mod.rs:118-119 (the default, :130-134) */
+#define SDFV_MESHER_DUAL_CONTOURING_PARTICLE 4u /* Meshers::DualContouringParticleBasedMinimization, isosurface::mesh(4, ..) */
 /* Meshers::mesh (meshers/mod.rs:136-149 -> isosurface.rs:16-66) on the device: max_voxels_per_axis^3 cells over the
  * unit cube mapped onto the bounding box, distances from ScalarSource, one vertex per crossing lattice edge with
  * its HermiteSource normal, material fields zero (Vertex::default) until sdfv_mesh_postproc.  The extraction
  * algorithm itself is the build's own (the reference delegates to the un-vendored `isosurface` crate); algorithms
- * other than marching cubes are rejected like the reference's "Unsupported algorithm" (isosurface.rs:49).
+ * other than marching cubes and SDFV_MESHER_DUAL_CONTOURING_PARTICLE ("Dual contouring" below: one vertex per cell the
+ * surface passes through, creases and corners kept) are rejected like the reference's "Unsupported algorithm"
+ * (isosurface.rs:49).
  * Synchronises `stream` (the output size is data dependent).  Vertex and triangle counts are 32-bit: a surface has
  * O(N^2) of them, far below 2^32 for max_voxels_per_axis <= 1024; a field crossing zero on nearly every lattice edge
  * (not a distance field) at the largest sizes would overflow them. */
 int sdfv_mesh_extract(const sdfv_demo_params *params, uint32_t sdf_id, const float bb_min[3], const float bb_max[3],
                       uint32_t max_voxels_per_axis, uint32_t algorithm, sdfv_mesh *out, void *stream);
 int sdfv_mesh_free(sdfv_mesh *mesh);
-/* sdfv_mesh_extract keeps its scratch (about 13 bytes per lattice point) for the calling thread's next extraction;
+/* sdfv_mesh_extract keeps its scratch (about 13 bytes per lattice point, about 17 once dual contouring has run: its third
+ * scan) for the calling thread's next extraction;
  * this releases it -- and the three side streams a batch of more than 64 cameras makes (SDFV_OPT_RAYMARCH_BATCH_STREAMS) and the
  * camera ring (SDFV_OPT_RAYMARCH_CAMERA_STAGING). */
 int sdfv_mesh_trim(void);
@@ -549,12 +553,48 @@ int sdfv_mesh_trim(void);
  *     not clamped: a MATERIAL with colour 1.5 gives 1.5); normal = normal(position, None) only where
  *     nx*nx + ny*ny + nz*nz < 1e-4, untouched elsewhere.
  * NaN rules as above: bit for bit while no NaN arises.  Like the other device entry points of a program these return
- * SDFV_ERR_NO_DEVICE and write nothing without a device; argument errors are reported first. */
+ * SDFV_ERR_NO_DEVICE and write nothing without a device; argument errors are reported first.
+ *
+ * ---- Dual contouring (SDFV_MESHER_DUAL_CONTOURING_PARTICLE, for the demo tree and for programs alike) ----
+ * Arithmetic as above: IEEE f32, every step rounded on its own, left to right as written, nothing contracted; min and max as the
+ * program table defines them; every sum starts at 0.0f and takes its terms in the order given.
+ *   lattice, inside, Hermite data   unchanged from marching cubes: for every crossing edge, in lattice order then axis order,
+ *                p_e = the marching-cubes vertex position of that edge and n_e = the SDF's normal(p_e, None).  An intermediate of
+ *                this algorithm, not its output.
+ *   vertices   one per ACTIVE cell, in cell order (x fastest); a cell is active when at least one of its 12 edges crosses.  The
+ *              cell's crossing edges are visited in the marching-cubes table's numbering, e = 4 * axis + u + 2 * v ascending
+ *              (the edge along `axis` from the corner offset by u along the lower and v along the higher other axis); m = their
+ *              count.
+ *                c  = (sum p_e) / (float)m                                         per component: the mass point
+ *                an edge is USED iff w = nx*nx + ny*ny + nz*nz has w > 0.5f && w < 2.0f   (NaN and zero normals are not); k = count
+ *                over the used edges, with r = p_e - c and b = (nx*r.x + ny*r.y) + nz*r.z:
+ *                  Mxx += nx*nx  Mxy += nx*ny  Mxz += nx*nz  Myy += ny*ny  Myz += ny*nz  Mzz += nz*nz
+ *                  gx += nx*b    gy += ny*b    gz += nz*b
+ *                y = 0; if k > 0: s = 1.0f / (float)k, then 24 times, all three components from the old y:
+ *                  tx = gx - ((Mxx*y.x + Mxy*y.y) + Mxz*y.z)
+ *                  ty = gy - ((Mxy*y.x + Myy*y.y) + Myz*y.z)
+ *                  tz = gz - ((Mxz*y.x + Myz*y.y) + Mzz*y.z)
+ *                  y  = y + s * t
+ *                x = c + y, then per axis x = max(lo, min(x, hi)), lo and hi the lattice positions of the cell's corners (i, j, k)
+ *                and (i + 1, j + 1, k + 1)
+ *              normal = normal(x, None); material fields zero until postproc, or, for a program with SDFV_MESH_WITH_MATERIALS,
+ *              as extract + postproc would leave the vertex.
+ *              This is gradient descent on sum (n_e . (x - p_e))^2 from the mass point with step 1 / k: the eigenvalues of M / k
+ *              lie in [0, 1], so it cannot diverge, and a direction the normals do not constrain (along a crease, within a face)
+ *              keeps the mass point's coordinate -- what a QEF solver needs a truncated SVD for.  On a balanced 90 degree crease
+ *              the error halves per step; on a cube corner it shrinks by 2/3 per step, (2/3)^24 = 6e-5.
+ *   triangles  two per INTERIOR crossing edge, in the Hermite order.  The edge from point (i, j, k) along axis a is interior when
+ *              all four cells around it exist (on both other axes 1 <= index <= cells - 1).  With o0 < o1 the two other axes, the
+ *              cells at (o0, o1) offsets (-1,-1), (0,-1), (0,0), (-1,0) from the point (same index along a) have the vertices
+ *              q0..q3; flip = (a == 1) != (d0 >= 0), d0 the distance at (i, j, k); the triangles are (q0,q1,q2), (q0,q2,q3), or
+ *              (q0,q2,q1), (q0,q3,q2) when flipped: counter-clockwise seen from outside.  Edges on the box's boundary emit
+ *              nothing: the surface is open where it leaves the box, as with marching cubes.
+ * Limits, synchronisation, ownership, the per-thread scratch and sdfv_mesh_trim are as for marching cubes. */
 /* SDFSurface::normal(p, eps) of the program for n points; eps <= 0 means None.  points, out: DEVICE, n x 3 floats. */
 int sdfv_program_normal_points(const sdfv_program *p, const float *points, size_t n, float eps, float *out, void *stream);
 #define SDFV_MESH_WITH_MATERIALS 1u /* vertices leave as extract + postproc would make them, in one pass */
-/* sdfv_mesh_extract for a program: limits (1 <= max_voxels_per_axis <= 1024, marching cubes only: "Unsupported algorithm"
- * otherwise), synchronisation and ownership (sdfv_mesh_free) are the same, and so is the per-thread scratch (ONE block, the one
+/* sdfv_mesh_extract for a program: limits (1 <= max_voxels_per_axis <= 1024; marching cubes or
+ * SDFV_MESHER_DUAL_CONTOURING_PARTICLE, "Unsupported algorithm" otherwise), synchronisation and ownership (sdfv_mesh_free) are the same, and so is the per-thread scratch (ONE block, the one
  * sdfv_mesh_trim releases).  bb_min, bb_max: both NULL for the program's own box, or both given.  flags: 0 or
  * SDFV_MESH_WITH_MATERIALS; without it the material fields are zero (Vertex::default) until sdfv_program_mesh_postproc. */
 int sdfv_program_mesh_extract(const sdfv_program *p, const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis,

@@ -167,6 +167,8 @@ def normal_points(params, points, eps=None, use_default=False, sdf_id=SDF_DEMO, 
     return out
 
 
+MESHER_MARCHING_CUBES = _capi.MESHER_MARCHING_CUBES
+MESHER_DUAL_CONTOURING_PARTICLE = _capi.MESHER_DUAL_CONTOURING_PARTICLE  # mesh_extract(algorithm=...): include/sdfgrid.h
 VERTEX_FLOATS = 12  # sdfv_vertex: position, normal, color, metallic, roughness, occlusion (meshers/mesh.rs:135-143)
 
 

@@ -204,6 +204,8 @@ PROTOTYPES = {
     "sdfv_program_mesh_postproc_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
 }
 MESH_WITH_MATERIALS = 1
+MESHER_MARCHING_CUBES = 0
+MESHER_DUAL_CONTOURING_PARTICLE = 4   # include/sdfgrid.h, "Dual contouring"
 LIGHT_AMBIENT, LIGHT_DIRECTIONAL, MAX_LIGHTS = 0, 1, 4
 
 

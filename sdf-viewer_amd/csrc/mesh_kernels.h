@@ -19,7 +19,9 @@ struct MeshWork {           // device scratch of one extraction, sized by mesh_w
     float* dist;            // [points] ScalarSource at every lattice point
     uint32_t* point_first;  // [points] first vertex id of the point's edges (exclusive scan of the edge counts)
     uint8_t* point_mask;    // [points] bit a: the edge towards +axis a crosses the surface
-    uint32_t* cell_first;   // [cells] first triangle of the cell (exclusive scan of the triangle counts)
+    uint32_t* cell_first;   // [cells] first triangle of the cell (exclusive scan of the triangle counts); dual contouring: the
+                            //         cell's vertex id (exclusive scan of a 0/1 per active cell)
+    uint32_t* quad_first;   // [points] dual contouring only (NULL otherwise): first quad of the point's interior crossing edges
     void* scan_tmp;
     size_t scan_tmp_bytes;
 };
@@ -32,11 +34,19 @@ hipError_t launch_mesh_lattice(const sdfv_demo_params& prm, uint32_t sdf_id, con
                                hipStream_t stream);
 // 2. edge masks, triangle counts, both scans.  Leaves the totals in totals_dev[0] (vertices), [1] (triangles).
 hipError_t launch_mesh_count(const MeshGrid& g, const MeshWork& w, uint32_t* totals_dev, hipStream_t stream);
+//    Its two parts, for an extractor that counts something else per cell (dual_contour_kernels.hip): edge masks + the point scan
+//    (checks the grid, as launch_mesh_lattice does), and the in-place exclusive scan of n counts through w.scan_tmp.
+hipError_t launch_mesh_edge_masks(const MeshGrid& g, const MeshWork& w, hipStream_t stream);
+hipError_t mesh_exclusive_scan(const MeshWork& w, uint32_t* counts, size_t n, hipStream_t stream);
 // 3. (the host reads the totals and allocates)
 // 4. vertices: position + HermiteSource normal of the demo tree, the rest zero
 hipError_t launch_mesh_vertices(const sdfv_demo_params& prm, uint32_t sdf_id, const MeshGrid& g, const MeshWork& w,
                                 sdfv_vertex* vertices, hipStream_t stream);
 // 5. triangle indices
 hipError_t launch_mesh_triangles(const MeshGrid& g, const MeshWork& w, uint32_t* indices, hipStream_t stream);
+// Dual contouring's last SDF step: normal = HermiteSource normal of the demo tree at the position of each of n vertices, the
+// rest of the record zero -- step 4's per-vertex part over a compacted list
+hipError_t launch_mesh_vertex_normals(const sdfv_demo_params& prm, uint32_t sdf_id, sdfv_vertex* vertices, size_t n,
+                                      hipStream_t stream);
 
 }  // namespace sdfv

@@ -18,6 +18,10 @@ hipError_t launch_program_mesh_lattice(const sdfv_prog_op* ops, uint32_t n_ops, 
 // normal (and, with `materials`, the material fields Mesh::postproc would write; zero otherwise)
 hipError_t launch_program_mesh_vertices(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const MeshWork& w,
                                         sdfv_vertex* vertices, size_t n_vertices, bool materials, hipStream_t stream);
+// the per-vertex half of step 4 by itself, over n vertices whose positions are written (16-byte aligned): what dual contouring
+// runs over its solved vertices -- the same kernels
+hipError_t launch_program_vertex_normals(const sdfv_prog_op* ops, uint32_t n_ops, sdfv_vertex* vertices, size_t n_vertices,
+                                         bool materials, hipStream_t stream);
 // normal_default_impl of the program at n points: 12 bytes in, 12 bytes out
 hipError_t launch_program_normal_points(const sdfv_prog_op* ops, uint32_t n_ops, const float* points, size_t n, float eps,
                                         float* out, hipStream_t stream);

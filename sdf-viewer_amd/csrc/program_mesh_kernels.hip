@@ -238,6 +238,13 @@ hipError_t launch_program_mesh_vertices(const sdfv_prog_op* ops, uint32_t n_ops,
     if (n_points > 0xffffffffull || n_vertices > 0xffffffffull || ((uintptr_t)vertices & 15)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(sdfprog_mesh_positions, dim3(blocks_for(n_points)), dim3(kBlock), 0, stream, g, w.dist, w.point_mask,
                        w.point_first, reinterpret_cast<float*>(vertices));
+    return launch_program_vertex_normals(ops, n_ops, vertices, n_vertices, materials, stream);
+}
+
+hipError_t launch_program_vertex_normals(const sdfv_prog_op* ops, uint32_t n_ops, sdfv_vertex* vertices, size_t n_vertices,
+                                         bool materials, hipStream_t stream) {
+    if (!vertices || n_vertices == 0) return hipSuccess;
+    if (n_vertices > 0xffffffffull || ((uintptr_t)vertices & 15)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(materials ? sdfprog_mesh_vertices_mat : sdfprog_mesh_vertices, dim3(blocks_for(n_vertices)), dim3(kBlock), 0,
                        stream, ops, n_ops, reinterpret_cast<float4*>(vertices), (uint32_t)n_vertices);
     return hipGetLastError();

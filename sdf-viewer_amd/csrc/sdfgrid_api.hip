@@ -26,6 +26,7 @@
 #include "program_kernels.h"
 #include "program_march_kernels.h"
 #include "program_mesh_kernels.h"
+#include "dual_contour_kernels.h"
 #include "raymarch_kernels.h"
 
 namespace {
@@ -1111,11 +1112,15 @@ int sdfv_mesh_postproc(const sdfv_demo_params* params, uint32_t sdf_id, sdfv_ver
 namespace {
 
 // Meshers::mesh for any SDF the device can evaluate: the arguments are checked by the caller, `lattice(g, w, stream)` writes the
-// distances of the lattice points and `vertices(g, w, vertices, n, stream)` the vertices of the crossing edges; counting, the
-// scans and the triangles (mesh_kernels.h) do not depend on the SDF.  The scratch is the calling thread's one block.
-template <typename LatticeFn, typename VerticesFn>
-int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis, sdfv_mesh* out, hipStream_t st,
-                 LatticeFn&& lattice, VerticesFn&& vertices) {
+// distances of the lattice points, `vertices(g, w, vertices, n, stream)` the marching-cubes vertices of the crossing edges and
+// `normals(vertices, n, stream)` everything but the position of n vertices whose positions are written; counting, the scans, the
+// triangles (mesh_kernels.h) and dual contouring's solve and quads (dual_contour_kernels.h) do not depend on the SDF.  Marching
+// cubes never calls `normals`; dual contouring calls `vertices` for its Hermite records, into a temporary.  The scratch is the
+// calling thread's one block.
+template <typename LatticeFn, typename VerticesFn, typename NormalsFn>
+int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis, uint32_t algorithm, sdfv_mesh* out,
+                 hipStream_t st, LatticeFn&& lattice, VerticesFn&& vertices, NormalsFn&& normals) {
+    const bool dual = algorithm == SDFV_MESHER_DUAL_CONTOURING_PARTICLE;
     sdfv::MeshGrid g;
     for (int i = 0; i < 3; ++i) {
         g.cells[i] = max_voxels_per_axis;
@@ -1131,7 +1136,7 @@ int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxe
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_dist = 0, o_first = o_dist + up(n_points * 4), o_cfirst = o_first + up(n_points * 4),
                  o_mask = o_cfirst + up(n_cells * 4), o_tmp = o_mask + up(n_points), o_totals = o_tmp + up(w.scan_tmp_bytes),
-                 need = o_totals + 256;
+                 o_qfirst = o_totals + 256, need = o_qfirst + (dual ? up(n_points * 4) : 0);  // dual contouring: one more scan
     const int device_now = current_device();
     if (g_mesh_scratch.bytes < need || g_mesh_scratch.device != device_now) {
         if (g_mesh_scratch.p) (void)hipFree(g_mesh_scratch.p);
@@ -1146,15 +1151,16 @@ int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxe
     w.cell_first = (uint32_t*)(base + o_cfirst);
     w.point_mask = (uint8_t*)(base + o_mask);
     w.scan_tmp = base + o_tmp;
+    w.quad_first = dual ? (uint32_t*)(base + o_qfirst) : nullptr;
     struct { void* p; } totals{base + o_totals};
     SDFV_HIP(lattice(g, w, st));
-    SDFV_HIP(sdfv::launch_mesh_count(g, w, (uint32_t*)totals.p, st));
-    uint32_t n[2] = {0, 0};
-    SDFV_HIP(hipMemcpyAsync(n, totals.p, 8, hipMemcpyDeviceToHost, st));
+    SDFV_HIP(dual ? sdfv::launch_dc_count(g, w, (uint32_t*)totals.p, st) : sdfv::launch_mesh_count(g, w, (uint32_t*)totals.p, st));
+    uint32_t n[3] = {0, 0, 0};  // marching cubes: vertices, triangles; dual contouring: Hermite records, vertices, quads
+    SDFV_HIP(hipMemcpyAsync(n, totals.p, dual ? 12 : 8, hipMemcpyDeviceToHost, st));
     SDFV_HIP(hipStreamSynchronize(st));
     sdfv_mesh m{};
-    m.n_vertices = n[0];
-    m.n_indices = (size_t)n[1] * 3;
+    m.n_vertices = dual ? n[1] : n[0];
+    m.n_indices = dual ? (size_t)n[2] * 6 : (size_t)n[1] * 3;
     if (m.n_vertices) SDFV_HIP(hipMalloc((void**)&m.vertices, m.n_vertices * sizeof(sdfv_vertex)));
     if (m.n_indices) {
         hipError_t e = hipMalloc((void**)&m.indices, m.n_indices * 4);
@@ -1163,9 +1169,23 @@ int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxe
             return hip_fail(e, "hipMalloc(indices)");
         }
     }
-    hipError_t e = vertices(g, w, m.vertices, m.n_vertices, st);
-    if (e == hipSuccess) e = sdfv::launch_mesh_triangles(g, w, m.indices, st);
+    hipError_t e = hipSuccess;
+    void* hermite = nullptr;  // dual contouring: n[0] Hermite records, then the list of the n[1] active cells
+    if (!dual) {
+        e = vertices(g, w, m.vertices, m.n_vertices, st);
+        if (e == hipSuccess) e = sdfv::launch_mesh_triangles(g, w, m.indices, st);
+    } else if (m.n_vertices) {
+        const size_t records = (size_t)n[0] * sizeof(sdfv_vertex);
+        e = hipMalloc(&hermite, records + m.n_vertices * 4);
+        if (e == hipSuccess) e = vertices(g, w, (sdfv_vertex*)hermite, n[0], st);
+        if (e == hipSuccess)
+            e = sdfv::launch_dc_vertices(g, w, (const sdfv_vertex*)hermite, (uint32_t*)((char*)hermite + records), m.vertices,
+                                         m.n_vertices, st);
+        if (e == hipSuccess) e = normals(m.vertices, m.n_vertices, st);
+        if (e == hipSuccess) e = sdfv::launch_dc_quads(g, w, m.indices, st);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(st);  // the next extraction on this thread reuses the scratch
+    if (hermite) (void)hipFree(hermite);
     if (e != hipSuccess) {
         (void)hipFree(m.vertices);
         (void)hipFree(m.indices);
@@ -1185,18 +1205,21 @@ int sdfv_mesh_extract(const sdfv_demo_params* params, uint32_t sdf_id, const flo
     memset(out, 0, sizeof(*out));
     if (int rc = check_params(params, sdf_id)) return rc;
     if (!bb_min || !bb_max) return fail(SDFV_ERR_INVALID_ARGUMENT, "bounding box is NULL");
-    if (algorithm != SDFV_MESHER_MARCHING_CUBES)
+    if (algorithm != SDFV_MESHER_MARCHING_CUBES && algorithm != SDFV_MESHER_DUAL_CONTOURING_PARTICLE)
         return fail(SDFV_ERR_INVALID_ARGUMENT, "Unsupported algorithm %u", algorithm);  // isosurface.rs:49
     if (max_voxels_per_axis < 1 || max_voxels_per_axis > 1024)
         return fail(SDFV_ERR_INVALID_ARGUMENT, "max_voxels_per_axis %u is outside [1, 1024]", max_voxels_per_axis);
     if (int rc = need_device()) return rc;
     return extract_mesh(
-        bb_min, bb_max, max_voxels_per_axis, out, (hipStream_t)stream,
+        bb_min, bb_max, max_voxels_per_axis, algorithm, out, (hipStream_t)stream,
         [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, hipStream_t st) {
             return sdfv::launch_mesh_lattice(*params, sdf_id, g, w, st);
         },
         [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, sdfv_vertex* vertices, size_t, hipStream_t st) {
             return sdfv::launch_mesh_vertices(*params, sdf_id, g, w, vertices, st);
+        },
+        [&](sdfv_vertex* vertices, size_t n, hipStream_t st) {
+            return sdfv::launch_mesh_vertex_normals(*params, sdf_id, vertices, n, st);
         });
 }
 
@@ -1691,7 +1714,7 @@ int sdfv_program_mesh_extract(const sdfv_program* p, const float bb_min[3], cons
     if (!p) return fail(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
     if ((bb_min == nullptr) != (bb_max == nullptr))
         return fail(SDFV_ERR_INVALID_ARGUMENT, "bounding box: bb_min and bb_max are both given or both NULL (the program's box)");
-    if (algorithm != SDFV_MESHER_MARCHING_CUBES)
+    if (algorithm != SDFV_MESHER_MARCHING_CUBES && algorithm != SDFV_MESHER_DUAL_CONTOURING_PARTICLE)
         return fail(SDFV_ERR_INVALID_ARGUMENT, "Unsupported algorithm %u", algorithm);  // isosurface.rs:49
     if (max_voxels_per_axis < 1 || max_voxels_per_axis > 1024)
         return fail(SDFV_ERR_INVALID_ARGUMENT, "max_voxels_per_axis %u is outside [1, 1024]", max_voxels_per_axis);
@@ -1701,13 +1724,18 @@ int sdfv_program_mesh_extract(const sdfv_program* p, const float bb_min[3], cons
     if (int rc = program_device_ops(p, &dev_ops)) return rc;
     const uint32_t n_ops = (uint32_t)p->ops.size();
     const bool materials = (flags & SDFV_MESH_WITH_MATERIALS) != 0;
+    // the Hermite records of dual contouring are an intermediate: the materials belong to the solved vertices
+    const bool edge_materials = materials && algorithm == SDFV_MESHER_MARCHING_CUBES;
     return extract_mesh(
-        bb_min ? bb_min : p->bb, bb_max ? bb_max : p->bb + 3, max_voxels_per_axis, out, (hipStream_t)stream,
+        bb_min ? bb_min : p->bb, bb_max ? bb_max : p->bb + 3, max_voxels_per_axis, algorithm, out, (hipStream_t)stream,
         [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, hipStream_t st) {
             return sdfv::launch_program_mesh_lattice(dev_ops, n_ops, g, w, st);
         },
         [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, sdfv_vertex* vertices, size_t n, hipStream_t st) {
-            return sdfv::launch_program_mesh_vertices(dev_ops, n_ops, g, w, vertices, n, materials, st);
+            return sdfv::launch_program_mesh_vertices(dev_ops, n_ops, g, w, vertices, n, edge_materials, st);
+        },
+        [&](sdfv_vertex* vertices, size_t n, hipStream_t st) {
+            return sdfv::launch_program_vertex_normals(dev_ops, n_ops, vertices, n, materials, st);
         });
 }
 

@@ -27,14 +27,15 @@ std::optional<Mesh> mesh_sdf(Meshers mesher, const SDFSurface& sdf, const Mesher
     const auto dev = sdf.device_sdf();
     const sdfv_program* program = dev ? nullptr : sdf.device_program();
     if (!dev && !program) return fail("this SDF has no device form: it cannot be meshed on the GPU");
-    if (mesher != Meshers::MarchingCubes) return fail("Unsupported algorithm");  // isosurface.rs:49
+    uint32_t algorithm = SDFV_MESHER_MARCHING_CUBES;
+    if (mesher == Meshers::DualContouringParticleBasedMinimization) algorithm = SDFV_MESHER_DUAL_CONTOURING_PARTICLE;
+    else if (mesher != Meshers::MarchingCubes) return fail("Unsupported algorithm");  // isosurface.rs:49
     const BoundingBox bb = sdf.bounding_box();
     const float lo[3] = {bb[0].x, bb[0].y, bb[0].z}, hi[3] = {bb[1].x, bb[1].y, bb[1].z};
     sdfv_mesh m{};
-    const int rc = dev ? sdfv_mesh_extract(&dev->params, dev->sdf_id, lo, hi, (uint32_t)cfg.max_voxels_per_axis,
-                                           SDFV_MESHER_MARCHING_CUBES, &m, nullptr)
-                       : sdfv_program_mesh_extract(program, lo, hi, (uint32_t)cfg.max_voxels_per_axis,
-                                                   SDFV_MESHER_MARCHING_CUBES, 0, &m, nullptr);
+    const int rc = dev ? sdfv_mesh_extract(&dev->params, dev->sdf_id, lo, hi, (uint32_t)cfg.max_voxels_per_axis, algorithm, &m,
+                                           nullptr)
+                       : sdfv_program_mesh_extract(program, lo, hi, (uint32_t)cfg.max_voxels_per_axis, algorithm, 0, &m, nullptr);
     if (rc != SDFV_OK) return fail(sdfv_last_error());
     Mesh out;
     out.vertices.resize(m.n_vertices);

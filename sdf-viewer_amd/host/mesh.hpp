@@ -44,8 +44,8 @@ struct Mesh {
     size_t serialize_ply(std::ostream& out, const std::string& version_info) const;
 };
 
-// Mesher::mesh (meshers/mod.rs:136-149).  Only MarchingCubes has a device implementation; the others report
-// "Unsupported algorithm" (isosurface.rs:49).  nullopt on error, text in *err.
+// Mesher::mesh (meshers/mod.rs:136-149).  MarchingCubes and DualContouringParticleBasedMinimization have a device
+// implementation; the other two report "Unsupported algorithm" (isosurface.rs:49).  nullopt on error, text in *err.
 std::optional<Mesh> mesh_sdf(Meshers mesher, const SDFSurface& sdf, const MesherConfig& cfg, std::string* err);
 
 // f32 Display as Rust prints it (shortest digits that round-trip, never an exponent): what ply-rs writes for floats.

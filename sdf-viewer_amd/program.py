@@ -163,14 +163,15 @@ class CompiledProgram:
         check(lib.sdfv_program_sample_points_host(self.h, pts.ctypes.data, pts.shape[0], int(bool(distance_only)), out.ctypes.data))
         return out
 
-    def mesh(self, n, bb=None, materials=False, stream=None):
-        """sdfv_program_mesh_extract: marching cubes over n^3 cells of `bb` (min.xyz + max.xyz; None: the program's box) ->
-        (vertices [V, 12] float32, indices [3 * triangles] int32), copied out of the library's buffers.  materials=True: the
-        vertices leave as mesh_postproc would make them (SDFV_MESH_WITH_MATERIALS)."""
+    def mesh(self, n, bb=None, materials=False, stream=None, algorithm=0):
+        """sdfv_program_mesh_extract: marching cubes (algorithm 0) or dual contouring (_capi.MESHER_DUAL_CONTOURING_PARTICLE) over
+        n^3 cells of `bb` (min.xyz + max.xyz; None: the program's box) -> (vertices [V, 12] float32, indices [3 * triangles]
+        int32), copied out of the library's buffers.  materials=True: the vertices leave as mesh_postproc would make them
+        (SDFV_MESH_WITH_MATERIALS)."""
         from . import _stream_ptr, f3, mesh_tensors
         m = _capi.Mesh()
         lo, hi = (None, None) if bb is None else (f3(bb[:3]), f3(bb[3:]))
-        check(lib.sdfv_program_mesh_extract(self.h, lo, hi, int(n), 0, _capi.MESH_WITH_MATERIALS if materials else 0, C.byref(m),
+        check(lib.sdfv_program_mesh_extract(self.h, lo, hi, int(n), int(algorithm), _capi.MESH_WITH_MATERIALS if materials else 0, C.byref(m),
                                             _stream_ptr(stream)))
         return mesh_tensors(m)
 

@@ -1,0 +1,151 @@
+"""What dual contouring costs next to marching cubes, phase by phase (profiles/dual_contour.json is this tool's output).
+
+    rocprofv3 --kernel-trace --stats --output-format csv -d TRACE -- python tools/dual_contour_bench.py --rounds 12 --timing TRACE/timing.json
+    python tools/dual_contour_bench.py --from-trace TRACE --timing TRACE/timing.json > profiles/dual_contour.json
+
+Algorithm 4 (SDFV_MESHER_DUAL_CONTOURING_PARTICLE) and algorithm 0 (marching cubes) at 128 and 256 cells of
+  demo      the demo tree through sdfv_mesh_extract,
+  demo3     CUBE 0.95, SPHERE 1.05, SUBTRACT: the demo's distance as a program,
+  spheres8  eight blended spheres (39 instructions; tools/program_mesh_bench.py's),
+the programs through sdfv_program_mesh_extract with SDFV_MESH_WITH_MATERIALS, alternated (model, algorithm) by (model, algorithm)
+in ONE process after a warm-up.  An extraction synchronises in the middle, so the per-phase times are the DEVICE timestamps of
+the kernels in a rocprofv3 kernel trace of that same process (a run of its own), grouped by kernel name --
+  lattice    lattice_kernel / sdfprog_mesh_lattice
+  count      edge_mask_kernel, cell_count_kernel, dc_cell_count, dc_edge_count, the rocPRIM scan kernels, totals_kernel, dc_totals
+  hermite    the marching-cubes vertex kernels: the OUTPUT of algorithm 0, the Hermite records of algorithm 4
+             (emit_vertices_kernel / sdfprog_mesh_positions + sdfprog_mesh_vertices[_mat]; for algorithm 4 the first of the two
+             sdfprog_mesh_vertices dispatches of an extraction)
+  solve      dc_cell_list + dc_solve
+  normals    dc_demo_normals / the second sdfprog_mesh_vertices[_mat] dispatch: the normals (materials) at the solved vertices
+  triangles  emit_triangles_kernel / dc_quads
+-- median over the rounds, per (model, algorithm, cells); extractions are told apart by the order of the process's dispatches,
+which this run records.  Read as a ratio, none of them a threshold: (solve + quads) of algorithm 4 against the triangle phase of
+algorithm 0 in the same process, and solve against the lattice phase.  Stamped with sdfv_build_id()."""
+import argparse
+import csv
+import glob
+import importlib
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from program_mesh_bench import spheres8  # noqa: E402
+
+PHASES = (("lattice", ("lattice_kernel", "sdfprog_mesh_lattice")),
+          ("count", ("edge_mask_kernel", "cell_count_kernel", "totals_kernel", "dc_cell_count", "dc_edge_count", "dc_totals",
+                     "rocprim", "scan")),
+          ("solve", ("dc_cell_list", "dc_solve")),
+          ("normals", ("dc_demo_normals",)),
+          ("hermite", ("emit_vertices_kernel", "sdfprog_mesh_positions", "sdfprog_mesh_vertices")),
+          ("triangles", ("emit_triangles_kernel", "dc_quads")))
+DUAL = 4
+
+
+def phase_of(kernel):
+    for phase, keys in PHASES:
+        if any(k in kernel for k in keys):
+            return phase
+    return None
+
+
+def run(args):
+    import torch
+    pkg = importlib.import_module("sdf-viewer_amd")
+    PM = importlib.import_module("sdf-viewer_amd.program")
+    prm = pkg.default_params()
+    builders = {"demo3": PM.Program().cube(0.95).sphere(1.05).subtract(), "spheres8": spheres8(PM)}
+    progs = {k: b.build() for k, b in builders.items()}
+    variants = {}
+    for alg in (DUAL, 0):
+        variants[f"demo/{alg}"] = (lambda n, alg=alg: pkg.mesh_extract(prm, n, algorithm=alg))
+        for k, p in progs.items():
+            variants[f"{k}/{alg}"] = (lambda n, p=p, alg=alg: p.mesh(n, materials=True, algorithm=alg))
+    seq, calls = [], {}
+    for n in [int(c) for c in args.cells.split(",")]:
+        for _ in range(args.warmup):
+            for k, fn in variants.items():
+                fn(n)
+                seq.append([k, n, "warmup"])
+        for _ in range(args.rounds):
+            for k, fn in variants.items():                 # alternated: every variant sees the same drift
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                v, i = fn(n)
+                e1.record()
+                e1.synchronize()
+                calls.setdefault(f"{k}@{n}", {"ms": [], "vertices": int(v.shape[0]), "triangles": int(i.shape[0]) // 3})["ms"].append(
+                    e0.elapsed_time(e1))
+                seq.append([k, n, "timed"])
+    out = {"build_id": pkg.lib.sdfv_build_id().decode(), "device": torch.cuda.get_device_name(0), "rounds": args.rounds,
+           "warmup": args.warmup, "ops": {k: len(b.ops) for k, b in builders.items()}, "sequence": seq,
+           "calls": {k: {"ms_median": statistics.median(c["ms"]), "ms_min": min(c["ms"]), "vertices": c["vertices"],
+                         "triangles": c["triangles"]} for k, c in calls.items()}}
+    os.makedirs(os.path.dirname(os.path.abspath(args.timing)), exist_ok=True)
+    json.dump(out, open(args.timing, "w"))
+    print("wrote", args.timing)
+
+
+def from_trace(args):
+    timing = json.load(open(args.timing))
+    rows = []
+    for f in glob.glob(os.path.join(args.from_trace, "**", "*kernel_trace.csv"), recursive=True):
+        rows += [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(f))]
+    rows.sort()
+    # an extraction = one lattice dispatch and what follows it up to the next one's; they come in the recorded sequence
+    groups = []
+    for start, end, name in rows:
+        phase = phase_of(name)
+        if phase == "lattice":
+            groups.append({"solved": False})
+        if not phase or not groups:
+            continue
+        g = groups[-1]
+        if phase == "solve":
+            g["solved"] = True
+        elif phase == "hermite" and g["solved"]:
+            phase = "normals"                  # a program's vertex kernel again, this time over the solved vertices
+        g[phase] = g.get(phase, 0) + (end - start)
+    mesh_seq = timing["sequence"]
+    assert len(groups) == len(mesh_seq), (len(groups), len(mesh_seq))
+    acc = {}
+    for (variant, n, kind), g in zip(mesh_seq, groups):
+        assert g["solved"] == variant.endswith(f"/{DUAL}"), (variant, n, g)
+        if kind == "timed":
+            acc.setdefault(f"{variant}@{n}", []).append(g)
+    phases = {}
+    for key, gs in acc.items():
+        phases[key] = {p: round(statistics.median([g.get(p, 0) for g in gs]) / 1e3, 2) for p, _ in PHASES}   # microseconds
+        phases[key]["sum_us"] = round(sum(phases[key].values()), 2)
+    ratios = {}
+    for key, ph in phases.items():
+        variant, n = key.split("@")
+        model, alg = variant.split("/")
+        if int(alg) != DUAL:
+            continue
+        mc = phases[f"{model}/0@{n}"]
+        ratios[f"{model}@{n}"] = {
+            "solve_plus_quads_over_mc_triangles": round((ph["solve"] + ph["triangles"]) / mc["triangles"], 3),
+            "solve_over_lattice": round(ph["solve"] / ph["lattice"], 3),
+            "dual_sum_over_mc_sum": round(ph["sum_us"] / mc["sum_us"], 3)}
+    out = {k: timing[k] for k in ("build_id", "device", "rounds", "warmup", "ops", "calls")}
+    out["phases_us_median"] = phases
+    out["ratios"] = ratios
+    out["method"] = ("phases: kernel durations (device timestamps) of a rocprofv3 --kernel-trace --stats run of the timed process; "
+                     "calls: device events around whole extractions in that run")
+    print(json.dumps(out, indent=1))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=12)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--cells", default="128,256")
+    ap.add_argument("--timing", default="dual_contour_timing.json")
+    ap.add_argument("--from-trace", default="")
+    a = ap.parse_args()
+    from_trace(a) if a.from_trace else run(a)
