@@ -8,7 +8,7 @@
 //  * dc_cell_count / dc_edge_count: one cell / one lattice point per thread, a 0/1 and a 0..3 for the two scans;
 //  * dc_cell_list: one cell per thread, the active ones write their id to their scanned slot -- the compacted list;
 //  * dc_solve: one thread per ENTRY of that list, dense waves.  The <= 12 Hermite records are gathered twice through
-//    point_first + popc(mask & ...) (once for the mass point, once for the normal equations: the second pass hits the cache) and
+//    edge_record of mesh_lattice.h (once for the mass point, once for the normal equations: the second pass hits the cache) and
 //    accumulated as they arrive -- nine sums, no per-thread array; then 24 steps on nine floats of state;
 //  * dc_quads: one lattice point per thread, those with an interior crossing edge look up four vertex ids in the cell scan.
 // The kernels carry C names: tests and profiles find them under the same symbol whatever the toolchain mangles.
@@ -39,13 +39,6 @@ __device__ __forceinline__ uint32_t interior_edges(const MeshGrid& g, uint32_t m
     return m & ((y && z ? 1u : 0u) | (x && z ? 2u : 0u) | (x && y ? 4u : 0u));
 }
 
-__device__ __forceinline__ void cell_of(const MeshGrid& g, uint32_t c, uint32_t& i, uint32_t& j, uint32_t& k) {
-    const uint32_t r = c / g.cells[0];  // 32-bit divisions: a handful of instructions, unlike 64-bit ones
-    i = c - r * g.cells[0];
-    k = r / g.cells[1];
-    j = r - k * g.cells[1];
-}
-
 __device__ __forceinline__ float min_f(float a, float b) { return b < a ? b : a; }  // the program table's min and max
 __device__ __forceinline__ float max_f(float a, float b) { return a < b ? b : a; }
 
@@ -53,15 +46,9 @@ __device__ __forceinline__ float max_f(float a, float b) { return a < b ? b : a;
 template <typename F>
 __device__ __forceinline__ void for_each_record(const Lattice& L, uint32_t edges, size_t origin, const uint8_t* __restrict__ mask,
                                                 const uint32_t* __restrict__ point_first, F&& f) {
-    const size_t stride[3] = {1, L.nx, (size_t)L.nx * L.ny};
 #pragma unroll
-    for (int e = 0; e < 12; ++e) {
-        if (!(edges >> e & 1u)) continue;
-        const int a = e >> 2, s = e & 3;
-        const int o0 = a == 0 ? 1 : 0, o1 = a == 2 ? 1 : 2;  // the two other axes, increasing
-        const size_t owner = origin + (s & 1) * stride[o0] + (s >> 1) * stride[o1];
-        f(point_first[owner] + __popc((uint32_t)mask[owner] & ((1u << a) - 1u)));
-    }
+    for (int e = 0; e < 12; ++e)
+        if (edges >> e & 1u) f(edge_record(L, origin, e, mask, point_first));
 }
 
 }  // namespace
@@ -71,11 +58,10 @@ extern "C" {
 __global__ __launch_bounds__(kBlock) void dc_cell_count(MeshGrid g, const uint8_t* __restrict__ mask,
                                                         uint32_t* __restrict__ count) {
     const Lattice L(g);
-    const uint32_t n = g.cells[0] * g.cells[1] * g.cells[2];
     const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
-    if (c >= n) return;
+    if (c >= L.cells()) return;
     uint32_t i, j, k;
-    cell_of(g, c, i, j, k);
+    L.uncell(c, i, j, k);
     count[c] = cell_edges(L, mask, L.flat(i, j, k)) != 0u ? 1u : 0u;
 }
 
@@ -95,9 +81,7 @@ __global__ void dc_totals(MeshGrid g, const uint8_t* mask, const uint32_t* point
     const Lattice L(g);
     const uint32_t last = L.points() - 1;
     totals[0] = point_first[last] + __popc((uint32_t)mask[last]);
-    const uint32_t i = g.cells[0] - 1, j = g.cells[1] - 1, k = g.cells[2] - 1;
-    const uint32_t n_cells = g.cells[0] * g.cells[1] * g.cells[2];
-    totals[1] = cell_first[n_cells - 1] + (cell_edges(L, mask, L.flat(i, j, k)) != 0u ? 1u : 0u);
+    totals[1] = cell_first[L.cells() - 1] + (cell_edges(L, mask, L.flat(L.cx - 1, L.cy - 1, L.cz - 1)) != 0u ? 1u : 0u);
     totals[2] = quad_first[last] + __popc(interior_edges(g, mask[last], L.nx - 1, L.ny - 1, L.nz - 1));
 }
 
@@ -105,11 +89,10 @@ __global__ void dc_totals(MeshGrid g, const uint8_t* mask, const uint32_t* point
 __global__ __launch_bounds__(kBlock) void dc_cell_list(MeshGrid g, const uint8_t* __restrict__ mask,
                                                        const uint32_t* __restrict__ cell_first, uint32_t* __restrict__ list) {
     const Lattice L(g);
-    const uint32_t n = g.cells[0] * g.cells[1] * g.cells[2];
     const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
-    if (c >= n) return;
+    if (c >= L.cells()) return;
     uint32_t i, j, k;
-    cell_of(g, c, i, j, k);
+    L.uncell(c, i, j, k);
     if (cell_edges(L, mask, L.flat(i, j, k)) != 0u) list[cell_first[c]] = c;
 }
 
@@ -122,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void dc_solve(MeshGrid g, const float4* __r
     const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= n) return;
     uint32_t i, j, k;
-    cell_of(g, list[t], i, j, k);
+    L.uncell(list[t], i, j, k);
     const size_t origin = L.flat(i, j, k);
     const uint32_t edges = cell_edges(L, mask, origin);
     // mass point
@@ -181,8 +164,8 @@ __global__ __launch_bounds__(kBlock) void dc_quads(MeshGrid g, const float* __re
     const uint32_t m = interior_edges(g, mask[v], idx[0], idx[1], idx[2]);
     if (m == 0) return;
     const bool outside0 = dist[v] >= 0.0f;
-    const uint32_t cell_stride[3] = {1, g.cells[0], g.cells[0] * g.cells[1]};
-    const uint32_t here = (idx[2] * g.cells[1] + idx[1]) * g.cells[0] + idx[0];  // the cell whose lowest corner is this point
+    const uint32_t cell_stride[3] = {1, L.cx, L.cx * L.cy};
+    const uint32_t here = (idx[2] * L.cy + idx[1]) * L.cx + idx[0];  // the cell whose lowest corner is this point
     uint2* out = reinterpret_cast<uint2*>(indices) + (size_t)quad_first[v] * 3;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -203,8 +186,7 @@ __global__ __launch_bounds__(kBlock) void dc_quads(MeshGrid g, const float* __re
 hipError_t launch_dc_count(const MeshGrid& g, const MeshWork& w, uint32_t* totals_dev, hipStream_t stream) {
     if (!w.quad_first) return hipErrorInvalidValue;
     if (hipError_t e = launch_mesh_edge_masks(g, w, stream); e != hipSuccess) return e;  // also checks the grid
-    const size_t n_points = (size_t)(g.cells[0] + 1) * (g.cells[1] + 1) * (g.cells[2] + 1);
-    const size_t n_cells = (size_t)g.cells[0] * g.cells[1] * g.cells[2];
+    const size_t n_points = g.n_points(), n_cells = g.n_cells();
     hipLaunchKernelGGL(dc_cell_count, dim3(blocks_for(n_cells)), dim3(kBlock), 0, stream, g, w.point_mask, w.cell_first);
     if (hipError_t e = mesh_exclusive_scan(w, w.cell_first, n_cells, stream); e != hipSuccess) return e;
     hipLaunchKernelGGL(dc_edge_count, dim3(blocks_for(n_points)), dim3(kBlock), 0, stream, g, w.point_mask, w.quad_first);
@@ -218,17 +200,15 @@ hipError_t launch_dc_vertices(const MeshGrid& g, const MeshWork& w, const sdfv_v
                               sdfv_vertex* vertices, size_t n_vertices, hipStream_t stream) {
     if (n_vertices == 0) return hipSuccess;
     if (!hermite || !cell_list || !vertices || n_vertices > 0xffffffffull || ((uintptr_t)hermite & 15)) return hipErrorInvalidValue;
-    const size_t n_cells = (size_t)g.cells[0] * g.cells[1] * g.cells[2];
-    hipLaunchKernelGGL(dc_cell_list, dim3(blocks_for(n_cells)), dim3(kBlock), 0, stream, g, w.point_mask, w.cell_first, cell_list);
+    hipLaunchKernelGGL(dc_cell_list, dim3(blocks_for(g.n_cells())), dim3(kBlock), 0, stream, g, w.point_mask, w.cell_first, cell_list);
     hipLaunchKernelGGL(dc_solve, dim3(blocks_for(n_vertices)), dim3(kBlock), 0, stream, g, reinterpret_cast<const float4*>(hermite),
                        w.point_mask, w.point_first, cell_list, (uint32_t)n_vertices, reinterpret_cast<float*>(vertices));
     return hipGetLastError();
 }
 
 hipError_t launch_dc_quads(const MeshGrid& g, const MeshWork& w, uint32_t* indices, hipStream_t stream) {
-    const size_t n_points = (size_t)(g.cells[0] + 1) * (g.cells[1] + 1) * (g.cells[2] + 1);
     if (indices)
-        hipLaunchKernelGGL(dc_quads, dim3(blocks_for(n_points)), dim3(kBlock), 0, stream, g, w.dist, w.point_mask, w.quad_first,
+        hipLaunchKernelGGL(dc_quads, dim3(blocks_for(g.n_points())), dim3(kBlock), 0, stream, g, w.dist, w.point_mask, w.quad_first,
                            w.cell_first, indices);
     return hipGetLastError();
 }

@@ -13,6 +13,12 @@ namespace sdfv {
 struct MeshGrid {
     uint32_t cells[3];     // cells per axis; lattice points = cells + 1
     float bb_min[3], bb_size[3];
+    // host side (the kernels have mesh_lattice.h's Lattice): the sizes every launcher and the scratch layout go by
+    size_t n_points() const { return (size_t)(cells[0] + 1) * (cells[1] + 1) * (cells[2] + 1); }
+    size_t n_cells() const { return (size_t)cells[0] * cells[1] * cells[2]; }
+    // what every launch of an extraction may assume, checked by its first launcher: cells on every axis, and lattice points a
+    // kernel can index with 32 bits (their workgroups then fit one launch)
+    bool launchable() const { return n_cells() != 0 && n_points() <= 0xffffffffull; }
 };
 
 struct MeshWork {           // device scratch of one extraction, sized by mesh_work_bytes()
@@ -27,26 +33,32 @@ struct MeshWork {           // device scratch of one extraction, sized by mesh_w
 };
 
 size_t mesh_scan_tmp_bytes(size_t n);
-// An extraction is five steps on one stream; the first and the fourth evaluate the SDF, the others do not and serve every kind
-// of SDF (the demo tree here, SDF programs in program_mesh_kernels.hip):
-// 1. lattice distances into w.dist (the demo tree's)
+// An extraction is six steps on one stream (five for the demo tree's marching cubes: see the end); the first and the fifth evaluate the SDF, the others do not and serve every kind of
+// SDF (the demo tree here, SDF programs in program_mesh_kernels.hip) and both meshers (dual_contour_kernels.h has algorithm 4's
+// own counting, solve and quads):
+// 1. lattice distances into w.dist (the demo tree's).  Checks the grid (MeshGrid::launchable).
 hipError_t launch_mesh_lattice(const sdfv_demo_params& prm, uint32_t sdf_id, const MeshGrid& g, const MeshWork& w,
                                hipStream_t stream);
 // 2. edge masks, triangle counts, both scans.  Leaves the totals in totals_dev[0] (vertices), [1] (triangles).
 hipError_t launch_mesh_count(const MeshGrid& g, const MeshWork& w, uint32_t* totals_dev, hipStream_t stream);
 //    Its two parts, for an extractor that counts something else per cell (dual_contour_kernels.hip): edge masks + the point scan
-//    (checks the grid, as launch_mesh_lattice does), and the in-place exclusive scan of n counts through w.scan_tmp.
+//    (checks the grid too), and the in-place exclusive scan of n counts through w.scan_tmp.
 hipError_t launch_mesh_edge_masks(const MeshGrid& g, const MeshWork& w, hipStream_t stream);
 hipError_t mesh_exclusive_scan(const MeshWork& w, uint32_t* counts, size_t n, hipStream_t stream);
 // 3. (the host reads the totals and allocates)
-// 4. vertices: position + HermiteSource normal of the demo tree, the rest zero
-hipError_t launch_mesh_vertices(const sdfv_demo_params& prm, uint32_t sdf_id, const MeshGrid& g, const MeshWork& w,
-                                sdfv_vertex* vertices, hipStream_t stream);
-// 5. triangle indices
-hipError_t launch_mesh_triangles(const MeshGrid& g, const MeshWork& w, uint32_t* indices, hipStream_t stream);
-// Dual contouring's last SDF step: normal = HermiteSource normal of the demo tree at the position of each of n vertices, the
-// rest of the record zero -- step 4's per-vertex part over a compacted list
+// 4. positions: vertices[id].position of the n vertices step 2 counted, one per crossing edge in lattice then axis order, on the
+//    edge by linear interpolation of its two distances.  Nothing else of a record is written.  The output vertices of marching
+//    cubes, the Hermite records of dual contouring.
+hipError_t launch_mesh_edge_positions(const MeshGrid& g, const MeshWork& w, sdfv_vertex* vertices, size_t n, hipStream_t stream);
+// 5. attributes: one thread per vertex of a list whose positions are written -- the rest of the record.  The demo tree's: the
+//    HermiteSource normal at the position, a zero material.  Dual contouring runs it over its Hermite records and again over its
+//    solved vertices.
 hipError_t launch_mesh_vertex_normals(const sdfv_demo_params& prm, uint32_t sdf_id, sdfv_vertex* vertices, size_t n,
                                       hipStream_t stream);
+// 4 + 5 in one kernel, for the demo tree's marching cubes alone: the same records, written under the sparse mask of step 4
+hipError_t launch_mesh_fused_vertices(const sdfv_demo_params& prm, uint32_t sdf_id, const MeshGrid& g, const MeshWork& w,
+                                      sdfv_vertex* vertices, size_t n, hipStream_t stream);
+// 6. triangle indices
+hipError_t launch_mesh_triangles(const MeshGrid& g, const MeshWork& w, uint32_t* indices, hipStream_t stream);
 
 }  // namespace sdfv

@@ -1,7 +1,8 @@
-// mesh_lattice.h -- the lattice arithmetic the mesh kernels share on the device (mesh_kernels.hip for the demo tree,
-// program_mesh_kernels.hip for SDF programs): where a lattice point lies and where the vertex of a crossing edge lies.  One
-// statement of each, so that the two extractors cannot drift apart: both translation units are built with
-// -ffp-contract=off, every step below is one rounded f32 operation.
+// mesh_lattice.h -- the lattice arithmetic the mesh kernels share on the device (mesh_kernels.hip: the demo tree and every SDF-free
+// step; program_mesh_kernels.hip: SDF programs; dual_contour_kernels.hip): which point or cell a thread has, where a lattice point
+// lies, where the vertex of a crossing edge lies and which vertex record it is.  One statement of each, so that the extractors
+// cannot drift apart: the translation units are built with -ffp-contract=off, every float step below is one rounded f32
+// operation, every division is a 32-bit one.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,8 +14,11 @@ namespace sdfv {
 
 struct Lattice {
     uint32_t nx, ny, nz;  // points per axis
-    __device__ __forceinline__ explicit Lattice(const MeshGrid& g) : nx(g.cells[0] + 1), ny(g.cells[1] + 1), nz(g.cells[2] + 1) {}
-    __device__ __forceinline__ uint32_t points() const { return nx * ny * nz; }  // < 2^32: the API caps cells per axis at 1024
+    uint32_t cx, cy, cz;  // cells per axis
+    __device__ __forceinline__ explicit Lattice(const MeshGrid& g)
+        : nx(g.cells[0] + 1), ny(g.cells[1] + 1), nz(g.cells[2] + 1), cx(g.cells[0]), cy(g.cells[1]), cz(g.cells[2]) {}
+    __device__ __forceinline__ uint32_t points() const { return nx * ny * nz; }  // < 2^32: MeshGrid::launchable()
+    __device__ __forceinline__ uint32_t cells() const { return cx * cy * cz; }
     __device__ __forceinline__ size_t flat(uint32_t i, uint32_t j, uint32_t k) const {
         return ((size_t)k * ny + j) * nx + i;
     }
@@ -25,7 +29,26 @@ struct Lattice {
         k = r / ny;
         j = r - k * ny;
     }
+    // the same for a cell: c -> the (i, j, k) of the cell, which are those of its lowest corner
+    __device__ __forceinline__ void uncell(uint32_t c, uint32_t& i, uint32_t& j, uint32_t& k) const {
+        const uint32_t r = c / cx;
+        i = c - r * cx;
+        k = r / cy;
+        j = r - k * cy;
+    }
 };
+
+// The vertex record of edge e of the cell whose lowest corner is lattice point `origin`, e = 4 * axis + u + 2 * v (the
+// marching-cubes table's numbering): the edge along `axis` that starts at the corner offset by u along the lower and v along the
+// higher of the two other axes.  That corner owns the edge; its records come in axis order from point_first[corner] on.
+__device__ __forceinline__ uint32_t edge_record(const Lattice& L, size_t origin, int e, const uint8_t* __restrict__ mask,
+                                                const uint32_t* __restrict__ point_first) {
+    const size_t stride[3] = {1, L.nx, (size_t)L.nx * L.ny};
+    const int a = e >> 2, s = e & 3;
+    const int o0 = a == 0 ? 1 : 0, o1 = a == 2 ? 1 : 2;  // the two other axes, increasing
+    const size_t owner = origin + (s & 1) * stride[o0] + (s >> 1) * stride[o1];
+    return point_first[owner] + __popc((uint32_t)mask[owner] & ((1u << a) - 1u));
+}
 
 __device__ __forceinline__ float unit_coord(uint32_t i, uint32_t cells) { return (float)i / (float)cells; }
 

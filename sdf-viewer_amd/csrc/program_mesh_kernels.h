@@ -1,5 +1,5 @@
 // program_mesh_kernels.h -- launch interface of the mesh pipeline's SDF-program kernels (see program_mesh_kernels.hip): the two
-// steps of an extraction that evaluate the SDF (mesh_kernels.h has the other three), the batched normal and Mesh::postproc.
+// steps of an extraction that evaluate the SDF (mesh_kernels.h has the others), the batched normal and Mesh::postproc.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,15 +11,12 @@
 namespace sdfv {
 
 // ops: the DEVICE copy of the validated program.
-// step 1 of an extraction: the program's distance at every lattice point into w.dist
+// step 1 of an extraction: the program's distance at every lattice point into w.dist.  Checks the grid (MeshGrid::launchable).
 hipError_t launch_program_mesh_lattice(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const MeshWork& w,
                                        hipStream_t stream);
-// step 4: the n_vertices vertices the scans of step 2 counted -- positions from the lattice, then one thread per vertex for the
-// normal (and, with `materials`, the material fields Mesh::postproc would write; zero otherwise)
-hipError_t launch_program_mesh_vertices(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const MeshWork& w,
-                                        sdfv_vertex* vertices, size_t n_vertices, bool materials, hipStream_t stream);
-// the per-vertex half of step 4 by itself, over n vertices whose positions are written (16-byte aligned): what dual contouring
-// runs over its solved vertices -- the same kernels
+// step 5: one thread per vertex of n_vertices whose positions are written (16-byte aligned) for the normal and, with `materials`,
+// the material fields Mesh::postproc would write (zero otherwise).  Marching cubes runs it over the vertices of step 4, dual
+// contouring over its Hermite records and again over its solved vertices -- the same kernels
 hipError_t launch_program_vertex_normals(const sdfv_prog_op* ops, uint32_t n_ops, sdfv_vertex* vertices, size_t n_vertices,
                                          bool materials, hipStream_t stream);
 // normal_default_impl of the program at n points: 12 bytes in, 12 bytes out

@@ -1,14 +1,13 @@
 // program_mesh_kernels.hip -- the mesh pipeline over SDF programs on gfx950 (include/sdfgrid.h, "SDF programs: meshing"): the two
-// steps of a marching-cubes extraction that evaluate the SDF, the batched normal and Mesh::postproc, with the interpreter of
-// program_eval.h as the evaluator.  The SDF-independent steps (edge masks, the two scans, the triangles) are mesh_kernels.hip's,
-// unchanged and shared with the demo tree.
+// steps of an extraction that evaluate the SDF, the batched normal and Mesh::postproc, with the interpreter of program_eval.h as
+// the evaluator.  The SDF-independent steps (edge masks, the two scans, the vertex positions, the triangles) are
+// mesh_kernels.hip's, shared with the demo tree.
 //
 // Shape.  The interpreter costs one whole program run per WAVE, however few of its lanes are live, so nothing here evaluates the
 // program under a sparse mask:
 //  * sdfprog_mesh_lattice: one lattice point per thread, x fastest, distance only (no resolve(), no material traffic);
-//  * sdfprog_mesh_positions: SDF-free.  One thread per lattice point, those with a crossing edge write the POSITION of their
-//    vertices (edge_position of mesh_lattice.h, the arithmetic of the demo's emit_vertices_kernel);
-//  * sdfprog_mesh_vertices[_mat]: one thread per VERTEX of the compacted list the scan produced -- dense waves.  Reads the
+//  * sdfprog_mesh_vertices[_mat]: one thread per VERTEX of the compacted list the scan produced, whose positions
+//    mesh_edge_positions (mesh_kernels.hip, SDF-free) or dual contouring's solve has written -- dense waves.  Reads the
 //    position, runs the four taps of normal_default_impl through ONE copy of the interpreter in a loop (tap_normal; _mat adds a
 //    fifth, full run at the position itself + resolve(): material_at), writes the 48-byte record as three 16-byte stores;
 //  * sdfprog_normal_points[_staged], sdfprog_mesh_postproc[_unaligned]: the same per-lane function over caller arrays.
@@ -76,7 +75,7 @@ __device__ __forceinline__ void mesh_vertices(const sdfv_prog_op* __restrict__ o
     const bool live = i < n;
     float4* v = vertices + (size_t)(live ? i : 0) * 3;
     float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (live) p = v[0];  // the position sdfprog_mesh_positions left (w: not yet written, not used)
+    if (live) p = v[0];  // the position (w: not yet written, not used)
     // the 48-byte record leaves as three 16-byte stores: {b, metallic, roughness, occlusion} as soon as it is known
     Mat m = zero_mat();  // without MAT: Vertex::default()'s zero material
     if (MAT) m = material_at(ops, n_ops, p.x, p.y, p.z, live);
@@ -110,28 +109,6 @@ __global__ __launch_bounds__(kBlock) void sdfprog_mesh_lattice(const sdfv_prog_o
     float px, py, pz;
     lattice_position(g, i, j, k, px, py, pz);
     dist[v] = prog::run(ops, n_ops, px, py, pz).d;
-}
-
-__global__ __launch_bounds__(kBlock) void sdfprog_mesh_positions(MeshGrid g, const float* __restrict__ dist,
-                                                                 const uint8_t* __restrict__ mask,
-                                                                 const uint32_t* __restrict__ first,
-                                                                 float* __restrict__ vertices) {
-    const Lattice L(g);
-    const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
-    if (v >= L.points()) return;
-    const uint32_t m = mask[v];
-    if (m == 0) return;
-    uint32_t idx[3];
-    L.unflat(v, idx[0], idx[1], idx[2]);
-    const size_t stride[3] = {1, L.nx, (size_t)L.nx * L.ny};
-    const float d0 = dist[v];
-    uint32_t id = first[v];
-    for (int a = 0; a < 3; ++a) {
-        if (!(m & (1u << a))) continue;
-        float* o = vertices + (size_t)id * 12;
-        edge_position(g, idx, a, d0, dist[v + stride[a]], o[0], o[1], o[2]);
-        ++id;
-    }
 }
 
 __global__ __launch_bounds__(kBlock) void sdfprog_mesh_vertices(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
@@ -224,21 +201,9 @@ __global__ __launch_bounds__(kBlock) void sdfprog_mesh_postproc_unaligned(const 
 
 hipError_t launch_program_mesh_lattice(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const MeshWork& w,
                                        hipStream_t stream) {
-    const size_t n_points = (size_t)(g.cells[0] + 1) * (g.cells[1] + 1) * (g.cells[2] + 1);
-    const size_t n_cells = (size_t)g.cells[0] * g.cells[1] * g.cells[2];
-    if (n_cells == 0 || n_points > 0xffffffffull) return hipErrorInvalidValue;  // the kernels index lattice points with 32 bits
-    hipLaunchKernelGGL(sdfprog_mesh_lattice, dim3(blocks_for(n_points)), dim3(kBlock), 0, stream, ops, n_ops, g, w.dist);
+    if (!g.launchable()) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sdfprog_mesh_lattice, dim3(blocks_for(g.n_points())), dim3(kBlock), 0, stream, ops, n_ops, g, w.dist);
     return hipGetLastError();
-}
-
-hipError_t launch_program_mesh_vertices(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const MeshWork& w,
-                                        sdfv_vertex* vertices, size_t n_vertices, bool materials, hipStream_t stream) {
-    if (!vertices || n_vertices == 0) return hipSuccess;
-    const size_t n_points = (size_t)(g.cells[0] + 1) * (g.cells[1] + 1) * (g.cells[2] + 1);
-    if (n_points > 0xffffffffull || n_vertices > 0xffffffffull || ((uintptr_t)vertices & 15)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sdfprog_mesh_positions, dim3(blocks_for(n_points)), dim3(kBlock), 0, stream, g, w.dist, w.point_mask,
-                       w.point_first, reinterpret_cast<float*>(vertices));
-    return launch_program_vertex_normals(ops, n_ops, vertices, n_vertices, materials, stream);
 }
 
 hipError_t launch_program_vertex_normals(const sdfv_prog_op* ops, uint32_t n_ops, sdfv_vertex* vertices, size_t n_vertices,

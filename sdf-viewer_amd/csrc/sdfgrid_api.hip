@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstddef>
+#include <type_traits>
 #include <cstdio>
 #include <cstring>
 
@@ -1111,15 +1112,17 @@ int sdfv_mesh_postproc(const sdfv_demo_params* params, uint32_t sdf_id, sdfv_ver
 
 namespace {
 
-// Meshers::mesh for any SDF the device can evaluate: the arguments are checked by the caller, `lattice(g, w, stream)` writes the
-// distances of the lattice points, `vertices(g, w, vertices, n, stream)` the marching-cubes vertices of the crossing edges and
-// `normals(vertices, n, stream)` everything but the position of n vertices whose positions are written; counting, the scans, the
-// triangles (mesh_kernels.h) and dual contouring's solve and quads (dual_contour_kernels.h) do not depend on the SDF.  Marching
-// cubes never calls `normals`; dual contouring calls `vertices` for its Hermite records, into a temporary.  The scratch is the
-// calling thread's one block.
-template <typename LatticeFn, typename VerticesFn, typename NormalsFn>
+// Meshers::mesh for any SDF the device can evaluate: the arguments are checked by the caller.  An SDF kind supplies two things:
+// `lattice(g, w, stream)` writes the distances of the lattice points, and `attributes(vertices, n, final, stream)` everything but
+// the position of n vertices whose positions are written.  Counting, the scans, the positions of the crossing edges, the
+// triangles (mesh_kernels.h) and dual contouring's solve and quads (dual_contour_kernels.h) do not depend on the SDF.  `final` is
+// false only for dual contouring's Hermite records: crossing-edge vertices in a temporary, of which the solve reads position and
+// normal and nothing else.  The scratch is the calling thread's one block.
+// An SDF kind whose attributes are cheap enough to write under the positions' sparse mask may also give
+// `fused(g, w, vertices, n, stream)`: marching cubes then calls it in the place of positions + attributes (the demo tree does).
+template <typename LatticeFn, typename AttributesFn, typename FusedFn = std::nullptr_t>
 int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis, uint32_t algorithm, sdfv_mesh* out,
-                 hipStream_t st, LatticeFn&& lattice, VerticesFn&& vertices, NormalsFn&& normals) {
+                 hipStream_t st, LatticeFn&& lattice, AttributesFn&& attributes, FusedFn&& fused = nullptr) {
     const bool dual = algorithm == SDFV_MESHER_DUAL_CONTOURING_PARTICLE;
     sdfv::MeshGrid g;
     for (int i = 0; i < 3; ++i) {
@@ -1127,8 +1130,7 @@ int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxe
         g.bb_min[i] = bb_min[i];
         g.bb_size[i] = bb_max[i] - bb_min[i];
     }
-    const size_t n_points = (size_t)(g.cells[0] + 1) * (g.cells[1] + 1) * (g.cells[2] + 1);
-    const size_t n_cells = (size_t)g.cells[0] * g.cells[1] * g.cells[2];
+    const size_t n_points = g.n_points(), n_cells = g.n_cells();
     // One scratch block per host thread, grown on demand and kept between calls (allocating ~13 B per lattice point
     // afresh costs more than the extraction itself); sdfv_mesh_trim() gives it back.
     sdfv::MeshWork w{};
@@ -1172,16 +1174,22 @@ int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxe
     hipError_t e = hipSuccess;
     void* hermite = nullptr;  // dual contouring: n[0] Hermite records, then the list of the n[1] active cells
     if (!dual) {
-        e = vertices(g, w, m.vertices, m.n_vertices, st);
+        if constexpr (std::is_same_v<std::decay_t<FusedFn>, std::nullptr_t>) {
+            e = sdfv::launch_mesh_edge_positions(g, w, m.vertices, m.n_vertices, st);
+            if (e == hipSuccess) e = attributes(m.vertices, m.n_vertices, true, st);
+        } else {
+            e = fused(g, w, m.vertices, m.n_vertices, st);
+        }
         if (e == hipSuccess) e = sdfv::launch_mesh_triangles(g, w, m.indices, st);
     } else if (m.n_vertices) {
         const size_t records = (size_t)n[0] * sizeof(sdfv_vertex);
         e = hipMalloc(&hermite, records + m.n_vertices * 4);
-        if (e == hipSuccess) e = vertices(g, w, (sdfv_vertex*)hermite, n[0], st);
+        if (e == hipSuccess) e = sdfv::launch_mesh_edge_positions(g, w, (sdfv_vertex*)hermite, n[0], st);
+        if (e == hipSuccess) e = attributes((sdfv_vertex*)hermite, n[0], false, st);
         if (e == hipSuccess)
             e = sdfv::launch_dc_vertices(g, w, (const sdfv_vertex*)hermite, (uint32_t*)((char*)hermite + records), m.vertices,
                                          m.n_vertices, st);
-        if (e == hipSuccess) e = normals(m.vertices, m.n_vertices, st);
+        if (e == hipSuccess) e = attributes(m.vertices, m.n_vertices, true, st);
         if (e == hipSuccess) e = sdfv::launch_dc_quads(g, w, m.indices, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);  // the next extraction on this thread reuses the scratch
@@ -1215,11 +1223,11 @@ int sdfv_mesh_extract(const sdfv_demo_params* params, uint32_t sdf_id, const flo
         [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, hipStream_t st) {
             return sdfv::launch_mesh_lattice(*params, sdf_id, g, w, st);
         },
-        [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, sdfv_vertex* vertices, size_t, hipStream_t st) {
-            return sdfv::launch_mesh_vertices(*params, sdf_id, g, w, vertices, st);
-        },
-        [&](sdfv_vertex* vertices, size_t n, hipStream_t st) {
+        [&](sdfv_vertex* vertices, size_t n, bool, hipStream_t st) {
             return sdfv::launch_mesh_vertex_normals(*params, sdf_id, vertices, n, st);
+        },
+        [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, sdfv_vertex* vertices, size_t n, hipStream_t st) {
+            return sdfv::launch_mesh_fused_vertices(*params, sdf_id, g, w, vertices, n, st);
         });
 }
 
@@ -1724,18 +1732,13 @@ int sdfv_program_mesh_extract(const sdfv_program* p, const float bb_min[3], cons
     if (int rc = program_device_ops(p, &dev_ops)) return rc;
     const uint32_t n_ops = (uint32_t)p->ops.size();
     const bool materials = (flags & SDFV_MESH_WITH_MATERIALS) != 0;
-    // the Hermite records of dual contouring are an intermediate: the materials belong to the solved vertices
-    const bool edge_materials = materials && algorithm == SDFV_MESHER_MARCHING_CUBES;
     return extract_mesh(
         bb_min ? bb_min : p->bb, bb_max ? bb_max : p->bb + 3, max_voxels_per_axis, algorithm, out, (hipStream_t)stream,
         [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, hipStream_t st) {
             return sdfv::launch_program_mesh_lattice(dev_ops, n_ops, g, w, st);
         },
-        [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, sdfv_vertex* vertices, size_t n, hipStream_t st) {
-            return sdfv::launch_program_mesh_vertices(dev_ops, n_ops, g, w, vertices, n, edge_materials, st);
-        },
-        [&](sdfv_vertex* vertices, size_t n, hipStream_t st) {
-            return sdfv::launch_program_vertex_normals(dev_ops, n_ops, vertices, n, materials, st);
+        [&](sdfv_vertex* vertices, size_t n, bool final, hipStream_t st) {  // the materials belong to the output vertices only
+            return sdfv::launch_program_vertex_normals(dev_ops, n_ops, vertices, n, materials && final, st);
         });
 }
 

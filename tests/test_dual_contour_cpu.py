@@ -159,7 +159,8 @@ def test_the_restated_demo_is_closed(oracle):
 
 
 # ---- the built kernels (tests/kernel_objects.py) ----
-NEW_KERNELS = ("dc_cell_count", "dc_edge_count", "dc_totals", "dc_cell_list", "dc_solve", "dc_quads", "dc_demo_normals")
+DC_KERNELS = ("dc_cell_count", "dc_edge_count", "dc_totals", "dc_cell_list", "dc_solve", "dc_quads")
+NEW_KERNELS = DC_KERNELS + ("mesh_demo_normals",)        # the demo's per-vertex kernel (mesh_kernels.hip)
 
 
 def interpreter_loops(table, name):
@@ -186,7 +187,7 @@ def test_dual_contour_kernels_keep_the_resource_ceilings(code_objects):
     do and that dual contouring runs over its solved vertices (sdfprog_mesh_vertices[_mat]) keep theirs free of vector-memory
     and LDS operations."""
     table = kernel_table(code_objects)
-    assert sorted(n for n in table if n.startswith("dc_")) == sorted(NEW_KERNELS)
+    assert sorted(n for n in table if n.startswith("dc_")) == sorted(DC_KERNELS)
     for name in NEW_KERNELS:
         k = table[name]
         print(name, {a: b for a, b in k.items() if a != "co"})

@@ -168,6 +168,24 @@ def test_scratch_is_reused_and_can_be_trimmed(pkg):
     assert torch.equal(a[0], d[0]) and torch.equal(a[1], d[1])
 
 
+def test_marching_cubes_is_the_same_before_and_after_dual_contouring(pkg):
+    """The cube child at 9 cells in the non-cubic box of test_extraction_matches_numpy_restatement, algorithm 0, then 4, then 0 on
+    one thread: the two meshers share the thread's scratch and the positions kernel, which writes into the output vertices for
+    one and into a temporary for the other.  Guards the state shared between calls; tests/test_gpu_dual_contour.py checks what
+    algorithm 4 itself returns."""
+    prm = pkg.default_params(cube_half_side=0.6)
+    box = ((-1.0, -0.75, -1.25), (1.0, 1.0, 0.5))
+
+    def extract(algorithm):
+        return [x.cpu().numpy() for x in pkg.mesh_extract(prm, 9, *box, sdf_id=1, algorithm=algorithm)]
+    before = extract(0)
+    dual = extract(4)
+    after = extract(0)
+    assert before[0].shape[0] > 0 and before[1].shape[0] > 0 and dual[0].shape[0] > 0 and dual[1].shape[0] > 0
+    for a, b in zip(before, after):
+        assert a.shape == b.shape and (a.view(np.uint32) == b.view(np.uint32)).all()
+
+
 def test_randomised_extractions_match_numpy_restatement(pkg, oracle, table):
     """Seeded sweep (tools/soak.sh varies the seed): random demo parameters, sub-trees, boxes and lattice sizes."""
     rng = np.random.default_rng(int(os.environ.get("SDFV_SOAK_SEED", 11)))

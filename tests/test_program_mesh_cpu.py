@@ -69,15 +69,19 @@ def test_argument_errors_come_first_and_without_a_device_nothing_is_written(pkg,
 # ---- the built kernels (tests/kernel_objects.py) ----
 INTERPRETING = ("sdfprog_mesh_lattice", "sdfprog_mesh_vertices", "sdfprog_mesh_vertices_mat", "sdfprog_mesh_postproc",
                 "sdfprog_mesh_postproc_unaligned", "sdfprog_normal_points", "sdfprog_normal_points_staged")
+POSITIONS = "mesh_edge_positions"                         # SDF-free and shared with the demo tree (mesh_kernels.hip)
 
 
 def test_mesh_kernels_keep_the_resource_ceilings(code_objects):
-    """DESIGN.md 3.7's ceilings for every sdfprog_mesh_* / sdfprog_normal_points* kernel, read from the built library: at most
+    """DESIGN.md 3.7's ceilings for every sdfprog_mesh_* / sdfprog_normal_points* kernel and the positions kernel that runs
+    between them, read from the built library: at most
     80 VGPRs (6 waves per SIMD), no scratch, no spill, at most 256 bytes of kernel arguments, and no vector memory operation
     inside an interpreter loop (the instruction fetch is scalar)."""
     table = kernel_table(code_objects)
     names = sorted(n for n in table if n.startswith(("sdfprog_mesh_", "sdfprog_normal_points")))
-    assert set(names) == set(INTERPRETING) | {"sdfprog_mesh_positions"}, names
+    assert set(names) == set(INTERPRETING), names
+    assert POSITIONS in table
+    names.append(POSITIONS)
     for name in names:
         k = table[name]
         assert k["vgpr"] <= 80, (name, k)

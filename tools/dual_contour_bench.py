@@ -13,10 +13,10 @@ the kernels in a rocprofv3 kernel trace of that same process (a run of its own),
   lattice    lattice_kernel / sdfprog_mesh_lattice
   count      edge_mask_kernel, cell_count_kernel, dc_cell_count, dc_edge_count, the rocPRIM scan kernels, totals_kernel, dc_totals
   hermite    the marching-cubes vertex kernels: the OUTPUT of algorithm 0, the Hermite records of algorithm 4
-             (emit_vertices_kernel / sdfprog_mesh_positions + sdfprog_mesh_vertices[_mat]; for algorithm 4 the first of the two
-             sdfprog_mesh_vertices dispatches of an extraction)
+             (the demo's marching cubes: emit_vertices_kernel; everything else: mesh_edge_positions + mesh_demo_normals /
+             sdfprog_mesh_vertices[_mat]; for algorithm 4 the first of the two per-vertex dispatches of an extraction)
   solve      dc_cell_list + dc_solve
-  normals    dc_demo_normals / the second sdfprog_mesh_vertices[_mat] dispatch: the normals (materials) at the solved vertices
+  normals    the second mesh_demo_normals / sdfprog_mesh_vertices[_mat] dispatch: the normals (materials) at the solved vertices
   triangles  emit_triangles_kernel / dc_quads
 -- median over the rounds, per (model, algorithm, cells); extractions are told apart by the order of the process's dispatches,
 which this run records.  Read as a ratio, none of them a threshold: (solve + quads) of algorithm 4 against the triangle phase of
@@ -40,9 +40,10 @@ PHASES = (("lattice", ("lattice_kernel", "sdfprog_mesh_lattice")),
           ("count", ("edge_mask_kernel", "cell_count_kernel", "totals_kernel", "dc_cell_count", "dc_edge_count", "dc_totals",
                      "rocprim", "scan")),
           ("solve", ("dc_cell_list", "dc_solve")),
-          ("normals", ("dc_demo_normals",)),
-          ("hermite", ("emit_vertices_kernel", "sdfprog_mesh_positions", "sdfprog_mesh_vertices")),
+          ("hermite", ("emit_vertices_kernel", "mesh_edge_positions", "mesh_demo_normals", "sdfprog_mesh_vertices")),
           ("triangles", ("emit_triangles_kernel", "dc_quads")))
+# the columns of the output: a per-vertex ("hermite") kernel that runs after the solve is counted under "normals"
+COLUMNS = ("lattice", "count", "hermite", "solve", "normals", "triangles")
 DUAL = 4
 
 
@@ -108,7 +109,7 @@ def from_trace(args):
         if phase == "solve":
             g["solved"] = True
         elif phase == "hermite" and g["solved"]:
-            phase = "normals"                  # a program's vertex kernel again, this time over the solved vertices
+            phase = "normals"                  # the SDF's per-vertex kernel again, this time over the solved vertices
         g[phase] = g.get(phase, 0) + (end - start)
     mesh_seq = timing["sequence"]
     assert len(groups) == len(mesh_seq), (len(groups), len(mesh_seq))
@@ -119,7 +120,7 @@ def from_trace(args):
             acc.setdefault(f"{variant}@{n}", []).append(g)
     phases = {}
     for key, gs in acc.items():
-        phases[key] = {p: round(statistics.median([g.get(p, 0) for g in gs]) / 1e3, 2) for p, _ in PHASES}   # microseconds
+        phases[key] = {p: round(statistics.median([g.get(p, 0) for g in gs]) / 1e3, 2) for p in COLUMNS}   # microseconds
         phases[key]["sum_us"] = round(sum(phases[key].values()), 2)
     ratios = {}
     for key, ph in phases.items():

@@ -14,7 +14,7 @@ outside the library: the per-phase times are the DEVICE timestamps of the kernel
 process (a run of its own: tracing is not combined with counters), grouped by kernel name --
   lattice    lattice_kernel / sdfprog_mesh_lattice
   count      edge_mask_kernel, cell_count_kernel, the rocPRIM scan kernels, totals_kernel
-  positions  sdfprog_mesh_positions                       (the demo writes positions in its vertex kernel)
+  positions  mesh_edge_positions                          (the demo writes positions in its fused vertex kernel)
   vertices   emit_vertices_kernel / sdfprog_mesh_vertices[_mat]
   triangles  emit_triangles_kernel
 -- median over the rounds, per (variant, cells); a variant's kernels are told apart by the order of the process's dispatches,
@@ -38,7 +38,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 PHASES = (("lattice", ("lattice_kernel", "sdfprog_mesh_lattice")),
           ("count", ("edge_mask_kernel", "cell_count_kernel", "totals_kernel", "rocprim", "scan")),
-          ("positions", ("sdfprog_mesh_positions",)),
+          ("positions", ("mesh_edge_positions",)),
           ("vertices", ("emit_vertices_kernel", "sdfprog_mesh_vertices")),
           ("triangles", ("emit_triangles_kernel",)))
 
