@@ -1,7 +1,10 @@
 // api_internal.h -- shared by the translation units behind include/sdfgrid.h (not part of the ABI).
 #pragma once
 
+#include <hip/hip_runtime.h>
+
 #include <cstdint>
+#include <cstring>
 #include <string>
 
 #include "../../include/sdfgrid.h"
@@ -12,7 +15,7 @@ struct Options {
     uint32_t fill_nontemporal = 0;   // 0 auto (nt when the launch also writes the distance volume), 1 always, 2 never
     uint32_t fill_form = 0;          // 0 auto, 1 rows, 2 flat
     uint32_t raymarch_disable = 0;   // SDFV_RM_NO_*
-    bool raymarch_keep_normal = false;
+    uint32_t raymarch_keep_normal = 0;
     uint32_t raymarch_batch_streams = 1;  // batches of several SMALL launches overlap on side streams
     uint32_t raymarch_camera_staging = 1;  // host arrays of more than kInlineCameras cameras are copied to stream-ordered device memory
     uint32_t raymarch_box_first = 1;   // single frames: groups under the projected bounding box are launched first
@@ -27,15 +30,121 @@ struct Options {
     unsigned long long priority_map = 0;  // tuning build only
     unsigned long long tile_order = 0;    // tuning build only
 };
-const Options& options();
+// One definition each (api_common.hip), hidden like everything that is not the ABI: the calling thread's last message and options.
+extern thread_local char g_err[512];
+extern thread_local Options g_options;
+inline const Options& options() { return g_options; }
 // SDFV_OPT_RCCL_LIBRARY: process-wide path of the RCCL-ABI library the communicator loads (empty = librccl.so.1 by name)
 // (claim_rccl_library_path: the path, and from that moment on SDFV_OPT_RCCL_LIBRARY is refused -- one RCCL per process)
-const char* rccl_library_path();
 std::string rccl_library_path_copy();
-bool rccl_loaded();
 const char* claim_rccl_library_path();
 // Formats the thread-local message sdfv_last_error() returns and hands `code` back.
 int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int hip_fail(hipError_t e, const char* what);  // SDFV_ERR_NO_DEVICE or SDFV_ERR_HIP, with HIP's text
+#define SDFV_HIP(call)                                          \
+    do {                                                        \
+        hipError_t e_ = (call);                                 \
+        if (e_ != hipSuccess) return sdfv::hip_fail(e_, #call); \
+    } while (0)
+#define SDFV_HIP_RETURN(call) return sdfv::hip_status((call), #call)  // the entry point's last call: its status is the answer
+inline int hip_status(hipError_t e, const char* what) { return e == hipSuccess ? SDFV_OK : hip_fail(e, what); }
+
+// ---- the check vocabulary: one body and one message per rule; tests/golden/api_errors.json pins each entry point's order.
+int check_params(const sdfv_demo_params* p, uint32_t sdf_id);
+int check_grid(const sdfv_grid* g);
+int check_lights(const sdfv_render_params* rp);  // only ambient entries can be rendered
+int need_device();
+inline int need_textures(const void* tex0, const void* tex1) {
+    return tex0 && tex1 ? SDFV_OK : set_error(SDFV_ERR_INVALID_ARGUMENT, "texture pointer is NULL");
+}
+// Every entry point that reinterprets a float* as float4* (dwordx4 loads and stores) checks this first: a misaligned
+// caller buffer is an argument error, not a GPU fault.
+template <typename... P>
+int check_texel_alignment(const P*... p) {
+    return ((... | (uintptr_t)p) & 15) ? set_error(SDFV_ERR_INVALID_ARGUMENT, "texel buffers (tex0, tex1, rgba) must be 16-byte aligned") : SDFV_OK;
+}
+inline int check_textures(const void* tex0, const void* tex1) {
+    const int rc = need_textures(tex0, tex1);
+    return rc ? rc : check_texel_alignment(tex0, tex1);
+}
+// `names` is how the message calls the pointers: "dist", "points and out", ...
+template <typename... P>
+int check_word_aligned(const char* names, const P*... p) {
+    return ((... | (uintptr_t)p) & 3) ? set_error(SDFV_ERR_INVALID_ARGUMENT, "%s must be 4-byte aligned", names) : SDFV_OK;
+}
+// SDFV_PASS_VOLUME_INTERLEAVED: the flag needs a volume whose rows pair up.
+inline int check_interleaved_volume(const sdfv_grid* grid, const float* dist, uint32_t flags) {
+    if (!(flags & SDFV_PASS_VOLUME_INTERLEAVED)) return SDFV_OK;
+    if (!dist) return set_error(SDFV_ERR_INVALID_ARGUMENT, "SDFV_PASS_VOLUME_INTERLEAVED without a volume");
+    if ((grid->dims[1] & 1u) || ((uintptr_t)dist & 7))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "the interleaved volume pairs rows: H = %u must be even and the volume 8-byte aligned", grid->dims[1]);
+    return SDFV_OK;
+}
+// A dense fill's argument block (FillArgs, ProgramFillArgs): rows and row length fit the launch's 31-bit indices.
+template <typename Args>
+int check_one_launch(const Args& a) {
+    if ((uint64_t)a.H * a.slab_d > 0x7fffffffull || a.W > 0x7fffffffu)
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "slab of %u x %u rows is too large for one launch", a.H, a.slab_d);
+    return SDFV_OK;
+}
+inline int check_point_buffers(const void* points, const void* out, size_t n) {
+    return n && (!points || !out) ? set_error(SDFV_ERR_INVALID_ARGUMENT, "NULL buffer") : SDFV_OK;
+}
+inline int check_mesher(uint32_t algorithm, uint32_t max_voxels_per_axis) {
+    if (algorithm != SDFV_MESHER_MARCHING_CUBES && algorithm != SDFV_MESHER_DUAL_CONTOURING_PARTICLE)
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "Unsupported algorithm %u", algorithm);  // isosurface.rs:49
+    if (max_voxels_per_axis < 1 || max_voxels_per_axis > 1024)
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "max_voxels_per_axis %u is outside [1, 1024]", max_voxels_per_axis);
+    return SDFV_OK;
+}
+inline uint64_t slab_voxels(const sdfv_grid* g) { return (uint64_t)g->dims[0] * g->dims[1] * (g->z_end - g->z_begin); }
+// A size-prefixed descriptor: read what the caller's header knew, take the rest as 0 / NULL (a binder built against an older
+// header).  A NEWER caller's descriptor: fields this library does not know may only be zero (0 / NULL = "not used" by the
+// descriptors' rule); anything else would be dropped silently.  The caller checks `reserved` next.
+template <typename Desc>
+int read_sized_desc(const Desc* desc, size_t first_version_bytes, const char* type, Desc& d) {
+    if (!desc) return set_error(SDFV_ERR_INVALID_ARGUMENT, "desc is NULL");
+    if (desc->size < first_version_bytes)
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "%s.size = %u is smaller than the descriptor's first version (%zu)", type, desc->size,
+                    first_version_bytes);
+    memset(&d, 0, sizeof(d));
+    memcpy(&d, desc, desc->size < sizeof(d) ? desc->size : sizeof(d));
+    for (uint32_t i = (uint32_t)sizeof(d); i < desc->size; ++i)
+        if (reinterpret_cast<const unsigned char*>(desc)[i] != 0)
+            return set_error(SDFV_ERR_INVALID_ARGUMENT, "%s.size = %u: this library knows %zu bytes and byte %u beyond them is not 0", type,
+                        desc->size, sizeof(d), i);
+    return SDFV_OK;
+}
+
+// The four output planes of an argument block (RaymarchArgs, ProgramMarchArgs) at camera c0 of the caller's.
+template <typename Args>
+void point_outputs_at(Args& a, uint64_t pixels_per_cam, uint32_t c0, float* rgba, uint32_t* rgba8, sdfv_march_aux* aux, float* depth) {
+    a.rgba = rgba ? reinterpret_cast<float4*>(rgba) + c0 * pixels_per_cam : nullptr;
+    a.rgba8 = rgba8 ? rgba8 + c0 * pixels_per_cam : nullptr;
+    a.aux = aux ? aux + c0 * pixels_per_cam : nullptr;
+    a.depth = depth ? depth + c0 * pixels_per_cam : nullptr;
+}
+inline float air_dist() {
+    volatile float a = 1e-1f, b = 0.001234f;  // scene/sdf/mod.rs:42, f32 const evaluation
+    return a + b;
+}
+
+// The per-thread device caches (mesh scratch, batch streams, camera ring, staging block) belong to the HIP device that was
+// current when they were made: each records its owner and is released and re-made when the thread calls in with another.
+int current_device();  // -1: none
+void release_march_caches();  // the batch streams and the camera ring of the calling thread (sdfv_mesh_trim)
+// What the raymarch launcher needs to know about the device it launches on (cached per host thread and device): the
+// hand-written march loop is gfx950 machine code, the XCD-aware tile order assumes workgroup L -> XCD L % xcds, and the
+// occupancy rule counts wave slots.
+struct DeviceFacts {
+    int device = -2;
+    bool gfx950 = false;
+    uint32_t cus = 0, xcds = 0;
+    uint64_t last_level_cache_bytes = 0;
+};
+const DeviceFacts& device_facts();
+// An SDF program's instructions on the current device (copied there on the first use), their count and, if asked for, its box.
+int program_on_device(const sdfv_program* p, const sdfv_prog_op** ops, uint32_t* n_ops, const float** bb = nullptr);
 // The first and the last slice of `slab` (the ones the z-neighbours need) in one launch; o0/o1 address the first
 // owned slice.  Same texels as sdfv_fill_grid over those two slices.  Requires at least two owned slices.
 // Dense fill of `slab` in boundary-first workgroup order (fill_kernels.h): the `lead` first slices and the last one come

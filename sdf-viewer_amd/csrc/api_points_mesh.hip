@@ -1,0 +1,227 @@
+// api_points_mesh.hip -- point, normal and source sampling, and mesh extraction for every SDF kind.
+#include <cstring>
+#include <type_traits>
+
+#include "api_internal.h"
+#include "mesh_kernels.h"
+#include "points_kernels.h"
+#include "program_mesh_kernels.h"
+#include "dual_contour_kernels.h"
+
+using namespace sdfv;
+
+namespace {
+
+struct MeshScratch {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int device = -1;
+    void release() {
+        if (p) (void)hipFree(p);
+        *this = MeshScratch{};
+    }
+};
+thread_local MeshScratch g_mesh_scratch;  // freed by sdfv_mesh_trim(); a thread that exits without it leaks the block
+
+// Meshers::mesh for any SDF the device can evaluate: the arguments are checked by the caller.  An SDF kind supplies two things:
+// `lattice(g, w, stream)` writes the distances of the lattice points, and `attributes(vertices, n, final, stream)` everything but
+// the position of n vertices whose positions are written.  Counting, the scans, the positions of the crossing edges, the
+// triangles (mesh_kernels.h) and dual contouring's solve and quads (dual_contour_kernels.h) do not depend on the SDF.  `final` is
+// false only for dual contouring's Hermite records: crossing-edge vertices in a temporary, of which the solve reads position and
+// normal and nothing else.  The scratch is the calling thread's one block.
+// An SDF kind whose attributes are cheap enough to write under the positions' sparse mask may also give
+// `fused(g, w, vertices, n, stream)`: marching cubes then calls it in the place of positions + attributes (the demo tree does).
+template <typename LatticeFn, typename AttributesFn, typename FusedFn = std::nullptr_t>
+int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis, uint32_t algorithm, sdfv_mesh* out,
+                 hipStream_t st, LatticeFn&& lattice, AttributesFn&& attributes, FusedFn&& fused = nullptr) {
+    const bool dual = algorithm == SDFV_MESHER_DUAL_CONTOURING_PARTICLE;
+    sdfv::MeshGrid g;
+    for (int i = 0; i < 3; ++i) {
+        g.cells[i] = max_voxels_per_axis;
+        g.bb_min[i] = bb_min[i];
+        g.bb_size[i] = bb_max[i] - bb_min[i];
+    }
+    const size_t n_points = g.n_points(), n_cells = g.n_cells();
+    // One scratch block per host thread, grown on demand and kept between calls (allocating ~13 B per lattice point
+    // afresh costs more than the extraction itself); sdfv_mesh_trim() gives it back.
+    sdfv::MeshWork w{};
+    w.scan_tmp_bytes = sdfv::mesh_scan_tmp_bytes(n_points);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_dist = 0, o_first = o_dist + up(n_points * 4), o_cfirst = o_first + up(n_points * 4),
+                 o_mask = o_cfirst + up(n_cells * 4), o_tmp = o_mask + up(n_points), o_totals = o_tmp + up(w.scan_tmp_bytes),
+                 o_qfirst = o_totals + 256, need = o_qfirst + (dual ? up(n_points * 4) : 0);  // dual contouring: one more scan
+    const int device_now = current_device();
+    if (g_mesh_scratch.bytes < need || g_mesh_scratch.device != device_now) {
+        g_mesh_scratch.release();
+        SDFV_HIP(hipMalloc(&g_mesh_scratch.p, need));
+        g_mesh_scratch.bytes = need;
+        g_mesh_scratch.device = device_now;
+    }
+    char* base = static_cast<char*>(g_mesh_scratch.p);
+    w.dist = (float*)(base + o_dist);
+    w.point_first = (uint32_t*)(base + o_first);
+    w.cell_first = (uint32_t*)(base + o_cfirst);
+    w.point_mask = (uint8_t*)(base + o_mask);
+    w.scan_tmp = base + o_tmp;
+    w.quad_first = dual ? (uint32_t*)(base + o_qfirst) : nullptr;
+    struct { void* p; } totals{base + o_totals};
+    SDFV_HIP(lattice(g, w, st));
+    SDFV_HIP(dual ? sdfv::launch_dc_count(g, w, (uint32_t*)totals.p, st) : sdfv::launch_mesh_count(g, w, (uint32_t*)totals.p, st));
+    uint32_t n[3] = {0, 0, 0};  // marching cubes: vertices, triangles; dual contouring: Hermite records, vertices, quads
+    SDFV_HIP(hipMemcpyAsync(n, totals.p, dual ? 12 : 8, hipMemcpyDeviceToHost, st));
+    SDFV_HIP(hipStreamSynchronize(st));
+    sdfv_mesh m{};
+    m.n_vertices = dual ? n[1] : n[0];
+    m.n_indices = dual ? (size_t)n[2] * 6 : (size_t)n[1] * 3;
+    if (m.n_vertices) SDFV_HIP(hipMalloc((void**)&m.vertices, m.n_vertices * sizeof(sdfv_vertex)));
+    if (m.n_indices) {
+        hipError_t e = hipMalloc((void**)&m.indices, m.n_indices * 4);
+        if (e != hipSuccess) {
+            (void)hipFree(m.vertices);
+            return hip_fail(e, "hipMalloc(indices)");
+        }
+    }
+    hipError_t e = hipSuccess;
+    void* hermite = nullptr;  // dual contouring: n[0] Hermite records, then the list of the n[1] active cells
+    if (!dual) {
+        if constexpr (std::is_same_v<std::decay_t<FusedFn>, std::nullptr_t>) {
+            e = sdfv::launch_mesh_edge_positions(g, w, m.vertices, m.n_vertices, st);
+            if (e == hipSuccess) e = attributes(m.vertices, m.n_vertices, true, st);
+        } else {
+            e = fused(g, w, m.vertices, m.n_vertices, st);
+        }
+        if (e == hipSuccess) e = sdfv::launch_mesh_triangles(g, w, m.indices, st);
+    } else if (m.n_vertices) {
+        const size_t records = (size_t)n[0] * sizeof(sdfv_vertex);
+        e = hipMalloc(&hermite, records + m.n_vertices * 4);
+        if (e == hipSuccess) e = sdfv::launch_mesh_edge_positions(g, w, (sdfv_vertex*)hermite, n[0], st);
+        if (e == hipSuccess) e = attributes((sdfv_vertex*)hermite, n[0], false, st);
+        if (e == hipSuccess)
+            e = sdfv::launch_dc_vertices(g, w, (const sdfv_vertex*)hermite, (uint32_t*)((char*)hermite + records), m.vertices,
+                                         m.n_vertices, st);
+        if (e == hipSuccess) e = attributes(m.vertices, m.n_vertices, true, st);
+        if (e == hipSuccess) e = sdfv::launch_dc_quads(g, w, m.indices, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // the next extraction on this thread reuses the scratch
+    if (hermite) (void)hipFree(hermite);
+    if (e != hipSuccess) {
+        (void)hipFree(m.vertices);
+        (void)hipFree(m.indices);
+        return hip_fail(e, "mesh emit");
+    }
+    *out = m;
+    return SDFV_OK;
+}
+
+}  // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int sdfv_sample_points(const sdfv_demo_params* params, uint32_t sdf_id, const float* points, size_t n,
+                       int distance_only, sdfv_sample* out, void* stream) {
+    if (int rc = check_params(params, sdf_id)) return rc;
+    if (int rc = check_point_buffers(points, out, n)) return rc;
+    if (int rc = need_device()) return rc;
+    SDFV_HIP_RETURN(sdfv::launch_sample_points(*params, sdf_id, points, n, distance_only != 0, out, (hipStream_t)stream));
+}
+
+int sdfv_normal_points(const sdfv_demo_params* params, uint32_t sdf_id, const float* points, size_t n, float eps,
+                       int use_default, float* out, void* stream) {
+    if (int rc = check_params(params, sdf_id)) return rc;
+    if (int rc = check_point_buffers(points, out, n)) return rc;
+    if (int rc = need_device()) return rc;
+    SDFV_HIP_RETURN(sdfv::launch_normal_points(*params, sdf_id, nullptr, nullptr, points, n, eps, use_default != 0, out,
+                                        (hipStream_t)stream));
+}
+
+int sdfv_source_sample_scalar(const sdfv_demo_params* params, uint32_t sdf_id, const float bb_min[3],
+                              const float bb_max[3], const float* unit_points, size_t n, float* dist_out, void* stream) {
+    if (int rc = check_params(params, sdf_id)) return rc;
+    if (!bb_min || !bb_max) return set_error(SDFV_ERR_INVALID_ARGUMENT, "bounding box is NULL");
+    if (int rc = check_point_buffers(unit_points, dist_out, n)) return rc;
+    if (int rc = need_device()) return rc;
+    SDFV_HIP_RETURN(sdfv::launch_source_scalar(*params, sdf_id, bb_min, bb_max, unit_points, n, dist_out, (hipStream_t)stream));
+}
+
+int sdfv_source_sample_normal(const sdfv_demo_params* params, uint32_t sdf_id, const float bb_min[3],
+                              const float bb_max[3], const float* unit_points, size_t n, float* normal_out,
+                              void* stream) {
+    if (int rc = check_params(params, sdf_id)) return rc;
+    if (!bb_min || !bb_max) return set_error(SDFV_ERR_INVALID_ARGUMENT, "bounding box is NULL");
+    if (int rc = check_point_buffers(unit_points, normal_out, n)) return rc;
+    if (int rc = need_device()) return rc;
+    SDFV_HIP_RETURN(sdfv::launch_normal_points(*params, sdf_id, bb_min, bb_max, unit_points, n, 0.0f, false, normal_out,
+                                        (hipStream_t)stream));
+}
+
+int sdfv_mesh_postproc(const sdfv_demo_params* params, uint32_t sdf_id, sdfv_vertex* vertices, size_t n, void* stream) {
+    if (int rc = check_params(params, sdf_id)) return rc;
+    if (int rc = check_point_buffers(vertices, vertices, n)) return rc;
+    if (int rc = check_word_aligned("vertices", vertices)) return rc;
+    if (int rc = need_device()) return rc;
+    SDFV_HIP_RETURN(sdfv::launch_mesh_postproc(*params, sdf_id, vertices, n, (hipStream_t)stream));
+}
+
+int sdfv_mesh_extract(const sdfv_demo_params* params, uint32_t sdf_id, const float bb_min[3], const float bb_max[3],
+                      uint32_t max_voxels_per_axis, uint32_t algorithm, sdfv_mesh* out, void* stream) {
+    if (!out) return set_error(SDFV_ERR_INVALID_ARGUMENT, "out is NULL");
+    memset(out, 0, sizeof(*out));
+    if (int rc = check_params(params, sdf_id)) return rc;
+    if (!bb_min || !bb_max) return set_error(SDFV_ERR_INVALID_ARGUMENT, "bounding box is NULL");
+    if (int rc = check_mesher(algorithm, max_voxels_per_axis)) return rc;
+    if (int rc = need_device()) return rc;
+    return extract_mesh(
+        bb_min, bb_max, max_voxels_per_axis, algorithm, out, (hipStream_t)stream,
+        [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, hipStream_t st) {
+            return sdfv::launch_mesh_lattice(*params, sdf_id, g, w, st);
+        },
+        [&](sdfv_vertex* vertices, size_t n, bool, hipStream_t st) {
+            return sdfv::launch_mesh_vertex_normals(*params, sdf_id, vertices, n, st);
+        },
+        [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, sdfv_vertex* vertices, size_t n, hipStream_t st) {
+            return sdfv::launch_mesh_fused_vertices(*params, sdf_id, g, w, vertices, n, st);
+        });
+}
+
+int sdfv_program_mesh_extract(const sdfv_program* p, const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis,
+                              uint32_t algorithm, uint32_t flags, sdfv_mesh* out, void* stream) {
+    if (!out) return set_error(SDFV_ERR_INVALID_ARGUMENT, "out is NULL");
+    memset(out, 0, sizeof(*out));
+    if (!p) return set_error(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if ((bb_min == nullptr) != (bb_max == nullptr))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "bounding box: bb_min and bb_max are both given or both NULL (the program's box)");
+    if (int rc = check_mesher(algorithm, max_voxels_per_axis)) return rc;
+    if (flags & ~SDFV_MESH_WITH_MATERIALS) return set_error(SDFV_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
+    if (int rc = need_device()) return rc;
+    const sdfv_prog_op* dev_ops = nullptr;
+    uint32_t n_ops = 0;
+    const float* bb = nullptr;
+    if (int rc = program_on_device(p, &dev_ops, &n_ops, &bb)) return rc;
+    const bool materials = (flags & SDFV_MESH_WITH_MATERIALS) != 0;
+    return extract_mesh(
+        bb_min ? bb_min : bb, bb_max ? bb_max : bb + 3, max_voxels_per_axis, algorithm, out, (hipStream_t)stream,
+        [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, hipStream_t st) {
+            return sdfv::launch_program_mesh_lattice(dev_ops, n_ops, g, w, st);
+        },
+        [&](sdfv_vertex* vertices, size_t n, bool final, hipStream_t st) {  // the materials belong to the output vertices only
+            return sdfv::launch_program_vertex_normals(dev_ops, n_ops, vertices, n, materials && final, st);
+        });
+}
+
+int sdfv_mesh_trim(void) {
+    g_mesh_scratch.release();
+    release_march_caches();
+    return SDFV_OK;
+}
+
+int sdfv_mesh_free(sdfv_mesh* mesh) {
+    if (!mesh) return SDFV_OK;
+    if (mesh->vertices) (void)hipFree(mesh->vertices);
+    if (mesh->indices) (void)hipFree(mesh->indices);
+    memset(mesh, 0, sizeof(*mesh));
+    return SDFV_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

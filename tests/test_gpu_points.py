@@ -74,3 +74,63 @@ def test_unaligned_and_ragged_batches_take_the_scalar_path(pkg, oracle):
         for view in (flat[1:].view(n, 3), torch.from_numpy(pts).cuda()):   # misaligned by 4 bytes, aligned
             got = pkg.sample_points(prm, view).cpu().numpy()
             np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+# ---- the *_host forms: small requests go through the per-thread staging block, larger ones through temporary buffers
+STAGE_BYTES = 64 << 10                  # SmallStage::kBytes (csrc/api_host.hip)
+SAMPLE_BYTES = 28                       # sizeof(sdfv_sample)
+
+
+def last_staged(out_bytes_per_point):
+    """The largest n whose request fits the staging block: the 12 n bytes of points rounded up to 256, then the output."""
+    fits = lambda n: (12 * n + 255) // 256 * 256 + out_bytes_per_point * n <= STAGE_BYTES
+    n = STAGE_BYTES // (12 + out_bytes_per_point)
+    while not fits(n):
+        n -= 1
+    assert fits(n) and not fits(n + 1)
+    return n
+
+
+def test_host_forms_equal_the_stream_forms_on_both_sides_of_the_staging_threshold(pkg):
+    import ctypes as C
+    import importlib
+    PM = importlib.import_module("sdf-viewer_amd.program")
+    lib, prm = pkg.lib, pkg.default_params()
+    prog = PM.Program().sphere(0.6).material(0.9, 0.2, 0.1, 0.3, 0.4, 0.5).cube(0.45).smooth_union(0.1).build()
+    n_samples, n_normals = last_staged(SAMPLE_BYTES), last_staged(12)
+    assert (n_samples, n_normals) == (1636, 2730)            # 19712 + 45808 = 65520 <= 65536; 32768 + 32760 = 65528 <= 65536
+    rng = np.random.default_rng(31)
+    pts = rng.uniform(-1.2, 1.2, size=(n_normals + 1, 3)).astype(np.float32)
+    dev = torch.from_numpy(pts).cuda()
+
+    def sample_host(p):
+        out = np.full((len(p), 7), np.nan, np.float32)
+        pkg.check(lib.sdfv_sample_points_host(C.byref(prm), 0, p.ctypes.data, len(p), 0, out.ctypes.data))
+        return out
+
+    def normal_host(p):
+        out = np.full((len(p), 3), np.nan, np.float32)
+        pkg.check(lib.sdfv_normal_points_host(C.byref(prm), 0, p.ctypes.data, len(p), 0.0, 0, out.ctypes.data))
+        return out
+
+    forms = ((sample_host, lambda d: pkg.sample_points(prm, d), n_samples),
+             (normal_host, lambda d: pkg.normal_points(prm, d), n_normals),
+             (prog.sample_points_host, prog.sample_points, n_samples))
+    for host_form, stream_form, n_last in forms:
+        want = stream_form(dev).cpu().numpy().view(np.uint32)
+        for n in (n_last, n_last + 1, 1):                    # staged, temporary buffers, then one point through the used staging block
+            got = host_form(np.ascontiguousarray(pts[:n]))
+            np.testing.assert_array_equal(got.view(np.uint32), want[:n])
+
+    # Mesh::postproc in place over host vertices: three vertices near the surface, against the stream forms
+    verts = np.zeros((3, pkg.VERTEX_FLOATS), np.float32)
+    verts[:, :3] = [(0.95, 0.1, -0.2), (-0.3, 0.6, 0.1), (0.2, -0.45, 0.5)]
+    want = pkg.mesh_postproc(prm, torch.from_numpy(verts).cuda()).cpu().numpy()
+    got = verts.copy()
+    pkg.check(lib.sdfv_mesh_postproc_host(C.byref(prm), 0, got.ctypes.data, 3))
+    np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32))
+    want = prog.mesh_postproc(torch.from_numpy(verts).cuda()).cpu().numpy()
+    got = verts.copy()
+    pkg.check(lib.sdfv_program_mesh_postproc_host(prog.h, got.ctypes.data, 3))
+    np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert not (want == verts).all()                         # postproc did write something
