@@ -213,6 +213,29 @@ typedef enum sdfv_option {
                                         * path that fails to load is final too: one attempt per process, its dlerror() text is in
                                         * sdfv_last_error()).  sdfv_get_option hands back the address of a copy of the path that
                                         * belongs to the calling thread, valid until that thread asks again */
+    SDFV_OPT_RAYMARCH_LOD_FILTER = 16, /* how sdfv_raymarch_ex samples a grid that is still loading (rp->lod_dist_between_samples = L != 1;
+                                        * with L == 1 the option is not read and the launch takes the kernel it always took): 0 (default)
+                                        * sdfSampleRawNearest, the reference's snap to the nearest loaded lattice point (material.frag:27-36)
+                                        * | 1 lattice trilinear, the "manual interpolation of non-contiguous sdfTex values" the shader's
+                                        * author names as the correct way and leaves as a TODO (material.frag:39-52).  The reference has no
+                                        * text for it; this is the specification.  L must be a power of two in [2, 2^15] (what LoadingManager
+                                        * publishes), anything else is SDFV_ERR_INVALID_ARGUMENT.  A sample of texture T (tex0 or tex1, all
+                                        * four channels) at p: q = (p - bounds_min) / (bounds_max - bounds_min) as for every filter; per
+                                        * axis with N texels, in f32, every step rounded on its own:
+                                        *     u = q * N - 0.5         (the LINEAR footprint's coordinate: continuous with the loaded state)
+                                        *     s = u / L,  f = floorf(s),  a = s - f,  m = (int)f
+                                        *     M = (N + L - 1) / L     (lattice points on the axis, what LoadingManager's pass_len counts)
+                                        *     texel indices clamp(m, 0, M - 1) * L and clamp(m + 1, 0, M - 1) * L
+                                        * and the value is mix(mix(mix(t000, t100, ax), mix(t010, t110, ax), ay), mix(mix(t001, t101, ax),
+                                        * mix(t011, t111, ax), ay), az) with mix(x, y, a) = x * (1 - a) + y * a over those eight texels.  The
+                                        * clamp is the rule on every grid (no MirroredRepeat), so no texel off the lattice is ever read.
+                                        * Everything else of main() is the shader's: ray set-up, the 0.2 shift, 255 samples, the 1e-4 and
+                                        * 1e-5 thresholds, the -0.1 decode; raw0 / raw1 are tex0 / tex1 through this filter at the hit, and
+                                        * sdfNormal's four taps go through it at h = 1 / length(tex_size / L).  The march reads tex0.r in
+                                        * place (dist / pairs / ilv are ignored while L != 1, as with 0).  Not read by the program march
+                                        * (which uses the lod for the tap distance only) nor by the sharded march (which refuses L != 1).
+                                        * Per thread like every option: sdfv_raymarch_host, SDFViewer::render, sdfv_viewer_render and
+                                        * sdfv_scene_render march on the caller's thread and follow it */
     SDFV_OPT_TUNING_WAVE_TIMING = 100, /* tuning build only (-DSDFV_TUNING): DEVICE address of 32 B per raymarch wave */
     SDFV_OPT_TUNING_TILE_ORDER = 102,  /* tuning build only: DEVICE address of tiles_x * tiles_y uint32 tile numbers (row-major
                                         * tile index by * tiles_x + bx): workgroup L of a single-camera launch renders tile

@@ -108,7 +108,9 @@ int sdfv_viewer_textures(const sdfv_viewer *v, float **tex0, float **tex1, sdfv_
 /* both textures to HOST memory (W*H*D*4 floats each); synchronises the viewer's stream */
 int sdfv_viewer_download(sdfv_viewer *v, float *tex0_host, float *tex1_host);
 /* SDFViewerMaterial::render: one ray per pixel into rgba_device (width*height*4 floats, DEVICE); view NULL = the scene's
- * default camera */
+ * default camera.  The march runs on the CALLING thread, so that thread's options hold: while the grid is still loading,
+ * sdfv_set_option(SDFV_OPT_RAYMARCH_LOD_FILTER, 1) (sdfgrid.h) on it makes this frame -- and sdfv_scene_render's -- interpolate
+ * between the loaded lattice points instead of snapping to the nearest.  Nothing is exported here for it */
 int sdfv_viewer_render(sdfv_viewer *v, const sdfv_view *view, uint32_t width, uint32_t height, float *rgba_device);
 /* the hipStream_t every later call of this viewer enqueues on (NULL = the default stream) */
 int sdfv_viewer_set_stream(sdfv_viewer *v, void *stream);

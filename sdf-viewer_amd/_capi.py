@@ -234,6 +234,7 @@ OPT_RAYMARCH_CAMERA_STAGING = 12
 OPT_PASS_FORM = 13  # 0 auto | 1 per-voxel kernels for unflagged passes (A/B)
 OPT_RCCL_LIBRARY = 14  # process-wide: address of the path of the RCCL-ABI library to load (before the first communicator)
 OPT_PASS_LOADS = 15  # 0 auto (SDFV_PASS_EXPECT_NOOP decides) | 1 cached | 2 nontemporal loads for update_required
+OPT_RAYMARCH_LOD_FILTER = 16  # a loading grid (lod != 1): 0 sdfSampleRawNearest (default) | 1 trilinear over the loaded lattice
 OPT_EXT_SRGB_QUANT = 10  # Srgba::from(Vec3): 0 truncate (default) | 1 round
 OPT_TUNING_WAVE_TIMING = 100
 OPT_TUNING_PRIORITY_MAP = 101

@@ -134,6 +134,7 @@ static const struct { uint32_t option; uint32_t Options::*member; uint32_t max; 
     {SDFV_OPT_RAYMARCH_CAMERA_STAGING, &Options::raymarch_camera_staging, 1},
     {SDFV_OPT_EXT_SRGB_QUANT, &Options::ext_srgb_quant, 1},       {SDFV_OPT_PASS_FORM, &Options::pass_form, 1},
     {SDFV_OPT_PASS_LOADS, &Options::pass_loads, 2},                {SDFV_OPT_RAYMARCH_KEEP_NORMAL, &Options::raymarch_keep_normal, 1},
+    {SDFV_OPT_RAYMARCH_LOD_FILTER, &Options::raymarch_lod_filter, 1},
     {SDFV_OPT_RAYMARCH_DISABLE, &Options::raymarch_disable,  // a mask: the six flags are bits 0..5, so no other bit = at most their sum
      SDFV_RM_NO_FAST_INDEX | SDFV_RM_NO_POW2_EXTENT | SDFV_RM_NO_POW2_SIZE | SDFV_RM_NO_SYMMETRIC | SDFV_RM_NO_ASM_LOOP | SDFV_RM_NO_INTERIOR_FETCH},
 };

@@ -16,6 +16,7 @@ struct Options {
     uint32_t fill_form = 0;          // 0 auto, 1 rows, 2 flat
     uint32_t raymarch_disable = 0;   // SDFV_RM_NO_*
     uint32_t raymarch_keep_normal = 0;
+    uint32_t raymarch_lod_filter = 0;  // 0 sdfSampleRawNearest, 1 the lattice filter (launches with lod_dist_between_samples != 1 only)
     uint32_t raymarch_batch_streams = 1;  // batches of several SMALL launches overlap on side streams
     uint32_t raymarch_camera_staging = 1;  // host arrays of more than kInlineCameras cameras are copied to stream-ordered device memory
     uint32_t raymarch_box_first = 1;   // single frames: groups under the projected bounding box are launched first

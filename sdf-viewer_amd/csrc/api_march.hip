@@ -169,6 +169,14 @@ int raymarch_rows(const sdfv_march_desc& d, uint32_t y0, uint32_t y1, uint32_t b
     if (rp->tex_size[0] == 0 || rp->tex_size[1] == 0 || rp->tex_size[2] == 0)
         return set_error(SDFV_ERR_INVALID_ARGUMENT, "empty texture");
     if (!(rp->lod_dist_between_samples >= 1.0f)) return set_error(SDFV_ERR_INVALID_ARGUMENT, "lod_dist_between_samples < 1");
+    const uint32_t lod_filter = g_options.raymarch_lod_filter;
+    if (lod_filter == 1 && rp->lod_dist_between_samples != 1.0f) {  // the lattice filter: L a power of two (what LoadingManager publishes)
+        int e = 0;
+        const float lod = rp->lod_dist_between_samples;
+        if (!(lod >= 2.0f && lod <= 32768.0f) || frexpf(lod, &e) != 0.5f)
+            return set_error(SDFV_ERR_INVALID_ARGUMENT,
+                             "SDFV_OPT_RAYMARCH_LOD_FILTER 1: lod_dist_between_samples %g is not a power of two in [2, 32768]", (double)lod);
+    }
     if ((uint64_t)rp->tex_size[0] * rp->tex_size[1] * rp->tex_size[2] >= (1ull << 32))
         return set_error(SDFV_ERR_INVALID_ARGUMENT, "texture too large for 32-bit texel indexing");
     if (int rc = need_device()) return rc;
@@ -269,11 +277,11 @@ int raymarch_rows(const sdfv_march_desc& d, uint32_t y0, uint32_t y1, uint32_t b
             if (r.recorded[slot] && !hip_ok(hipStreamWaitEvent(on, r.read[slot], 0), "hipStreamWaitEvent")) break;
             if (!hip_ok(sdfv::launch_store_cameras(cameras + c0, nc, at, on), "store_cameras")) break;
             a.camera_list = at;
-            hip_ok(sdfv::launch_raymarch(a, on), "launch_raymarch") && hip_ok(hipEventRecord(r.read[slot], on), "hipEventRecord");
+            hip_ok(sdfv::launch_raymarch(a, on, lod_filter), "launch_raymarch") && hip_ok(hipEventRecord(r.read[slot], on), "hipEventRecord");
             r.recorded[slot] = true;  // (a failed record leaves the event as it was: waiting on it is harmless)
             continue;
         }
-        hip_ok(sdfv::launch_raymarch(a, on), "launch_raymarch");
+        hip_ok(sdfv::launch_raymarch(a, on, lod_filter), "launch_raymarch");
     }
     for (uint32_t i = 0; i < used; ++i)  // (joined even after an error: the side streams must not run on behind the caller's)
         hip_ok(hipEventRecord(g_batch_streams.join[i], g_batch_streams.side[i]), "hipEventRecord") &&

@@ -70,7 +70,9 @@ struct RaymarchArgs {
 // full MirroredRepeat); the others the fast march (LINEAR, clamp for mirror) over tex0.r in place, the compact distance volume
 // (sdfv_commit_distance), the y-pair volume (sdfv_commit_pairs; two 16-byte gathers per cell) and the y-interleaved volume
 // (sdfv_commit_interleaved; 4 B/voxel, 2 or 4 lines per cell) -- the last two are read by the hand-written loop only.
-constexpr int kMarchGeneral = 0, kMarchTex0 = 1, kMarchDist = 2, kMarchPairs = 3, kMarchIlv = 4;
+// kMarchLattice: the lattice filter of a loading grid (SDFV_OPT_RAYMARCH_LOD_FILTER 1, lod_dist_between_samples = L > 1): trilinear over
+// the texels whose indices are multiples of L, tex0.r in place, clamp on every grid (include/sdfgrid.h states it).
+constexpr int kMarchGeneral = 0, kMarchTex0 = 1, kMarchDist = 2, kMarchPairs = 3, kMarchIlv = 4, kMarchLattice = 5;
 
 constexpr uint32_t kInlineCameras = 16;
 // One launch for BASELINE config 5's 64-camera batch (1.59 -> 1.48 ms against four launches of 16, and a rank's share of it
@@ -99,7 +101,9 @@ struct SlabMarchArgs {
 };
 hipError_t launch_raymarch_slab(const RaymarchArgs& a, const SlabMarchArgs& s, hipStream_t stream);
 
-hipError_t launch_raymarch(const RaymarchArgs& a, hipStream_t stream);
+// lod_filter: SDFV_OPT_RAYMARCH_LOD_FILTER as the caller's thread has it; read only when rp.lod_dist_between_samples != 1 (then
+// the caller has checked that the lod is a power of two in [2, 2^15]).
+hipError_t launch_raymarch(const RaymarchArgs& a, hipStream_t stream, uint32_t lod_filter);
 // would the launcher march over a pair (kind kMarchPairs) / y-interleaved (kind kMarchIlv) volume for these arguments, pointers apart?
 bool march_volume_applicable(const RaymarchArgs& a, int kind);
 // the launcher's choice among the volumes taken as present: kMarchIlv, kMarchPairs, or 0 = neither (dist / tex0.r is marched)

@@ -273,6 +273,99 @@ __device__ __forceinline__ void march_fast(const RaymarchArgs& a, const Tex& t, 
     if (covered) status = marching ? -1 : (oob_dist<SYMM>(a, ray_pos) > 1e-4f ? -2 : 1);
 }
 
+// ---- the lattice filter: trilinear over the points a loading grid already holds (SDFV_OPT_RAYMARCH_LOD_FILTER = 1) ----------
+// While a grid loads, only the texels whose three indices are multiples of L = lod_dist_between_samples (a power of two) are
+// there; include/sdfgrid.h states the filter over them operation by operation.  Per axis with N texels: u = q * N - 0.5 (the
+// LINEAR footprint's coordinate), s = u / L, cell floor(s), weight s - floor(s), the two texels clamp(m, 0, M - 1) * L and
+// clamp(m + 1, 0, M - 1) * L with M = ceil(N / L) lattice points.  The clamp is the rule everywhere (no mirror, no condition on
+// the box), so no texel off the lattice is ever read.
+struct Lattice {
+    uint32_t shift;     // log2(L)
+    float inv_l;        // 1 / L: a power of two, so u * inv_l == u / L bit for bit
+    int mx1, my1, mz1;  // M - 1 per axis
+};
+__device__ __forceinline__ Lattice lattice_of(const RaymarchArgs& a, const Tex& t) {
+    const uint32_t l = (uint32_t)a.rp.lod_dist_between_samples;  // the API layer checked: a power of two in [2, 2^15]
+    Lattice g;
+    g.shift = 31u - (uint32_t)__builtin_clz(l);
+    g.inv_l = 1.0f / a.rp.lod_dist_between_samples;
+    g.mx1 = (int)(((uint32_t)t.w + l - 1u) >> g.shift) - 1;
+    g.my1 = (int)(((uint32_t)t.h + l - 1u) >> g.shift) - 1;
+    g.mz1 = (int)(((uint32_t)t.d + l - 1u) >> g.shift) - 1;
+    return g;
+}
+// The eight texel offsets of lattice cell (floor(s) per axis = fu, fv, fw): the one place the index rule is written.
+__device__ __forceinline__ void lattice_cell(const Tex& t, const Lattice& g, float fu, float fv, float fw, Footprint& f) {
+    const int i0 = (int)fu, j0 = (int)fv, k0 = (int)fw;
+    const uint32_t sy = (uint32_t)t.w, sz = (uint32_t)t.w * (uint32_t)t.h;
+    const uint32_t i0m = (uint32_t)min(max(i0, 0), g.mx1) << g.shift, i1m = (uint32_t)min(max(i0 + 1, 0), g.mx1) << g.shift;
+    const uint32_t j0m = ((uint32_t)min(max(j0, 0), g.my1) << g.shift) * sy, j1m = ((uint32_t)min(max(j0 + 1, 0), g.my1) << g.shift) * sy;
+    const uint32_t k0m = ((uint32_t)min(max(k0, 0), g.mz1) << g.shift) * sz, k1m = ((uint32_t)min(max(k0 + 1, 0), g.mz1) << g.shift) * sz;
+    f.o000 = k0m + j0m + i0m; f.o100 = k0m + j0m + i1m;
+    f.o010 = k0m + j1m + i0m; f.o110 = k0m + j1m + i1m;
+    f.o001 = k1m + j0m + i0m; f.o101 = k1m + j0m + i1m;
+    f.o011 = k1m + j1m + i0m; f.o111 = k1m + j1m + i1m;
+}
+__device__ __forceinline__ Footprint lattice_footprint(const Tex& t, const Lattice& g, V3 p01) {
+    const float u = p01.x * (float)t.w - 0.5f, v = p01.y * (float)t.h - 0.5f, w = p01.z * (float)t.d - 0.5f;
+    const float su = u * g.inv_l, sv = v * g.inv_l, sw = w * g.inv_l;
+    const float fu = floorf(su), fv = floorf(sv), fw = floorf(sw);
+    Footprint f;
+    f.ax = su - fu; f.ay = sv - fv; f.az = sw - fw;
+    lattice_cell(t, g, fu, fv, fw, f);
+    return f;
+}
+
+// sdfRaycast's loop for the lattice filter: march_fast's shape (predicated straight-line code, the ballot as the wave-level
+// exit, status and step count derived after the loop) over tex0.r in place, with the one-cell register cache keyed on
+// floor(s).  A lattice cell is L voxels wide, so a ray stays in its cell for more steps than on the loaded grid.  The cache
+// starts with a NaN key: no floor(s) compares equal to it, whatever the box (there is no fast_index condition here).
+template <int XF, bool SYMM, bool T>
+__device__ __forceinline__ void march_lattice(const RaymarchArgs& a, const Tex& t, const Lattice& g, V3 ray_dir, bool covered, V3& ray_pos,
+                                              float& dist_from_origin, int& status, int& steps, int& iterations) {
+    static_assert(XF == 0 || XF == 1, "no fused scale: s = (q * N - 0.5) / L keeps the LINEAR footprint's u");
+    const float* __restrict__ vol = reinterpret_cast<const float*>(a.tex0);
+    const float fw_ = (float)t.w, fh_ = (float)t.h, fd_ = (float)t.d;
+    bool marching = covered;
+    int last_i = -1;
+    float cfu = __int_as_float(0x7fc00000), cfv = cfu, cfw = cfu;
+    float t000 = 0.0f, t100 = 0.0f, t010 = 0.0f, t110 = 0.0f, t001 = 0.0f, t101 = 0.0f, t011 = 0.0f, t111 = 0.0f;
+    for (int i = 0; i < 255; ++i) {
+        // Stop condition: out of bounds (material.frag:106-109)
+        marching = marching && !(oob_dist<SYMM>(a, ray_pos) > 1e-4f);
+        if (__ballot(marching) == 0ull) break;  // wave-level early termination
+        ++iterations;
+        last_i = marching ? i : last_i;
+        const V3 q = to_p01<XF>(a, ray_pos);
+        const float su = (q.x * fw_ - 0.5f) * g.inv_l, sv = (q.y * fh_ - 0.5f) * g.inv_l, sw = (q.z * fd_ - 0.5f) * g.inv_l;
+        const float fu = floorf(su), fv = floorf(sv), fw = floorf(sw);
+        const float ax = su - fu, ay = sv - fv, az = sw - fw;
+        if (marching && (fu != cfu || fv != cfv || fw != cfw)) {
+            cfu = fu; cfv = fv; cfw = fw;
+            Footprint c;
+            lattice_cell(t, g, fu, fv, fw, c);
+            t000 = vol[(uint64_t)c.o000 * 4]; t100 = vol[(uint64_t)c.o100 * 4];
+            t010 = vol[(uint64_t)c.o010 * 4]; t110 = vol[(uint64_t)c.o110 * 4];
+            t001 = vol[(uint64_t)c.o001 * 4]; t101 = vol[(uint64_t)c.o101 * 4];
+            t011 = vol[(uint64_t)c.o011 * 4]; t111 = vol[(uint64_t)c.o111 * 4];
+        }
+        const float sample_dist = trilerp(t000, t100, t010, t110, t001, t101, t011, t111, ax, ay, az) - 1e-1f;
+        // Stop condition: actually hit the surface (material.frag:117-121)
+        marching = marching && !(sample_dist < 1e-5f);
+        // Move the ray forward by the minimum distance to the surface (material.frag:124-125)
+        const V3 np = madd(ray_pos, ray_dir, sample_dist);
+        ray_pos.x = marching ? np.x : ray_pos.x;
+        ray_pos.y = marching ? np.y : ray_pos.y;
+        ray_pos.z = marching ? np.z : ray_pos.z;
+        if (T) {
+            const float nt = dist_from_origin + sample_dist;
+            dist_from_origin = marching ? nt : dist_from_origin;
+        }
+    }
+    steps = last_i + 1;
+    if (covered) status = marching ? -1 : (oob_dist<SYMM>(a, ray_pos) > 1e-4f ? -2 : 1);
+}
+
 // ---- the march loop in gfx950 assembly -------------------------------------------------------------------------------
 // A frame is as long as its longest wave: ONE grazing ray doing up to 255 dependent iterations alone on its SIMD, where
 // a lone wave issues one instruction every ~6-11 cycles whatever the instruction is.  So the loop is priced per
@@ -665,7 +758,8 @@ __device__ __forceinline__ bool box_fragment_ray(const RaymarchArgs& a, V3 eye, 
     return covered;
 }
 
-// MODE: kMarchGeneral .. kMarchIlv = 0 .. 4, what the march loop reads (raymarch_kernels.h).
+// MODE: kMarchGeneral .. kMarchIlv = 0 .. 4, what the march loop reads (raymarch_kernels.h); kMarchLattice = 5: the lattice
+//       filter of a loading grid (march_lattice; LINEAR false, XF 0 or 1).
 // XF:   0 = IEEE divide, 1 = exact power-of-two reciprocal, 2 = power-of-two extents and texture sizes.
 // AUX:  the per-pixel march record is stored (and distanceFromOrigin accumulated).
 #ifndef SDFV_RM_MIN_WAVES
@@ -800,7 +894,9 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
 #ifdef SDFV_TUNING
     const unsigned long long t_loop0 = a.wave_timing ? __builtin_readcyclecounter() : 0ull;
 #endif
-    if constexpr (FAST && ASM) {
+    if constexpr (MODE == kMarchLattice) {
+        march_lattice<XF, SYMM, AUX>(a, tex0, lattice_of(a, tex0), ray_dir, covered, ray_pos, dist_from_origin, status, steps, iterations);
+    } else if constexpr (FAST && ASM) {
         march_asm<MODE, AUX>(a, tex0, ray_dir, covered, ray_pos, dist_from_origin, status, steps, iterations);
     } else if constexpr (FAST) {  // the C++ loop, where the hand-written one's specialisation does not apply
         march_fast<MODE, XF, SYMM, AUX>(a, tex0, ray_dir, covered, ray_pos, dist_from_origin, status, steps, iterations);
@@ -841,13 +937,17 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
     if (status == 1) {
         // The fast kernels know the hit point is within 1e-4 of the box; the normal's taps are h further out,
         // a.fast_normal says whether floor(u) still stays in [-1, N-1] for them.
-        const float4 raw0 = sample_rgba<LINEAR, XF, FAST ? kClamp : kMirror>(a, tex0, ray_pos);  // == the march's last sample
+        float4 raw0;
+        if constexpr (MODE == kMarchLattice) raw0 = gather_rgba(tex0.data, lattice_footprint(tex0, lattice_of(a, tex0), to_p01<XF>(a, ray_pos)));
+        else raw0 = sample_rgba<LINEAR, XF, FAST ? kClamp : kMirror>(a, tex0, ray_pos);  // == the march's last sample
         // one texture's eight 16-byte corners at a time: both sets in flight together cost 6 more VGPRs (78: one wave per
         // SIMD less) and buy nothing even for single frames, which are not occupancy-limited -- measured 1 % SLOWER on
         // every view at 1080p / 256^3 and 4K / 512^3 (round 3 A/B, profiles/r03_hit_path_ab.json)
         V3 pos1 = ray_pos;
         asm volatile("" : "+v"(pos1.x) : "v"(raw0.x), "v"(raw0.y), "v"(raw0.z), "v"(raw0.w));  // same value, after raw0
-        const float4 raw1 = sample_rgba<LINEAR, XF, FAST ? kClamp : kMirror>(a, tex1, pos1);  // material.frag:154
+        float4 raw1;  // material.frag:154
+        if constexpr (MODE == kMarchLattice) raw1 = gather_rgba(tex1.data, lattice_footprint(tex1, lattice_of(a, tex1), to_p01<XF>(a, pos1)));
+        else raw1 = sample_rgba<LINEAR, XF, FAST ? kClamp : kMirror>(a, tex1, pos1);
         rgba = shade(a.rp, raw0, raw1);
         if (a.depth) {  // gl_FragDepth, material.frag:180-181
             frag_depth = frag_depth_of(cam.bvp, ray_pos.x, ray_pos.y, ray_pos.z);
@@ -857,7 +957,13 @@ __global__ __launch_bounds__(256, SDFV_RM_MIN_WAVES) void raymarch_kernel(Raymar
             const float h = tap_distance((float)tex0.w, (float)tex0.h, (float)tex0.d, a.rp.lod_dist_between_samples);
             const V3 p1 = normal_tap(ray_pos, h, 0), p2 = normal_tap(ray_pos, h, 1), p3 = normal_tap(ray_pos, h, 2), p4 = normal_tap(ray_pos, h, 3);
             float d1, d2, d3, d4;
-            if (MODE >= kMarchDist && a.dist && a.fast_normal) {  // the taps read the compact distance volume too
+            if constexpr (MODE == kMarchLattice) {  // the taps go through the lattice footprint as well
+                const Lattice g = lattice_of(a, tex0);
+                d1 = gather_r(tex0_r, 4, lattice_footprint(tex0, g, to_p01<XF>(a, p1))) - 1e-1f;
+                d2 = gather_r(tex0_r, 4, lattice_footprint(tex0, g, to_p01<XF>(a, p2))) - 1e-1f;
+                d3 = gather_r(tex0_r, 4, lattice_footprint(tex0, g, to_p01<XF>(a, p3))) - 1e-1f;
+                d4 = gather_r(tex0_r, 4, lattice_footprint(tex0, g, to_p01<XF>(a, p4))) - 1e-1f;
+            } else if (MODE >= kMarchDist && a.dist && a.fast_normal) {  // the taps read the compact distance volume too
                 d1 = sample_r<true, XF, kClamp>(a, a.dist, 1, tex0, p1) - 1e-1f;
                 d2 = sample_r<true, XF, kClamp>(a, a.dist, 1, tex0, p2) - 1e-1f;
                 d3 = sample_r<true, XF, kClamp>(a, a.dist, 1, tex0, p3) - 1e-1f;
@@ -1189,14 +1295,15 @@ int march_volume_mode(const RaymarchArgs& a) { return march_volume_choice(a, a.d
 // tex0.r as before -- the same bits either way.
 struct MarchKernel {
     int mode;                // kMarch*
-    bool linear;             // LINEAR filter (lod_dist_between_samples == 1), else sdfSampleRawNearest
+    bool linear;             // LINEAR filter (lod_dist_between_samples == 1), else sdfSampleRawNearest or (kMarchLattice) the lattice filter
     int xf;                  // 0 = IEEE divide, 1 = exact power-of-two reciprocal, 2 = ... and the fused scale (fast march only)
     bool symm;               // |p| - max for the out-of-bounds distance (fast march with xf >= 1 only)
     bool hand_written_loop;  // ASM
 };
 
-MarchKernel select_march_kernel(const RaymarchArgs& a) {
+MarchKernel select_march_kernel(const RaymarchArgs& a, uint32_t lod_filter) {
     MarchKernel k{kMarchGeneral, a.rp.lod_dist_between_samples == 1.0f, a.pow2_extent ? 1 : 0, false, false};
+    if (!k.linear && lod_filter == 1) k.mode = kMarchLattice;  // a loading grid under SDFV_OPT_RAYMARCH_LOD_FILTER 1: any box, any size
     if (!k.linear || !a.fast_index) return k;
     k.mode = march_volume_mode(a);
     if (k.mode == 0) k.mode = a.dist ? kMarchDist : kMarchTex0;
@@ -1245,6 +1352,8 @@ hipError_t launch_selected(const MarchKernel& k, const RaymarchArgs& a, dim3 gri
         SDFV_VARIANT(kMarchGeneral, true, 0, false, false);
         SDFV_VARIANT(kMarchGeneral, false, 1, false, false);
         SDFV_VARIANT(kMarchGeneral, false, 0, false, false);
+        SDFV_VARIANT(kMarchLattice, false, 1, false, false);
+        SDFV_VARIANT(kMarchLattice, false, 0, false, false);
     default: return hipErrorInvalidValue;  // select_march_kernel names no other
     }
 #undef SDFV_VARIANT
@@ -1319,7 +1428,7 @@ static uint32_t lds_cap_for(uint32_t w) {
     return bytes;
 }
 
-hipError_t launch_raymarch(const RaymarchArgs& a, hipStream_t stream) {
+hipError_t launch_raymarch(const RaymarchArgs& a, hipStream_t stream, uint32_t lod_filter) {
     const uint32_t rows = a.rows_out;
     if (a.width == 0 || rows == 0 || a.n_cameras == 0) return hipSuccess;
     dim3 grid((a.width + 15) / 16, (rows + 15) / 16, a.n_cameras);
@@ -1329,7 +1438,7 @@ hipError_t launch_raymarch(const RaymarchArgs& a, hipStream_t stream) {
     if (a.tile_order) {
         ag.group_shift = 0;
         ag.lds_cap_bytes = lds_cap_for(occupancy_rule(ag));  // no rectangle here: the caller's cap or none
-        return launch_selected(select_march_kernel(ag), ag, dim3(tiles.x * tiles.y, 1, 1), stream);
+        return launch_selected(select_march_kernel(ag, lod_filter), ag, dim3(tiles.x * tiles.y, 1, 1), stream);
     }
 #endif
     // the 1-D launch over groups of 2^shift x 2^shift tiles (padded to whole groups, a multiple of 8 of them), with the
@@ -1356,7 +1465,7 @@ hipError_t launch_raymarch(const RaymarchArgs& a, hipStream_t stream) {
         grouped(a.group_shift);
     }
     ag.lds_cap_bytes = lds_cap_for(occupancy_rule(ag));
-    return launch_selected(select_march_kernel(ag), ag, grid, stream);
+    return launch_selected(select_march_kernel(ag, lod_filter), ag, grid, stream);
 }
 
 }  // namespace sdfv

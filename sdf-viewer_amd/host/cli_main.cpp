@@ -1,7 +1,7 @@
 // cli_main.cpp -- `sdf-viewer-gpu`: the reference's `app` command line on the MI355X path, headless.
 //
 //   sdf-viewer-gpu app [--max-voxels-side N] [--loading-passes P] demo [-t M] [-c F] [-l M] [-s F] [-m F] [-d B]
-//                  [--width W] [--height H] [--out image.ppm] [--dump-textures prefix] [--frames K]
+//                  [--width W] [--height H] [--out image.ppm] [--dump-textures prefix] [--frames K] [--lod-filter nearest|linear]
 //   sdf-viewer-gpu app [...] url <library.so | file://library.so>
 //
 // `url` is the reference's second provider (CliSDFProvider::Url, src/app/cli/mod.rs:41-46: a WebAssembly file exporting the
@@ -44,6 +44,8 @@ static int usage(const char* msg) {
     fprintf(stderr,
             "USAGE:\n    sdf-viewer-gpu app [--max-voxels-side <N>] [--loading-passes <P>] demo [demo flags]\n"
             "                   [--width <W>] [--height <H>] [--out <file.ppm>] [--dump-textures <prefix>] [--frames <K>]\n"
+            "                   [--lod-filter <nearest|linear>]   how a grid that is still loading is sampled (default nearest); this\n"
+            "                                                     program renders after the load has finished, so its frame does not change\n"
             "    sdf-viewer-gpu app [...] url <library.so>      a native SDF provider (include/sdf_provider.h), sampled on the host\n"
             "    sdf-viewer-gpu mesh [-o <mesh.ply|->] [-v <max-voxels-per-axis>] [marching-cubes] [demo [demo flags]]\n"
             "demo flags: -t/--cube-material <brick|normal>  -c/--cube-half-side <f>  -l/--sphere-material <brick|normal>\n"
@@ -126,7 +128,7 @@ int main(int argc, char** argv) {
     size_t max_voxels_side = 64, loading_passes = 2;  // src/app/cli/mod.rs:13-18
     uint32_t width = 1280, height = 720;
     int frames = 1;
-    std::string out = "sdf-viewer-gpu.ppm", dump, url;
+    std::string out = "sdf-viewer-gpu.ppm", dump, url, lod_filter = "nearest";
     std::vector<std::string> demo_args;
     bool in_demo = false;
     for (size_t i = 1; i < args.size(); ++i) {
@@ -145,10 +147,18 @@ int main(int argc, char** argv) {
         else if (a == "--frames") frames = atoi(next("--frames"));
         else if (a == "--out") out = next("--out");
         else if (a == "--dump-textures") dump = next("--dump-textures");
+        else if (a == "--lod-filter") lod_filter = next("--lod-filter <nearest|linear>");
         else if (a == "demo") in_demo = true;
         else if (a == "url") url = next("url <URL>");
         else if (in_demo) demo_args.push_back(a);
         else return usage(("Found argument '" + a + "' which wasn't expected").c_str());
+    }
+    if (lod_filter != "nearest" && lod_filter != "linear") return usage(("--lod-filter: '" + lod_filter + "' is neither nearest nor linear").c_str());
+    // per thread: this thread issues every render below.  SDFV_OPT_RAYMARCH_LOD_FILTER is read while a grid is still loading, and
+    // this program loads to the end before its first frame: the flag sets the option for a host that renders earlier, no more
+    if (sdfv_set_option(SDFV_OPT_RAYMARCH_LOD_FILTER, lod_filter == "linear" ? 1 : 0) != SDFV_OK) {
+        fprintf(stderr, "error: %s\n", sdfv_last_error());
+        return 1;
     }
     std::string err;
     std::shared_ptr<SDFSurface> sdf;
