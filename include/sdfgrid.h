@@ -490,6 +490,22 @@ int  sdfv_program_sample_points_host(const sdfv_program *p, const float *points_
  * Honours SDFV_OPT_EXT_SRGB_QUANT and SDFV_OPT_FILL_NONTEMPORAL; writes tex1.a = AIR_DIST. */
 int  sdfv_program_fill_grid_commit(const sdfv_program *p, const sdfv_grid *grid, float *tex0, float *tex1, float *dist,
                                    uint32_t flags, void *stream);
+/* sdfv_fill_grid_pass_ex for a program: one LoadingManager pass with the program as the SDF, over a whole grid or a z-slab of at
+ * most 2^32 voxels.  The same contract: the pass visits the voxels whose x, y and GLOBAL z are multiples of `step` (a power of
+ * two); a visited voxel is updated if tex0.r == AIR_DIST or its position -- idx / (dim - 1) * size + min, three separately
+ * rounded steps -- lies inside the closed changed_box (HOST, 6 floats min.xyz max.xyz, may be NULL; a NaN bound: nothing is
+ * inside); an updated voxel gets the texel pair sdfv_program_fill_grid_commit writes for it, bit for bit (SDFV_OPT_EXT_SRGB_QUANT
+ * applies); every other voxel is untouched.  With `dist` (either layout, as in sdfv_fill_grid_pass_ex) the volume is read for
+ * update_required, its entries are rewritten with the texels and tex1.a is written as AIR_DIST; without it tex0.r is read and
+ * tex1.a keeps what the grid holds.
+ * An edit of a program is a NEW program (handles do not change) passed over the loaded grid with the box the edit reaches: the
+ * library turns the box into index ranges on the pass lattice once per call, fills exactly those lattice points in one launch
+ * and scans the rest for AIR_DIST in another, so the cost is that of the voxels in the box plus one read of the volume.
+ * flags: SDFV_PASS_VOLUME_INTERLEAVED (layout of dist), SDFV_PASS_EXPECT_NOOP (hint), SDFV_PASS_FRESH_GRID / SDFV_PASS_SAME_LOAD
+ * (knowledge: nothing is read; at step 1 with a volume or over a fresh grid the pass is the dense program fill).  "The same
+ * load" means the same program.  SDFV_PASS_VIRGIN_GRID is refused (SDFV_ERR_INVALID_ARGUMENT): sdfv_grid_init first. */
+int  sdfv_program_grid_pass(const sdfv_program *p, const sdfv_grid *grid, uint32_t step, const float *changed_box,
+                            float *tex0, float *tex1, float *dist, uint32_t flags, void *stream);
 
 /* ---- batched point sampling (the "Batched sampling" TODO, src/sdf/mod.rs:39) ---- */
 /* points: DEVICE, n x 3 floats.  out: DEVICE, n x sdfv_sample.  SDFSurface::sample(p, distance_only). */

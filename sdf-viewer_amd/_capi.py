@@ -194,6 +194,8 @@ PROTOTYPES = {
     "sdfv_program_sample_points_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "sdfv_program_fill_grid_commit": (C.c_int, [C.c_void_p, C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),
+    "sdfv_program_grid_pass": (C.c_int, [C.c_void_p, C.POINTER(Grid), C.c_uint32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint32, C.c_void_p]),
     "sdfv_program_raymarch": (C.c_int, [C.POINTER(ProgramMarchDesc), C.c_void_p]),
     "sdfv_program_raymarch_check": (C.c_int, [C.POINTER(ProgramMarchDesc), C.POINTER(ProgramMarchDesc), C.POINTER(C.c_float)]),
     # ... meshing

@@ -5,6 +5,7 @@
 #include "fill_kernels.h"
 #include "ingest_kernels.h"
 #include "program_kernels.h"
+#include "program_pass_kernels.h"
 
 using namespace sdfv;
 
@@ -322,6 +323,93 @@ int sdfv_program_fill_grid_commit(const sdfv_program* p, const sdfv_grid* grid, 
     a.nontemporal = fill_launch_config(dist != nullptr).nontemporal ? 1u : 0u;
     if (int rc = check_one_launch(a)) return rc;
     SDFV_HIP_RETURN(sdfv::launch_program_fill(a, (hipStream_t)stream));
+}
+
+int sdfv_program_grid_pass(const sdfv_program* p, const sdfv_grid* grid, uint32_t step, const float* changed_box, float* tex0,
+                           float* tex1, float* dist, uint32_t flags, void* stream) {
+    if (!p) return set_error(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if (int rc = check_grid(grid)) return rc;
+    if (int rc = need_textures(tex0, tex1)) return rc;
+    if (step == 0 || (step & (step - 1))) return set_error(SDFV_ERR_INVALID_ARGUMENT, "step %u is not a power of two", step);
+    if (flags & ~(SDFV_PASS_FRESH_GRID | SDFV_PASS_SAME_LOAD | SDFV_PASS_VIRGIN_GRID | SDFV_PASS_VOLUME_INTERLEAVED | SDFV_PASS_EXPECT_NOOP))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "unknown pass flags 0x%x", flags);
+    if (flags & SDFV_PASS_VIRGIN_GRID)
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "SDFV_PASS_VIRGIN_GRID is not supported for programs (sdfv_grid_init first)");
+    if (int rc = check_interleaved_volume(grid, dist, flags)) return rc;
+    if (int rc = check_texel_alignment(tex0, tex1)) return rc;
+    if (int rc = check_word_aligned("dist", dist)) return rc;
+    if (slab_voxels(grid) > (1ull << 32))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "a program pass takes slabs of at most 2^32 voxels, not %llu",
+                         (unsigned long long)slab_voxels(grid));
+    if (int rc = need_device()) return rc;
+    const uint32_t ilv = (flags & SDFV_PASS_VOLUME_INTERLEAVED) ? 1u : 0u;
+    sdfv::ProgramFillArgs f;
+    memset(&f, 0, sizeof(f));
+    if (int rc = program_on_device(p, &f.ops, &f.n_ops)) return rc;
+    set_grid_fill_args(f, *grid, tex0, tex1, dist, ilv);
+    sdfv::ProgramPassArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ops = f.ops;
+    a.n_ops = f.n_ops;
+    set_grid_fill_args(a, *grid, tex0, tex1, dist, ilv);
+    a.step = step;
+    a.nx = (a.W + step - 1) / step;  // loading.rs:82: ceil(limit / step) visits per axis
+    a.ny = (a.H + step - 1) / step;
+    a.z_first = ((grid->z_begin + step - 1) / step) * step;
+    a.nz = a.z_first < grid->z_end ? (grid->z_end - a.z_first + step - 1) / step : 0;
+    if ((uint64_t)a.nx * a.ny * a.nz == 0) return SDFV_OK;
+    // update_required is known to hold for every visited voxel (sdfv_fill_grid_pass_ex: FRESH_GRID, SAME_LOAD): the sub-box is the
+    // whole lattice.  Otherwise it is the lattice points INSIDE the closed changed box: voxel_coord -- three separately rounded
+    // steps, spelled out below as the kernels compute them (this file is built with -ffp-contract=off) -- does not decrease with
+    // the index, so per axis the points with coord >= lo are a tail of the lattice, those with coord <= hi a head, and two
+    // bisections find where they meet.  A NaN bound (or coordinate) fails both compares: the sub-box is empty.
+    const uint32_t n_axis[3] = {a.nx, a.ny, a.nz};
+    uint32_t first[3] = {0, 0, 0}, count[3] = {a.nx, a.ny, a.nz};
+    if (!(flags & (SDFV_PASS_FRESH_GRID | SDFV_PASS_SAME_LOAD))) {
+        for (int i = 0; i < 3; ++i) {
+            if (!changed_box) {
+                count[i] = 0;
+                continue;
+            }
+            auto coord = [&](uint32_t k) {
+                float c = (float)((i == 2 ? a.z_first : 0u) + k * step);
+                c = c / a.dm1[i];
+                c = c * a.bb_size[i];
+                c = c + a.bb_min[i];
+                return c;
+            };
+            // the first k in [0, n] for which `reached(k)` holds, given that it holds on a tail of the lattice
+            auto bisect = [&](auto reached) {
+                uint32_t lo = 0, hi = n_axis[i];
+                while (lo < hi) {
+                    const uint32_t mid = lo + (hi - lo) / 2;
+                    if (reached(mid)) hi = mid;
+                    else lo = mid + 1;
+                }
+                return lo;
+            };
+            const uint32_t begin = bisect([&](uint32_t k) { return coord(k) >= changed_box[i]; });
+            const uint32_t end = bisect([&](uint32_t k) { return !(coord(k) <= changed_box[3 + i]); });
+            first[i] = begin;
+            count[i] = end > begin ? end - begin : 0;
+        }
+    }
+    a.bx0 = first[0], a.by0 = first[1], a.bz0 = first[2];
+    a.bnx = count[0], a.bny = count[1], a.bnz = count[2];
+    const bool whole = a.bnx == a.nx && a.bny == a.ny && a.bnz == a.nz;
+    // ... and a step-1 pass over the whole lattice is the dense program fill, where that writes the same tex1.a: with a volume
+    // (AIR_DIST by contract) or over a fresh grid (AIR_DIST is what it holds)
+    if (whole && step == 1 && (dist || (flags & SDFV_PASS_FRESH_GRID)) && (uint64_t)f.H * f.slab_d <= 0x7fffffffull && f.W <= 0x7fffffffu) {
+        f.nontemporal = fill_launch_config(dist != nullptr).nontemporal ? 1u : 0u;
+        SDFV_HIP_RETURN(sdfv::launch_program_fill(f, (hipStream_t)stream));
+    }
+    SDFV_HIP(sdfv::launch_program_pass_box(a, (hipStream_t)stream));
+    if (whole) return SDFV_OK;
+    // the scan's loads, as sdfv_fill_grid_pass_ex chooses them
+    const uint64_t volume_bytes = slab_voxels(grid) * 4u, llc = device_facts().last_level_cache_bytes;
+    const bool hinted = (flags & SDFV_PASS_EXPECT_NOOP) != 0 && (llc == 0 || volume_bytes > llc);
+    a.stream_loads = g_options.pass_loads == 0 ? (hinted ? 1u : 0u) : (g_options.pass_loads == 2 ? 1u : 0u);
+    SDFV_HIP_RETURN(sdfv::launch_program_pass_scan(a, (hipStream_t)stream));
 }
 
 }  // extern "C"

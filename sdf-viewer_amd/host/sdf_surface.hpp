@@ -145,6 +145,12 @@ class SDFSurface {
     // An SDF that IS an SDF program (include/sdfgrid.h, "SDF programs"): the handle the library's program entry points take.
     // mesh_sdf() and Mesh::postproc() (mesh.hpp) take this route when device_sdf() is empty.  nullptr = not a program.
     virtual const sdfv_program* device_program() const { return nullptr; }
+
+    // ============ whole passes on the device (not in the reference) ============
+    // true: SDFViewer::update loads this SDF -- one with a device_program() -- as it loads the demo: a LoadingManager pass is one
+    // sdfv_program_grid_pass, the budget is checked between passes.  false (ProgramSDF, every callback surface): run by run
+    // through the device-sampled route.
+    virtual bool takes_whole_passes() const { return false; }
 };
 
 // merge_bounding_boxes, defaults.rs:59-72

@@ -186,6 +186,12 @@ size_t SDFViewer::update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_tim
             load_sdf_ = *dev_now;
         }
     }
+    // ... and so does another snapshot of a program that is loaded by whole passes (an edit is a new sdfv_program)
+    const sdfv_program* prog = sdf.takes_whole_passes() ? sdf.device_program() : nullptr;
+    if (prog != load_program_) {
+        if (!fresh_ && (prog || load_program_)) same_load_ = false;
+        load_program_ = prog;
+    }
     if (auto new_box = sdf.changed()) {
         same_load_ = false;
         changed_box = changed_box ? merge_bounding_boxes(*changed_box, *new_box) : *new_box;
@@ -205,10 +211,17 @@ size_t SDFViewer::update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_tim
 
     const size_t start_iter = loading_mgr.total_iterations();
     const auto dev = sdf.device_sdf();
-    if (!dev && sdf.has_device_sampler()) return update_device(sdf, max_delta_time);  // sampled by the caller's kernel
-    if (!dev) return update_host(sdf, max_delta_time);  // any `impl SDFSurface`: sampled on the host, packed on the device
+    if (dev) prog = nullptr;  // (the demo's device form comes first, as in sdfv_surface)
+    if (!dev && !prog && sdf.has_device_sampler()) return update_device(sdf, max_delta_time);  // sampled by the caller's kernel
+    if (!dev && !prog) return update_host(sdf, max_delta_time);  // any `impl SDFSurface`: sampled on the host, packed on the device
     host_mirror_valid_ = false;  // (whatever runs below rewrites tex0.r on the device)
     const sdfv_grid g = grid();
+    // From here on a pass is one launch: the demo tree (dev) or an SDF program that opted in (prog, SDFSurface::takes_whole_passes)
+    // as the SDF of the same loop.  A program pass never takes a virgin grid: the initial state is written first.
+    auto run_pass = [&](uint32_t step, const float* box_ptr, float* dist, uint32_t flags) {
+        return prog ? sdfv_program_grid_pass(prog, &g, step, box_ptr, tex0_device(), tex1_device(), dist, flags, stream)
+                    : sdfv_fill_grid_pass_ex(&dev->params, dev->sdf_id, &g, step, box_ptr, tex0_device(), tex1_device(), dist, flags, stream);
+    };
     const auto start_time = std::chrono::steady_clock::now();
     // Fresh grid, nothing pending, and a budget that lets every pass be enqueued in this call anyway (a pass is
     // one asynchronous launch): the state all passes converge to is the dense fill, which moves 32 B/voxel once
@@ -240,7 +253,10 @@ size_t SDFViewer::update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_tim
         // The fill writes the distance volume in the same pass (+4 B/voxel instead of a second pass over tex0).
         float* dist_out = dist_synced_ ? material.dist->f32() : nullptr;
         int rc;
-        if (dist_out && material.dist_interleaved) {
+        if (prog) {
+            rc = sdfv_program_fill_grid_commit(prog, &g, tex0_device(), tex1_device(), dist_out,
+                                               dist_out && material.dist_interleaved ? SDFV_PASS_VOLUME_INTERLEAVED : 0u, stream);
+        } else if (dist_out && material.dist_interleaved) {
             // the same dense launch through the pass entry point, which carries the volume's layout: a step-1 pass in which
             // update_required holds everywhere (a virgin / fresh grid, or a box that covers it) IS the dense fused fill
             float box[6];
@@ -293,6 +309,10 @@ size_t SDFViewer::update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_tim
         // and read nothing.  A pass that must READ the grid (a changed box, another SDF mid-load) first gets the initial
         // state written into the rows no pass has reached.
         uint32_t flags = 0;
+        if (prog && material.materialize(stream) != 0) {  // (a program pass takes no virgin grid: it becomes a fresh one)
+            error_ = sdfv_last_error();
+            break;
+        }
         if (same_load_ && !changed_box)
             flags = material.undefined_rows ? (SDFV_PASS_VIRGIN_GRID | SDFV_PASS_SAME_LOAD)
                                             : ((fresh_ ? SDFV_PASS_FRESH_GRID : 0u) | SDFV_PASS_SAME_LOAD);
@@ -304,8 +324,7 @@ size_t SDFViewer::update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_tim
         // the manager the reference runs once a changed box has been worked off (:146-156, no box any more) scans a loaded grid
         // and finds nothing: say so (a hint: the scan streams the volume past the caches)
         if (loaded_once_ && !changed_box && flags == (flags & SDFV_PASS_VOLUME_INTERLEAVED)) flags |= SDFV_PASS_EXPECT_NOOP;
-        if (sdfv_fill_grid_pass_ex(&dev->params, dev->sdf_id, &g, (uint32_t)step, box_ptr, tex0_device(), tex1_device(),
-                                   dist_synced_ ? material.dist->f32() : nullptr, flags, stream) != 0) {
+        if (run_pass((uint32_t)step, box_ptr, dist_synced_ ? material.dist->f32() : nullptr, flags) != 0) {
             error_ = sdfv_last_error();
             break;
         }

@@ -115,6 +115,8 @@ class SDFViewer {
     // code: an exception it throws on the calling thread propagates out of update() once the run's workers have stopped --
     // that run is dropped and a later call samples it again; one thrown on a worker thread ends the process, as a panic ends
     // the reference's loop.)
+    // An SDF program that opts in (takes_whole_passes() with a device_program(): EditableProgramSDF) loads like the demo: a pass is
+    // one sdfv_program_grid_pass over the current snapshot, a fresh load or a box that covers the grid one dense program fill.
     // An SDF the application samples on the device itself (has_device_sampler(), no device_sdf()): the same loop with its first
     // half on the device too -- per run, sdfv_emit_update_points writes out the points update_required lets through,
     // sample_batch_device samples them and sdfv_pack_samples packs them; the budget is checked between runs, each timed to its
@@ -175,6 +177,7 @@ class SDFViewer {
     // (added last: the members above keep their offsets)
     std::unique_ptr<DeviceRuns, DeviceRunsDeleter> device_runs_;  // created by the first update() with a device sampler
     size_t visited_before_throw_ = 0;
+    const sdfv_program* load_program_ = nullptr;  // the snapshot the load samples, for an SDF that takes whole passes
 };
 
 }  // namespace sdfviewer

@@ -12,7 +12,9 @@
 #include <string>
 #include <thread>
 
+#include "../../include/sdfprogram.h"
 #include "../../include/sdfviewer.h"
+#include "program_editor.hpp"
 #include "scene.hpp"
 #include "sdf_viewer.hpp"
 
@@ -229,6 +231,23 @@ int sdfv_viewer_update(sdfv_viewer* v, const sdfv_surface* surface, uint64_t bud
             if (visited) *visited = v->v->visited_before_throw();  // (the runs packed before the one that failed)
             throw;
         }
+        if (visited) *visited = n;
+        if (v->v->last_error()[0]) {
+            v->err = v->v->last_error();
+            return (int)SDFV_ERR_HIP;
+        }
+        return (int)SDFV_OK;
+    });
+}
+
+// include/sdfprogram.h: the same call with the editor's own class as the SDF, which opts in to whole passes
+int sdfv_viewer_update_program(sdfv_viewer* v, sdfv_program_editor* e, uint64_t budget_ns, size_t* visited) {
+    if (visited) *visited = 0;
+    if (!v || !v->v) return SDFV_ERR_INVALID_ARGUMENT;
+    return guarded(v->err, [&] {
+        if (!e || !e->sdf) return v->err = "editor is NULL", (int)SDFV_ERR_INVALID_ARGUMENT;
+        const auto budget = std::chrono::nanoseconds((long long)std::min<uint64_t>(budget_ns, (uint64_t)INT64_MAX));
+        const size_t n = v->v->update(*e->sdf, budget);
         if (visited) *visited = n;
         if (v->v->last_error()[0]) {
             v->err = v->v->last_error();

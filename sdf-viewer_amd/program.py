@@ -10,6 +10,15 @@
     prog.fill_grid(grid, t0, t1)                       # the dense fill, one launch
     records = prog.sample_points(points)               # [n, 3] CUDA tensor -> [n, 7]
     viewer.update(prog.as_surface())                   # progressive load through sdf-viewer_amd.viewer
+    prog2.grid_pass(grid, 1, t0, t1, changed_box=box)  # an edited program over the loaded grid: only the box is re-sampled
+
+Parameters (include/sdfprogram.h, "program editor"): name an operand while building, then edit it by name --
+
+    b = Program().material(0.8, 0.2, 0.1).sphere(0.5)
+    b.param("radius", [(len(b.ops) - 1, 0, PARAM_VALUE)], 0.1, 0.9, 0.01, 0.5, box=(-0.9,) * 3 + (0.9,) * 3)
+    ed = b.build_editor()
+    ed.set("radius", 0.6)                              # a new snapshot; ed.changed() -> the box, once
+    ed.update_viewer(viewer)                           # re-samples the box by whole passes (sdfv_viewer_update_program)
     rgba = prog.render(camera, 1920, 1080)             # sphere-traced directly per pixel: no grid
     vertices, indices = prog.mesh(128, materials=True) # marching cubes + Mesh::postproc: [V, 12], [3 * triangles]
 
@@ -20,6 +29,21 @@ import ctypes as C
 
 from . import _capi
 from ._capi import ProgOp, SdfvError, check, lib
+
+
+PARAM_VALUE, PARAM_NEGATED, PARAM_RECIPROCAL = 0, 1, 2
+PARAM_MAX_TARGETS = 4
+
+
+class ParamTarget(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("operand", C.c_uint32), ("kind", C.c_uint32)]
+
+
+class ProgramParam(C.Structure):
+    """sdfv_program_param"""
+    _fields_ = [("id", C.c_uint32), ("name", C.c_char_p), ("description", C.c_char_p), ("min", C.c_float), ("max", C.c_float),
+                ("step", C.c_float), ("value", C.c_float), ("n_targets", C.c_uint32), ("targets", ParamTarget * PARAM_MAX_TARGETS),
+                ("has_box", C.c_uint32), ("box", C.c_float * 6)]
 
 
 def translation(tx, ty, tz):
@@ -44,6 +68,7 @@ class Program:
     def __init__(self, bb=(-1.0, -1.0, -1.0, 1.0, 1.0, 1.0)):
         self.bb = tuple(float(x) for x in bb)
         self.ops = []
+        self.params = []
 
     def op(self, opcode, *operands):
         """Any instruction by opcode (_capi.OP_*) and operands; the named methods below all come here."""
@@ -93,6 +118,18 @@ class Program:
     def build(self):
         return CompiledProgram(self.array(), len(self.ops), self.bb)
 
+    def param(self, name, targets, lo, hi, step, value, box=None, description=""):
+        """A float parameter of the editor build_editor() makes: `targets` is a list of (instruction index, operand index,
+        PARAM_VALUE | PARAM_NEGATED | PARAM_RECIPROCAL), `box` the 6 floats an edit can reach (None: the program's box).  Its id is
+        its position in the list."""
+        self.params.append(dict(name=str(name), targets=[tuple(int(v) for v in t) for t in targets], lo=float(lo), hi=float(hi),
+                                step=float(step), value=float(value), box=None if box is None else tuple(float(v) for v in box),
+                                description=str(description)))
+        return self
+
+    def build_editor(self):
+        return ProgramEditor(self)
+
 
 def _rotation(axis, degrees):
     import math
@@ -135,6 +172,14 @@ class CompiledProgram:
         check(lib.sdfv_program_create(C.cast(ops_array, C.c_void_p), int(n), (C.c_float * 6)(*[float(x) for x in bb]), C.byref(h)))
         self.h = h
         self._surface = None
+        self._owner = None
+
+    @classmethod
+    def borrowed(cls, handle, owner):
+        """A view of a handle that `owner` owns (a ProgramEditor's snapshot): kept alive with it, never freed here."""
+        self = cls.__new__(cls)
+        self.h, self._surface, self._owner = C.c_void_p(handle), None, owner
+        return self
 
     def ops(self):
         """(numpy structured copy of the validated instructions, bounding box)."""
@@ -198,6 +243,14 @@ class CompiledProgram:
         from . import _dev_ptr, _stream_ptr
         check(lib.sdfv_program_fill_grid_commit(self.h, C.byref(grid), _dev_ptr(tex0, "tex0"), _dev_ptr(tex1, "tex1"),
                                                 None if dist is None else _dev_ptr(dist, "dist"), int(flags), _stream_ptr(stream)))
+
+    def grid_pass(self, grid, step, tex0, tex1, dist=None, changed_box=None, flags=0, stream=None):
+        """sdfv_program_grid_pass: one LoadingManager pass with this program as the SDF.  changed_box: 6 floats (min.xyz,
+        max.xyz) or None; flags: _capi.PASS_* as for pkg.fill_grid_pass."""
+        from . import _dev_ptr, _stream_ptr
+        box = None if changed_box is None else (C.c_float * 6)(*[float(v) for v in changed_box])
+        check(lib.sdfv_program_grid_pass(self.h, C.byref(grid), int(step), box, _dev_ptr(tex0, "tex0"), _dev_ptr(tex1, "tex1"),
+                                         None if dist is None else _dev_ptr(dist, "dist"), int(flags), _stream_ptr(stream)))
 
     def march_desc(self, cameras, width, height, rp=None, normal_h=0.0, y0=0, y1=None):
         """An sdfv_program_march_desc over this program without outputs (and what keeps its pointers alive).  cameras: a
@@ -284,8 +337,124 @@ class CompiledProgram:
         return s
 
     def close(self):
-        if self.h:
+        if self.h and self._owner is None:
             lib.sdfv_program_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ProgramEditor:
+    """An sdfv_program_editor (include/sdfprogram.h): a program whose named operands can be edited.  Every accepted set() makes a
+    new snapshot (an immutable sdfv_program); the replaced ones live until trim() or close()."""
+
+    def __init__(self, builder):
+        from . import viewer
+        self._lib = L = viewer.lib
+        L.sdfv_program_editor_create.restype = C.c_int
+        L.sdfv_program_editor_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(ProgramParam), C.c_size_t,
+                                                 C.POINTER(C.c_void_p)]
+        L.sdfv_program_editor_free.restype, L.sdfv_program_editor_free.argtypes = None, [C.c_void_p]
+        L.sdfv_program_editor_parameters.restype = C.c_int
+        L.sdfv_program_editor_parameters.argtypes = [C.c_void_p, C.POINTER(C.POINTER(ProgramParam)), C.POINTER(C.c_size_t)]
+        L.sdfv_program_editor_set.restype, L.sdfv_program_editor_set.argtypes = C.c_int, [C.c_void_p, C.c_uint32, C.c_float]
+        L.sdfv_program_editor_changed.restype, L.sdfv_program_editor_changed.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float)]
+        L.sdfv_program_editor_program.restype, L.sdfv_program_editor_program.argtypes = C.c_void_p, [C.c_void_p]
+        L.sdfv_program_editor_trim.restype, L.sdfv_program_editor_trim.argtypes = C.c_int, [C.c_void_p]
+        L.sdfv_program_editor_last_error.restype, L.sdfv_program_editor_last_error.argtypes = C.c_char_p, [C.c_void_p]
+        L.sdfv_program_editor_as_surface.restype = C.c_int
+        L.sdfv_program_editor_as_surface.argtypes = [C.c_void_p, C.POINTER(viewer.SurfaceStruct)]
+        L.sdfv_viewer_update_program.restype = C.c_int
+        L.sdfv_viewer_update_program.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_size_t)]
+        arr = (ProgramParam * max(len(builder.params), 1))()
+        for i, p in enumerate(builder.params):
+            if len(p["targets"]) > PARAM_MAX_TARGETS:
+                raise SdfvError(-1, f"parameter {p['name']}: more than {PARAM_MAX_TARGETS} targets")
+            arr[i].id, arr[i].name, arr[i].description = i, p["name"].encode(), p["description"].encode()
+            arr[i].min, arr[i].max, arr[i].step, arr[i].value = p["lo"], p["hi"], p["step"], p["value"]
+            arr[i].n_targets = len(p["targets"])
+            for k, (op, operand, kind) in enumerate(p["targets"]):
+                arr[i].targets[k] = ParamTarget(op, operand, kind)
+            arr[i].has_box = int(p["box"] is not None)
+            for k in range(6):
+                arr[i].box[k] = p["box"][k] if p["box"] is not None else 0.0
+        h = C.c_void_p()
+        rc = L.sdfv_program_editor_create(C.cast(builder.array(), C.c_void_p), len(builder.ops), (C.c_float * 6)(*builder.bb), arr,
+                                          len(builder.params), C.byref(h))
+        if rc != 0:
+            raise SdfvError(rc, L.sdfv_program_editor_last_error(None).decode())
+        self.h = h
+        self._ids = {p["name"]: i for i, p in enumerate(builder.params)}
+
+    def _id(self, name):
+        if isinstance(name, str):
+            if name not in self._ids:
+                raise SdfvError(-1, f"unknown parameter {name!r}")
+            return self._ids[name]
+        return int(name)
+
+    def parameters(self):
+        """[dict(id, name, description, min, max, step, value, targets, box)] with the current values."""
+        p, n = C.POINTER(ProgramParam)(), C.c_size_t()
+        check(self._lib.sdfv_program_editor_parameters(self.h, C.byref(p), C.byref(n)))
+        return [dict(id=p[i].id, name=p[i].name.decode(), description=p[i].description.decode(), min=p[i].min, max=p[i].max,
+                     step=p[i].step, value=p[i].value,
+                     targets=[(t.op, t.operand, t.kind) for t in list(p[i].targets)[:p[i].n_targets]],
+                     box=tuple(p[i].box) if p[i].has_box else None) for i in range(n.value)]
+
+    def get(self, name):
+        return self.parameters()[[q["id"] for q in self.parameters()].index(self._id(name))]["value"]
+
+    def set(self, name, value):
+        """set_parameter: raises SdfvError with the reason (out of range, unknown, or the validator's message) and changes nothing
+        when the value is refused."""
+        rc = self._lib.sdfv_program_editor_set(self.h, self._id(name), float(value))
+        if rc != 0:
+            raise SdfvError(rc, self._lib.sdfv_program_editor_last_error(self.h).decode())
+
+    def changed(self):
+        """The pending box (6 floats) once, then None."""
+        out = (C.c_float * 6)()
+        return tuple(out) if self._lib.sdfv_program_editor_changed(self.h, out) == 1 else None
+
+    @property
+    def program(self):
+        """The current snapshot as a CompiledProgram (borrowed: valid until trim() after a later set(), or close())."""
+        return CompiledProgram.borrowed(self._lib.sdfv_program_editor_program(self.h), self)
+
+    def trim(self):
+        """Frees the replaced snapshots; synchronise the streams that may still run one first."""
+        check(self._lib.sdfv_program_editor_trim(self.h))
+
+    def as_surface(self):
+        """A viewer.Surface over the current snapshot, whichever it is at each call, with `changed` set."""
+        from . import viewer
+        s = viewer.Surface()
+        rc = self._lib.sdfv_program_editor_as_surface(self.h, C.byref(s.struct))
+        if rc != 0:
+            raise SdfvError(rc, "sdfv_program_editor_as_surface")
+        bb = (C.c_float * 6)()
+        s.struct.bounding_box(s.struct.user, bb)
+        s._bb = tuple(bb)
+        s._keep.append(self)
+        return s
+
+    def update_viewer(self, viewer_obj, budget_s=0.03, budget_ns=None):
+        """sdfv_viewer_update_program: SDFViewer::update over this editor by whole passes; returns the iterations consumed."""
+        n = C.c_size_t()
+        ns = int(budget_s * 1e9) if budget_ns is None else int(budget_ns)
+        rc = self._lib.sdfv_viewer_update_program(viewer_obj.h, self.h, ns, C.byref(n))
+        if rc != 0:
+            raise SdfvError(rc, self._lib.sdfv_viewer_last_error(viewer_obj.h).decode())
+        return n.value
+
+    def close(self):
+        if self.h:
+            self._lib.sdfv_program_editor_free(self.h)
         self.h = None
 
     def __del__(self):
