@@ -502,6 +502,82 @@ def scenes():
             "smooth_blobs": scene_smooth_blobs(), "rotated_solids": scene_rotated_solids(), "scaled_shells": scene_scaled_shells()}
 
 
+# ---- random scenes: trees of the classes above, nested up to the machine's stack limits ----
+MAX_VALUES, MAX_FRAMES = 8, 4                          # SDFV_PROGRAM_MAX_VALUES, SDFV_PROGRAM_MAX_FRAMES
+RANDOM_SCENES_SEED = 20261019
+
+
+def stack_needs(node):
+    """(values, frames) the emitted program's stacks reach below this node: a Comb evaluates a, keeps it, evaluates b."""
+    if isinstance(node, Prim):
+        return 1, 0
+    if isinstance(node, Comb):
+        (va, fa), (vb, fb) = stack_needs(node.a), stack_needs(node.b)
+        return max(va, 1 + vb), max(fa, fb)
+    v, f = stack_needs(node.child)
+    return v, f + isinstance(node, (Rigid, Scale))
+
+
+def _random_tree(rng, values, frames, prims):
+    """A tree whose program needs at most `values` stack slots and `frames` open frames, of about `prims` primitives."""
+    u = rng.uniform
+    size = lambda: 0.15 + 0.6 * rng.beta(2.0, 2.0)     # noqa: E731
+    roll = rng.random()
+    if frames > 0 and roll < 0.28:
+        if rng.random() < 0.6:
+            R3 = None if rng.random() < 0.3 else rot(rng.normal(size=3), u(-180.0, 180.0))
+            return Rigid(_random_tree(rng, values, frames - 1, prims), tuple(u(-0.4, 0.4, 3)), R3)
+        return Scale(_random_tree(rng, values, frames - 1, prims), u(0.5, 1.6))
+    if roll < 0.36:
+        return Round(_random_tree(rng, values, frames, prims), u(0.01, 0.12))
+    if roll < 0.42:
+        return Shell(_random_tree(rng, values, frames, prims), u(0.03, 0.15))
+    if values >= 2 and prims >= 2:
+        kind = ("union", "intersect", "subtract", "smooth_union", "smooth_subtract")[int(rng.integers(5))]
+        k = u(0.03, 0.3) if kind.startswith("smooth") else None
+        left = 1 if rng.random() < 0.55 else int(rng.integers(1, prims))   # mostly right-deep: that is what fills the value stack
+        return Comb(kind, _random_tree(rng, values, frames, left), _random_tree(rng, values - 1, frames, prims - left), k)
+    mat = tuple(np.round(u(0.0, 1.0, 6), 3))
+    kind = ("sphere", "cube", "box", "cylinder", "torus", "plane")[int(rng.integers(6))]
+    if kind in ("sphere", "cube"):
+        return Prim(kind, size(), mat=mat)
+    if kind == "box":
+        return Prim(kind, size(), size(), size(), mat=mat)
+    if kind == "cylinder":
+        return Prim(kind, size(), size(), mat=mat)
+    if kind == "torus":
+        return Prim(kind, u(0.3, 0.8), u(0.08, 0.3), mat=mat)
+    nrm = rng.normal(size=3)
+    nrm /= np.linalg.norm(nrm)
+    return Prim(kind, *nrm, u(-0.4, 0.4), mat=mat)
+
+
+def random_scenes(seed, n):
+    """-> ([(scene, seed of its scene_points)], draws rejected): n random trees of Prim, Rigid, Scale, Comb, Round and Shell.  A
+    draw is kept when the REFERENCE ALONE says its comparison decides something -- at most 2 % of the scene's points left out of
+    the material comparison and every bound below 1e-4, the two conditions the hand-written scenes are held to -- and redrawn
+    otherwise.  Every fourth scene is drawn until it needs all 8 value slots, the one after it until it opens 4 frames."""
+    rng = np.random.default_rng(seed)
+    kept, rejected = [], 0
+    while len(kept) < n:
+        i = len(kept)
+        for _ in range(400):
+            scene = _random_tree(rng, MAX_VALUES, MAX_FRAMES, int(rng.integers(2, 20)))
+            v, f = stack_needs(scene)
+            if (i % 4 == 0 and v < MAX_VALUES) or (i % 4 == 1 and f < MAX_FRAMES):
+                continue                               # (not a rejected draw: a draw of another shape than the one asked for)
+            break
+        else:
+            raise AssertionError("no tree of the shape asked for")
+        points_seed = 1000 * int(seed) % 100003 + i
+        _, bound, _, decided = evaluate(scene, scene_points(points_seed))
+        if 1.0 - decided.mean() <= 0.02 and np.isfinite(bound).all() and bound.max() < 1e-4:
+            kept.append((scene, points_seed))
+        else:
+            rejected += 1
+    return kept, rejected
+
+
 SCENE_SEEDS = {"sixteen": 21, "every_opcode": 22, "nested_frames": 23, "smooth_blobs": 24, "rotated_solids": 25, "scaled_shells": 26}
 SCENE_GRID = (12, 10, 8)
 

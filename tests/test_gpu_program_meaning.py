@@ -41,16 +41,32 @@ def test_primitives_at_points_of_known_distance_on_the_device(pkg, PM):
 
 @pytest.mark.timeout(900)
 def test_scenes_on_the_device_equal_the_float64_reference_within_its_bound(pkg, PM):
+    scenes_on_the_device(pkg, PM, [(name, scene, G.SCENE_SEEDS[name]) for name, scene in G.scenes().items()])
+
+
+@pytest.mark.timeout(900)
+def test_random_scenes_on_the_device_equal_the_float64_reference_within_its_bound(pkg, PM):
+    """program_geometry.random_scenes -- trees nested up to the stack limits, kept or redrawn by the reference alone -- through the
+    sampler and the 24 x 10 x 6 fill, as the hand-written scenes are."""
+    kept, rejected = G.random_scenes(G.RANDOM_SCENES_SEED, 8)
+    print(f"random scenes: {len(kept)} kept, {rejected} draws rejected")
+    assert len(kept) >= 8 and rejected <= len(kept)
+    assert max(G.stack_needs(s)[0] for s, _ in kept) == G.MAX_VALUES and max(G.stack_needs(s)[1] for s, _ in kept) == G.MAX_FRAMES
+    scenes_on_the_device(pkg, PM, [(f"random_scenes({G.RANDOM_SCENES_SEED})[{i}]", scene, seed) for i, (scene, seed) in enumerate(kept)])
+
+
+def scenes_on_the_device(pkg, PM, cases):
+    """cases: [(name, scene, seed of its scene_points)]"""
     K = pkg._capi
     W, H, D = FILL_GRID
     lo, hi = (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)
     grid = pkg.make_grid(FILL_GRID, lo, hi)
     vox = R.grid_positions(FILL_GRID, lo, hi)
-    for name, scene in G.scenes().items():
+    for name, scene, points_seed in cases:
         builder = G.emit(scene, PM)
         prog = builder.build()
         # the sampler, on the scene's points: distance within the bound, material where the reference decides it
-        pts = G.scene_points(G.SCENE_SEEDS[name])
+        pts = G.scene_points(points_seed)
         ref, bound, mat, decided = G.evaluate(scene, pts)
         assert 1.0 - decided.mean() <= 0.02 and bound.max() < 1e-4, name
         got = prog.sample_points(torch.from_numpy(pts).cuda()).cpu().numpy()

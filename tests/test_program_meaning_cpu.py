@@ -87,6 +87,39 @@ def test_scenes_equal_the_float64_reference_within_its_bound(pkg, PM, V):
     assert {op for op, _ in G.emit(scenes["every_opcode"], PM).ops} == set(range(1, 19))   # ... and one of them does alone
 
 
+def test_random_scenes_equal_the_float64_reference_within_its_bound(pkg, PM, V):
+    """Random trees nested up to the stack limits (program_geometry.random_scenes), emitted through the public helpers like the
+    hand-written scenes: the host mirror's distance within the reference's derived bound, the material equal where the reference
+    decides it.  The generator keeps a draw by the reference alone; more than half rejected would mean its operand ranges are
+    wrong, not the interpreter."""
+    kept, rejected = G.random_scenes(G.RANDOM_SCENES_SEED, 12)
+    print(f"random scenes: {len(kept)} kept, {rejected} draws rejected")
+    assert len(kept) == 12 and rejected <= len(kept)                  # at most half of all draws
+    used, values_max, frames_max, worst = set(), 0, 0, 0.0
+    for i, (scene, points_seed) in enumerate(kept):
+        builder = G.emit(scene, PM)
+        what = f"random_scenes({G.RANDOM_SCENES_SEED})[{i}]: " + " ".join(f"{op}{a}" for op, a in builder.ops)
+        used |= {op for op, _ in builder.ops}
+        v, f = G.stack_needs(scene)
+        values_max, frames_max = max(values_max, v), max(frames_max, f)
+        pts = G.scene_points(points_seed)
+        ref, bound, mat, decided = G.evaluate(scene, pts)
+        excluded = 1.0 - decided.mean()
+        assert excluded <= 0.02 and np.isfinite(bound).all() and bound.max() < 1e-4, (what, excluded, bound.max())
+        got = host_records(V, builder, pts)
+        err = np.abs(got[:, 0].astype(np.float64) - ref)
+        ratio = float((err / np.maximum(bound, 1e-300)).max())
+        worst = max(worst, ratio)
+        print(f"random scene {i}: {len(builder.ops)} instructions, stacks {v} values / {f} frames, material left out at "
+              f"{100 * excluded:.2f} %, max error / bound = {ratio:.3f}")
+        k = int(np.argmax(err - bound))
+        assert (err <= bound).all(), (what, pts[k], got[k, 0], ref[k], bound[k])
+        wrong = np.flatnonzero(decided & (got[:, 1:].astype(np.float64) != mat).any(axis=1))
+        assert wrong.size == 0, (what, pts[wrong[:4]], got[wrong[:4]], mat[wrong[:4]])
+    assert worst < 1.0 and values_max == G.MAX_VALUES and frames_max == G.MAX_FRAMES
+    assert used == set(range(1, 19))
+
+
 def test_the_example_model_is_the_scene_that_describes_it(pkg, PM):
     """example_sixteen() instruction for instruction from its description: translation(), rigid_inverse(), push_scale() and the
     operand order of every builder method, as the emitter uses them."""

@@ -16,10 +16,14 @@ while [ $(date +%s) -lt $END ]; do
         tests/test_gpu_points.py::test_random_points_match_oracle \
         tests/test_gpu_mesh_extract.py::test_randomised_extractions_match_numpy_restatement \
         tests/test_gpu_sharded_march.py::test_randomised_slabs_and_cameras \
+        tests/test_gpu_program_fuzz.py::test_the_samplers_equal_the_restatement_on_both_corpora \
+        tests/test_gpu_program_fuzz.py::test_the_dense_fill_equals_packing_the_restated_samples_on_the_corpus \
+        tests/test_gpu_program_fuzz.py::test_the_direct_march_equals_its_restatement_on_the_corpus \
+        tests/test_gpu_program_fuzz.py::test_marching_cubes_and_dual_contouring_equal_their_restatements_on_the_corpus \
         tests/test_gpu_ingest.py::test_randomised_ingest_loads_and_edits > gpurun_out/soak_last.log 2>&1; then
     echo "SOAK FAILURE at seed $SEED"; grep -v "^RCCL\|^HIP \|^ROCm\|^Host\|^Libr" gpurun_out/soak_last.log | tail -40
     exit 1
   fi
   N=$((N + 1))
 done
-echo "soak: $N rounds of 8 sweeps x 40 trials passed, seeds $(( SEED - N + 1 ))..$SEED"
+echo "soak: $N rounds of 12 sweeps x 40 trials passed, seeds $(( SEED - N + 1 ))..$SEED"
