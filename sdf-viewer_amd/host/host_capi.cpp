@@ -11,6 +11,7 @@
 
 #include <sstream>
 
+#include "load_state.hpp"
 #include "loading_manager.hpp"
 #include "mesh.hpp"
 #include "program_sdf.hpp"
@@ -46,6 +47,80 @@ void sdfvh_lm_pass_point(void* m, size_t k, size_t out[3]) {
     out[0] = p[0]; out[1] = p[1]; out[2] = p[2];
 }
 uint32_t sdfvh_prev_power_of_2(uint32_t x) { return prev_power_of_2(x); }
+
+// ---- LoadState (load_state.hpp), with the facts a material would hold: events in, decisions out ----
+struct LoadStateHandle {
+    bool undefined_rows = false, pairs_valid = false, interleaved = false;
+    uint32_t defined_step = 0;
+    LoadState state{GridFacts{undefined_rows, defined_step, pairs_valid, interleaved}};
+};
+static LoadStateHandle& L(void* h) { return *static_cast<LoadStateHandle*>(h); }
+void* sdfvh_ls_new(int volume, int interleaved) {
+    auto* h = new LoadStateHandle();
+    h->interleaved = interleaved != 0;
+    h->state.created_virgin(volume != 0);
+    return h;
+}
+void sdfvh_ls_free(void* h) { delete static_cast<LoadStateHandle*>(h); }
+// device_sdf < 0: no device form, else a parameter block that differs with the value; program: a snapshot's address (0: none)
+int sdfvh_ls_observe(void* h, int device_sdf, size_t program, int change_reported) {
+    std::optional<DeviceSDF> dev;
+    if (device_sdf >= 0) {
+        dev.emplace();
+        memset(&*dev, 0, sizeof(*dev));
+        memcpy(&dev->params, &device_sdf, sizeof(device_sdf));
+    }
+    return L(h).state.observe(dev, reinterpret_cast<const sdfv_program*>(program), change_reported != 0) ? 1 : 0;
+}
+// returns materialize_first
+int sdfvh_ls_next_pass(void* h, int has_box, int program, uint32_t* flags) {
+    const LoadState::Pass p = L(h).state.next_pass(has_box != 0, program != 0);
+    *flags = p.flags;
+    return p.materialize_first ? 1 : 0;
+}
+static sdfv_grid grid_of(const uint32_t dims[3], const float bb[6]) {
+    sdfv_grid g{};
+    for (int i = 0; i < 3; ++i) g.dims[i] = dims[i], g.bb_min[i] = bb[i], g.bb_max[i] = bb[3 + i];
+    return g;
+}
+static BoundingBox box_of(const float b[6]) { return {Vec3{b[0], b[1], b[2]}, Vec3{b[3], b[4], b[5]}}; }
+// box may be NULL
+int sdfvh_ls_dense_shortcut(void* h, size_t iterations, size_t step, double budget_seconds, const uint32_t dims[3],
+                            const float bb[6], const float* box) {
+    const auto budget = std::chrono::nanoseconds((long long)(budget_seconds * 1e9));
+    return L(h).state.dense_shortcut(iterations, step, budget, grid_of(dims, bb), box ? std::optional<BoundingBox>(box_of(box)) : std::nullopt);
+}
+int sdfvh_box_covers_grid(const uint32_t dims[3], const float bb[6], const float box[6]) {
+    return LoadState::box_covers_grid(grid_of(dims, bb), box_of(box));
+}
+// 0 pass_ran(arg = step) | 1 dense_fill_ran | 2 records_packed | 3 materialised (what SDFViewerMaterial::materialize notes) |
+// 4 manager_finished | 5 device_route_entered | 6 mirror_rebuilt | 7 mirror_lost | 8 pairs_built
+void sdfvh_ls_event(void* h, int event, size_t arg) {
+    LoadState& s = L(h).state;
+    switch (event) {
+        case 0: s.pass_ran(arg); break;
+        case 1: s.dense_fill_ran(); break;
+        case 2: s.records_packed(); break;
+        case 3: L(h).undefined_rows = false; break;
+        case 4: s.manager_finished(); break;
+        case 5: s.device_route_entered(); break;
+        case 6: s.mirror_rebuilt(); break;
+        case 7: s.mirror_lost(); break;
+        case 8: s.pairs_built(); break;
+    }
+}
+// the facts the material holds: 1 pairs valid | 2 undefined rows; defined_step separately
+uint32_t sdfvh_ls_material(void* h, uint32_t* defined_step) {
+    *defined_step = L(h).defined_step;
+    return (L(h).pairs_valid ? 1u : 0u) | (L(h).undefined_rows ? 2u : 0u);
+}
+// 0 valid | 1 all AIR | 2 read back from the device
+int sdfvh_ls_mirror(void* h) { return (int)L(h).state.mirror(); }
+int sdfvh_ls_commit_derives_pairs(void* h, int loaded) { return L(h).state.commit_derives_pairs(loaded != 0) ? 1 : 0; }
+float sdfvh_voxel_coordinate(float index, uint32_t dim, float lo, float hi) { return voxel_coordinate(index, dim, lo, hi); }
+size_t sdfvh_next_run_length(double time_left, double per_voxel, double growth_cap, size_t capacity) {
+    return next_run_length(time_left, per_voxel, growth_cap, capacity);
+}
 
 // ---- SDFDemo (handle = shared_ptr<SDFSurface>*) ----
 void* sdfvh_demo_new(int argc, const char* const* argv, char* err, size_t err_len) {

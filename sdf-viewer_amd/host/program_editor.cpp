@@ -148,9 +148,7 @@ int through_editor(void* user, F&& body) {
 }
 void ecb_bounding_box(void* user, float out[6]) {
     through_editor(user, [&](EditableProgramSDF& sdf) {
-        const BoundingBox bb = sdf.bounding_box();
-        out[0] = bb[0].x; out[1] = bb[0].y; out[2] = bb[0].z;
-        out[3] = bb[1].x; out[4] = bb[1].y; out[5] = bb[1].z;
+        box_floats(sdf.bounding_box(), out);
     });
 }
 int ecb_sample_batch(void* user, const float* p, size_t n, int distance_only, sdfv_sample* out) {
@@ -167,11 +165,7 @@ uint32_t ecb_sample_concurrency(void* user) {
 int ecb_changed(void* user, float out[6]) {
     int some = 0;
     through_editor(user, [&](EditableProgramSDF& sdf) {
-        if (const auto b = sdf.changed()) {
-            out[0] = (*b)[0].x; out[1] = (*b)[0].y; out[2] = (*b)[0].z;
-            out[3] = (*b)[1].x; out[4] = (*b)[1].y; out[5] = (*b)[1].z;
-            some = 1;
-        }
+        some = box_floats(sdf.changed(), out) ? 1 : 0;
     });
     return some;
 }

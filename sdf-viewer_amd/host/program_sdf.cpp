@@ -42,9 +42,7 @@ int through_program_sdf(void* user, F&& body) {
 }
 void cb_bounding_box(void* user, float out[6]) {
     through_program_sdf(user, [&](const ProgramSDF& sdf) {
-        const BoundingBox bb = sdf.bounding_box();
-        out[0] = bb[0].x; out[1] = bb[0].y; out[2] = bb[0].z;
-        out[3] = bb[1].x; out[4] = bb[1].y; out[5] = bb[1].z;
+        box_floats(sdf.bounding_box(), out);
     });
 }
 int cb_sample_batch(void* user, const float* p, size_t n, int distance_only, sdfv_sample* out) {

@@ -156,4 +156,12 @@ class SDFSurface {
 // merge_bounding_boxes, defaults.rs:59-72
 BoundingBox merge_bounding_boxes(const BoundingBox& a, const BoundingBox& b);
 
+// A box as the six floats the C interfaces take (min.xyz max.xyz): `out`, or NULL without a box.
+inline const float* box_floats(const std::optional<BoundingBox>& box, float out[6]) {
+    if (!box) return nullptr;
+    out[0] = (*box)[0].x; out[1] = (*box)[0].y; out[2] = (*box)[0].z;
+    out[3] = (*box)[1].x; out[4] = (*box)[1].y; out[5] = (*box)[1].z;
+    return out;
+}
+
 }  // namespace sdfviewer

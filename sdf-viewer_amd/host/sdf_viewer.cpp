@@ -1,11 +1,13 @@
-// sdf_viewer.cpp -- see sdf_viewer.hpp.
+// sdf_viewer.cpp -- see sdf_viewer.hpp.  Of SDFViewer::update's three routes this file holds the entry and the WHOLE-PASS route
+// (the demo tree, an SDF program that opted in): a LoadingManager pass is one launch, a load that fits the call one dense fill.
+// What a launch may assume about the grid is LoadState's to say (load_state.hpp).
 #include "sdf_viewer.hpp"
 
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
 #include <cstdio>
-#include <cstring>
+#include <exception>
 
 namespace sdfviewer {
 
@@ -141,22 +143,21 @@ std::unique_ptr<SDFViewer> SDFViewer::new_voxels(std::array<size_t, 3> voxels, c
     if (!v->material.tex0->ok() || !v->material.tex1->ok()) return nullptr;
     // The reference fills both textures with [AIR_DIST; 4] here (:76-77).  This grid is VIRGIN instead: that state is
     // recorded, not written -- the first update() overwrites every byte of it anyway (36 B/voxel the load never pays for).
-    v->material.undefined_rows = true;
-    v->material.defined_step = 0;
     // The compact distance volume (tex0.r, 4 B/voxel) lives next to the textures from the start and every fill keeps
     // it in sync: passes read it for update_required instead of tex0's 16-byte texels, commit() has nothing to derive.
     v->material.dist = std::make_shared<DeviceBuffer>(v->material.tex0->bytes() / 4);
-    v->dist_synced_ = v->material.dist->ok();
-    if (!v->dist_synced_) v->material.dist.reset();  // out of memory: march tex0.r in place, passes read tex0
+    const bool volume = v->material.dist->ok();
+    if (!volume) v->material.dist.reset();  // out of memory: march tex0.r in place, passes read tex0
+    v->load_.created_virgin(volume);
     // Beyond the last-level cache the march gathers fastest from the y-interleaved volume (sdfv_march_volume_advice): the
     // fills and passes of THIS viewer write the volume in that layout from the start, so a load ends with the march's volume
     // in place and commit() builds nothing (512^3: 0.70 + 0.20 ms -> 0.70).  Smaller cubic grids keep the plain volume and
     // let commit() derive the pair volume from it.
-    if (v->dist_synced_ && layout == VolumeLayout::Auto) {
+    if (volume && layout == VolumeLayout::Auto) {
         const sdfv_grid g = v->grid();
         uint32_t kind = SDFV_MARCH_VOLUME_NONE;
         if (sdfv_march_volume_advice(&g, &kind) == 0 && kind == SDFV_MARCH_VOLUME_INTERLEAVED) v->material.dist_interleaved = true;
-    } else if (v->dist_synced_ && layout == VolumeLayout::Interleaved) {
+    } else if (volume && layout == VolumeLayout::Interleaved) {
         if (voxels[1] & 1) return nullptr;  // rows are paired
         v->material.dist_interleaved = true;
     }
@@ -173,39 +174,26 @@ sdfv_grid SDFViewer::grid() const {
     return g;
 }
 
+// update(): observe the SDF, renew the manager for a pending box, pick the route.  The whole-pass route below asks LoadState
+// (load_state.hpp) what every launch may assume; the rules are stated there.
 size_t SDFViewer::update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time) {
     error_.clear();  // last_error() describes THIS call
     visited_before_throw_ = 0;
     // Check whether the SDF self-reports updates.  (:130-141)
-    bool just_changed_box = false;
-    // the passes of ONE load share one SDF and one set of parameters: a different device SDF (or parameter block) than the
-    // one the load began with, or any reported change, ends it
-    if (const auto dev_now = sdf.device_sdf()) {
-        if (!load_sdf_ || memcmp(&*load_sdf_, &*dev_now, sizeof(*dev_now)) != 0) {
-            if (!fresh_) same_load_ = false;
-            load_sdf_ = *dev_now;
-        }
-    }
-    // ... and so does another snapshot of a program that is loaded by whole passes (an edit is a new sdfv_program)
+    const auto dev_now = sdf.device_sdf();
     const sdfv_program* prog = sdf.takes_whole_passes() ? sdf.device_program() : nullptr;
-    if (prog != load_program_) {
-        if (!fresh_ && (prog || load_program_)) same_load_ = false;
-        load_program_ = prog;
-    }
-    if (auto new_box = sdf.changed()) {
-        same_load_ = false;
+    const auto new_box = sdf.changed();
+    load_.observe(dev_now, prog, new_box.has_value());
+    if (new_box) {
         changed_box = changed_box ? merge_bounding_boxes(*changed_box, *new_box) : *new_box;
         changed_box_while_loading = loading_mgr.len() > 0 || changed_box_while_loading;
-        just_changed_box = true;
     }
     // Another full (3-pass) manager while changes are pending and the manager is idle.  (:146-156)
-    if (changed_box) {
-        if (loading_mgr.len() == 0) {
-            loading_mgr = LoadingManager(loading_mgr.limits, 3);
-            if (!just_changed_box) {
-                if (!changed_box_while_loading) changed_box.reset();
-                changed_box_while_loading = false;
-            }
+    if (changed_box && loading_mgr.len() == 0) {
+        loading_mgr = LoadingManager(loading_mgr.limits, 3);
+        if (!new_box) {
+            if (!changed_box_while_loading) changed_box.reset();
+            changed_box_while_loading = false;
         }
     }
 
@@ -214,79 +202,38 @@ size_t SDFViewer::update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_tim
     if (dev) prog = nullptr;  // (the demo's device form comes first, as in sdfv_surface)
     if (!dev && !prog && sdf.has_device_sampler()) return update_device(sdf, max_delta_time);  // sampled by the caller's kernel
     if (!dev && !prog) return update_host(sdf, max_delta_time);  // any `impl SDFSurface`: sampled on the host, packed on the device
-    host_mirror_valid_ = false;  // (whatever runs below rewrites tex0.r on the device)
+    load_.device_route_entered();
     const sdfv_grid g = grid();
-    // From here on a pass is one launch: the demo tree (dev) or an SDF program that opted in (prog, SDFSurface::takes_whole_passes)
-    // as the SDF of the same loop.  A program pass never takes a virgin grid: the initial state is written first.
-    auto run_pass = [&](uint32_t step, const float* box_ptr, float* dist, uint32_t flags) {
-        return prog ? sdfv_program_grid_pass(prog, &g, step, box_ptr, tex0_device(), tex1_device(), dist, flags, stream)
-                    : sdfv_fill_grid_pass_ex(&dev->params, dev->sdf_id, &g, step, box_ptr, tex0_device(), tex1_device(), dist, flags, stream);
+    float* const dist = load_.has_volume() ? material.dist->f32() : nullptr;  // every fill keeps it in sync (+4 B/voxel)
+    float box[6];
+    const float* box_ptr = box_floats(changed_box, box);
+    // From here on a unit of work is one launch over the demo tree (dev) or over an SDF program that opted in (prog,
+    // SDFSurface::takes_whole_passes).  The two differ in their entry points only: the pass and the dense fill.
+    auto run_pass = [&](uint32_t step) {
+        const LoadState::Pass pass = load_.next_pass(changed_box.has_value(), prog != nullptr);
+        if (pass.materialize_first && !materialize_grid()) return false;
+        const int rc = prog ? sdfv_program_grid_pass(prog, &g, step, box_ptr, tex0_device(), tex1_device(), dist, pass.flags, stream)
+                            : sdfv_fill_grid_pass_ex(&dev->params, dev->sdf_id, &g, step, box_ptr, tex0_device(), tex1_device(), dist,
+                                                     pass.flags, stream);
+        if (rc != 0) error_ = sdfv_last_error();
+        return rc == 0;
+    };
+    auto run_dense = [&] {
+        // The demo's dense entry point carries no layout.  Over an interleaved volume the same launch goes through its pass entry
+        // point: a step-1 pass in which update_required holds everywhere (a virgin / fresh grid, or a box that covers it) IS the
+        // dense fused fill.
+        if (!prog && load_.layout_flag()) return run_pass(1u);
+        const int rc = prog ? sdfv_program_fill_grid_commit(prog, &g, tex0_device(), tex1_device(), dist, load_.layout_flag(), stream)
+                            : sdfv_fill_grid_commit(&dev->params, dev->sdf_id, &g, tex0_device(), tex1_device(), dist, stream);
+        if (rc != 0) error_ = sdfv_last_error();
+        return rc == 0;
     };
     const auto start_time = std::chrono::steady_clock::now();
-    // Fresh grid, nothing pending, and a budget that lets every pass be enqueued in this call anyway (a pass is
-    // one asynchronous launch): the state all passes converge to is the dense fill, which moves 32 B/voxel once
-    // instead of re-reading and partially rewriting the grid once per pass.  No intermediate state is observable
-    // inside one update() call; the LoadingManager is advanced exactly as the passes would have advanced it.
-    // The same holds for a re-sampling whose changed box contains every voxel of the grid (the demo SDF reports its
-    // whole bounding box on any parameter edit, demo/mod.rs:135-144): inside the box update_required is true for
-    // every visited voxel, so the passes' common final state is again the dense fill.  "Contains every voxel" is
-    // decided on the voxels' own coordinates (first and last index per axis, same arithmetic as the kernels).
-    auto box_covers_grid = [&]() {
-        if (!changed_box) return false;
-        const float lo[3] = {(*changed_box)[0].x, (*changed_box)[0].y, (*changed_box)[0].z};
-        const float hi[3] = {(*changed_box)[1].x, (*changed_box)[1].y, (*changed_box)[1].z};
-        for (int i = 0; i < 3; ++i) {
-            const float dm1 = (float)g.dims[i] - 1.0f, size = g.bb_max[i] - g.bb_min[i];
-            float first = 0.0f / dm1;  // scene/sdf/mod.rs:179-182, three separately rounded steps
-            first = first * size;
-            first = first + g.bb_min[i];
-            float last = ((float)g.dims[i] - 1.0f) / dm1;
-            last = last * size;
-            last = last + g.bb_min[i];
-            if (!(first >= lo[i] && first <= hi[i] && last >= lo[i] && last <= hi[i])) return false;  // NaN: no
-        }
-        return true;
-    };
-    const bool all_passes_fit = loading_mgr.total_iterations() == 0 && loading_mgr.step_size() != 0 &&
-                                max_delta_time >= std::chrono::milliseconds(1);
-    if (all_passes_fit && ((fresh_ && !changed_box) || box_covers_grid())) {
-        // The fill writes the distance volume in the same pass (+4 B/voxel instead of a second pass over tex0).
-        float* dist_out = dist_synced_ ? material.dist->f32() : nullptr;
-        int rc;
-        if (prog) {
-            rc = sdfv_program_fill_grid_commit(prog, &g, tex0_device(), tex1_device(), dist_out,
-                                               dist_out && material.dist_interleaved ? SDFV_PASS_VOLUME_INTERLEAVED : 0u, stream);
-        } else if (dist_out && material.dist_interleaved) {
-            // the same dense launch through the pass entry point, which carries the volume's layout: a step-1 pass in which
-            // update_required holds everywhere (a virgin / fresh grid, or a box that covers it) IS the dense fused fill
-            float box[6];
-            const float* box_ptr = nullptr;
-            uint32_t flags = SDFV_PASS_VOLUME_INTERLEAVED;
-            if (changed_box) {
-                box[0] = (*changed_box)[0].x; box[1] = (*changed_box)[0].y; box[2] = (*changed_box)[0].z;
-                box[3] = (*changed_box)[1].x; box[4] = (*changed_box)[1].y; box[5] = (*changed_box)[1].z;
-                box_ptr = box;
-                if (material.materialize(stream) != 0) {  // (a box test is no virgin pass; the dense launch overwrites it all anyway)
-                    error_ = sdfv_last_error();
-                    return 0;
-                }
-            } else {
-                flags |= (material.undefined_rows ? SDFV_PASS_VIRGIN_GRID : SDFV_PASS_FRESH_GRID) | SDFV_PASS_SAME_LOAD;
-            }
-            rc = sdfv_fill_grid_pass_ex(&dev->params, dev->sdf_id, &g, 1u, box_ptr, tex0_device(), tex1_device(), dist_out, flags, stream);
-        } else {
-            rc = sdfv_fill_grid_commit(&dev->params, dev->sdf_id, &g, tex0_device(), tex1_device(), dist_out, stream);
-        }
-        if (rc != 0) {
-            error_ = sdfv_last_error();
-            return 0;
-        }
-        fresh_ = false;
-        material.undefined_rows = false;  // the dense fill wrote every voxel
-        material.pairs_valid = false;
-        while (loading_mgr.step_size() != 0) loading_mgr.finish_pass();
-        loaded_once_ = true;
-        publish_lod();
+    if (load_.dense_shortcut(loading_mgr.total_iterations(), loading_mgr.step_size(), max_delta_time, g, changed_box)) {
+        if (!run_dense()) return 0;
+        load_.dense_fill_ran();
+        // the LoadingManager is advanced exactly as the passes would have advanced it
+        while (loading_mgr.step_size() != 0) finish_step(kRestOfPass);
         return loading_mgr.total_iterations() - start_iter;
     }
     bool first = true;
@@ -295,50 +242,36 @@ size_t SDFViewer::update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_tim
         first = false;
         const size_t step = loading_mgr.step_size();
         if (step == 0) break;  // No more work to do!
-        float box[6];
-        const float* box_ptr = nullptr;
-        if (changed_box) {
-            box[0] = (*changed_box)[0].x; box[1] = (*changed_box)[0].y; box[2] = (*changed_box)[0].z;
-            box[3] = (*changed_box)[1].x; box[4] = (*changed_box)[1].y; box[5] = (*changed_box)[1].z;
-            box_ptr = box;
-        }
-        // What this LoadingManager knows about the grid (sdfv_fill_grid_pass_ex): the first pass of a load over the grid
-        // new_voxels initialised sees AIR_DIST everywhere; the later passes of that load revisit only what ITS earlier
-        // passes wrote (same SDF, same parameters -- a changed box or another SDF ends the load, see set below).
-        // A virgin grid (nothing written by new_voxels): the same passes, told so -- they write the rows they visit whole
-        // and read nothing.  A pass that must READ the grid (a changed box, another SDF mid-load) first gets the initial
-        // state written into the rows no pass has reached.
-        uint32_t flags = 0;
-        if (prog && material.materialize(stream) != 0) {  // (a program pass takes no virgin grid: it becomes a fresh one)
-            error_ = sdfv_last_error();
-            break;
-        }
-        if (same_load_ && !changed_box)
-            flags = material.undefined_rows ? (SDFV_PASS_VIRGIN_GRID | SDFV_PASS_SAME_LOAD)
-                                            : ((fresh_ ? SDFV_PASS_FRESH_GRID : 0u) | SDFV_PASS_SAME_LOAD);
-        else if (material.materialize(stream) != 0) {
-            error_ = sdfv_last_error();
-            break;
-        }
-        if (dist_synced_ && material.dist_interleaved) flags |= SDFV_PASS_VOLUME_INTERLEAVED;
-        // the manager the reference runs once a changed box has been worked off (:146-156, no box any more) scans a loaded grid
-        // and finds nothing: say so (a hint: the scan streams the volume past the caches)
-        if (loaded_once_ && !changed_box && flags == (flags & SDFV_PASS_VOLUME_INTERLEAVED)) flags |= SDFV_PASS_EXPECT_NOOP;
-        if (run_pass((uint32_t)step, box_ptr, dist_synced_ ? material.dist->f32() : nullptr, flags) != 0) {
-            error_ = sdfv_last_error();
-            break;
-        }
-        fresh_ = false;
-        if (material.undefined_rows) {  // (only virgin passes get here with the flag still set)
-            material.defined_step = (uint32_t)step;
-            if (step == 1) material.undefined_rows = false;
-        }
-        material.pairs_valid = false;
-        loading_mgr.finish_pass();
-        if (loading_mgr.step_size() == 0) loaded_once_ = true;
-        publish_lod();
+        if (!run_pass((uint32_t)step)) break;
+        load_.pass_ran(step);
+        finish_step(kRestOfPass);
     }
     return loading_mgr.total_iterations() - start_iter;
+}
+
+bool SDFViewer::materialize_grid() {
+    if (material.materialize(stream) == 0) return true;
+    error_ = sdfv_last_error();
+    return false;
+}
+
+void SDFViewer::finish_step(size_t points) {
+    if (points == kRestOfPass) loading_mgr.finish_pass();
+    else loading_mgr.advance(points);
+    if (loading_mgr.step_size() == 0) load_.manager_finished();
+    publish_lod();
+}
+
+void SDFViewer::rethrow_described(const char* what, size_t start_iter) {
+    visited_before_throw_ = loading_mgr.total_iterations() - start_iter;
+    error_ = what;
+    try {
+        throw;
+    } catch (const std::exception& e) {
+        error_ += std::string(": ") + e.what();
+    } catch (...) {
+    }
+    throw;
 }
 
 // The reference's textures change only in commit(), together with the LOD uniform (scene/sdf/mod.rs:220-239).  Here a
@@ -359,8 +292,8 @@ void SDFViewer::commit() {
     // creation) the march reads tex0.r in place.
     // What a commit of the fully loaded grid does derive is the pair volume: the frames that follow (the reference renders
     // one per repaint) march over it.  12 B/voxel of traffic -- against the reference's re-upload of 32 B/voxel over PCIe.
-    if (dist_synced_ && material.dist_interleaved) return;  // the fills wrote the march's volume themselves
-    if (dist_synced_ && loading_mgr.step_size() == 0 && !material.pairs_valid) {
+    // (an interleaved volume is the march's volume: the fills wrote it themselves)
+    if (load_.commit_derives_pairs(loading_mgr.step_size() == 0)) {
         const sdfv_grid g = grid();
         if (!material.pairs && !material.no_march_volume) {
             // beyond the last-level cache the interleaved volume (4 B/voxel) marches faster than the pair volume (8)
@@ -376,7 +309,7 @@ void SDFViewer::commit() {
                        : material.pairs_interleaved ? sdfv_commit_interleaved(&g, material.dist->f32(), material.pairs->f32(), stream)
                                                     : sdfv_commit_pairs(&g, material.dist->f32(), material.pairs->f32(), stream);
         if (rc == 0)
-            material.pairs_valid = true;
+            load_.pairs_built();
         else {
             material.pairs.reset();  // out of memory: the march keeps reading the distance volume ...
             material.no_march_volume = true;  // ... and later commits do not retry the allocation

@@ -12,14 +12,18 @@
 //   - SDFViewerMaterial::render() is the fragment shader over every pixel (sdfv_raymarch);
 //   - new_voxels() allocates and writes NOTHING ("virgin" grid): the reference's initial state [AIR_DIST; 4] is only recorded.
 //     A load that runs all its passes never pays for it (the dense fill, or the step-1 pass, writes every byte); the passes
-//     before it write the rows they visit whole (SDFV_PASS_VIRGIN_GRID) and whatever READS the whole grid in between -- a
-//     frame at an intermediate LOD, download(), a pass with a changed box -- first writes AIR into the rows no pass reached.
+//     before it write the rows they visit whole and whatever READS the whole grid in between -- a frame at an intermediate
+//     LOD, download(), a pass with a changed box -- first writes AIR into the rows no pass reached;
+//   - what the viewer knows about its grid between calls, and what that allows the next pass to assume, is LoadState's
+//     (load_state.hpp): the three routes of update() and commit() report events to it and ask it for decisions.
 #pragma once
 
+#include <algorithm>
 #include <chrono>
 #include <memory>
 #include <optional>
 
+#include "load_state.hpp"
 #include "loading_manager.hpp"
 #include "sdf_surface.hpp"
 
@@ -73,7 +77,7 @@ struct SDFViewerMaterial {
                                          // level cache the fill writes the volume the march gathers fastest from ITSELF -- commit()
                                          // then has nothing to build, render() passes it as the descriptor's `ilv`
     std::shared_ptr<DeviceBuffer> pairs;  // y-pair volume (sdfv_commit_pairs) of the LOADED grid, or null / stale
-    bool pairs_valid = false;             // pairs mirrors dist: set by SDFViewer::commit, cleared by every fill
+    bool pairs_valid = false;             // pairs mirrors dist: set by SDFViewer::commit, cleared by every fill (LoadState)
     bool no_march_volume = false;         // sdfv_march_volume_advice said neither pays for this grid: commit() builds none
     bool pairs_interleaved = false;       // `pairs` holds the y-interleaved volume instead (sdfv_march_volume_advice)
     // Virgin load: the rows of the textures (and of dist) no pass has written yet hold undefined bytes, logically [AIR_DIST; 4].
@@ -91,6 +95,14 @@ struct SDFViewerMaterial {
     // Draws the volume: one ray per pixel of camera's viewport; rgba_device holds W*H*4 floats.
     int render(const Camera& camera, float* rgba_device, sdfv_march_aux* aux_device, void* stream) const;
 };
+
+// The length of a record route's next run: sized to end within half of the time that is left even if every voxel of it costs
+// `per_voxel` seconds, at most `growth_cap` (a multiple of the run before) and `capacity`, at least one voxel.
+inline size_t next_run_length(double time_left, double per_voxel, double growth_cap, size_t capacity) {
+    double want = per_voxel > 0.0 ? 0.5 * time_left / per_voxel : (double)capacity;
+    want = std::min(want, growth_cap);
+    return want < 1.0 ? 1 : (size_t)std::min(want, (double)capacity);
+}
 
 class SDFViewer {
    public:
@@ -122,6 +134,7 @@ class SDFViewer {
     // sample_batch_device samples them and sdfv_pack_samples packs them; the budget is checked between runs, each timed to its
     // end (none is left in flight) and sized as on the ingest path, for the largest cost per sample seen.  A sample_batch_device that throws: that run is dropped (nothing of it reaches the textures), the
     // exception propagates and a later call samples the run again.
+    // What each route may assume about the grid, and what it leaves known: LoadState (load_state.hpp).
     size_t update(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time);
     // Ingest path knobs: host threads (0 = what the SDF allows, at most the machine's), records per transfer buffer (0 = 16 Ki
     // per thread, between 64 Ki and 4 Mi: a run must outlast the fork/join of its workers by far; 32 B of pinned memory each).
@@ -157,27 +170,25 @@ class SDFViewer {
     SDFViewer(std::array<size_t, 3> voxels, const BoundingBox& bb, size_t passes);
     size_t update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time);  // sdf_viewer_ingest.cpp
     size_t update_device(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time);  // sdf_viewer_device.cpp
+    // ---- what the three routes share ----
+    // Writes the initial state into the rows no pass has reached; false (and error_) when that failed.
+    bool materialize_grid();
+    // The end of a unit of work: hands out `points` of the current pass (kRestOfPass: all that is left of it), notes a
+    // LoadingManager that ran to its end and publishes the LOD with the data.
+    static constexpr size_t kRestOfPass = ~(size_t)0;
+    void finish_step(size_t points);
+    // Inside a catch block, for the caller's code that threw: error_ = `what` (+ ": " + the exception's text), the iterations
+    // this call had consumed before the run that failed, and the exception goes on.
+    [[noreturn]] void rethrow_described(const char* what, size_t start_iter);
+    // (shared_ptr: the two types are complete only in their route's file)
     struct DeviceRuns;  // the device-sampled path's buffers (points, indices, samples, count, scan scratch)
-    struct DeviceRunsDeleter {
-        void operator()(DeviceRuns* p) const;
-    };
-    struct Ingest;  // pinned / device transfer buffers, the host mirror of tex0.r, the worker threads
-    struct IngestDeleter {
-        void operator()(Ingest* p) const;
-    };
-    std::unique_ptr<Ingest, IngestDeleter> ingest_;  // created by the first update() with a host-only SDF
-    bool host_mirror_valid_ = false;  // ingest_'s mirror equals tex0.r (cleared by every fill the device path runs)
+    struct Ingest;      // pinned / device transfer buffers, the host mirror of tex0.r, the worker threads
+    std::shared_ptr<Ingest> ingest_;  // created by the first update() with a host-only SDF
     std::string error_;
-    bool fresh_ = true;  // both textures still hold new_voxels' AIR_DIST everywhere
-    bool loaded_once_ = false;  // some LoadingManager has run to its end over this grid: a later pass without a box finds nothing to do
-    bool same_load_ = true;  // every pass so far belongs to ONE load: the SDF and parameters of load_sdf_, no change reported
-    std::optional<DeviceSDF> load_sdf_;  // what that load samples
-    bool dist_synced_ = false;  // material.dist exists and mirrors tex0.r (kept so by every fill)
+    LoadState load_{GridFacts{material.undefined_rows, material.defined_step, material.pairs_valid, material.dist_interleaved}};
     std::shared_ptr<DeviceBuffer> block_;  // owns tex0 and tex1 when they share one allocation
-    // (added last: the members above keep their offsets)
-    std::unique_ptr<DeviceRuns, DeviceRunsDeleter> device_runs_;  // created by the first update() with a device sampler
+    std::shared_ptr<DeviceRuns> device_runs_;  // created by the first update() with a device sampler
     size_t visited_before_throw_ = 0;
-    const sdfv_program* load_program_ = nullptr;  // the snapshot the load samples, for an SDF that takes whole passes
 };
 
 }  // namespace sdfviewer

@@ -13,7 +13,8 @@
 // sized to end within half of what is left even if every voxel of it needs a sample -- at the scan's cost per point plus the
 // LARGEST cost per sample seen for this SDF (a run of cheap skips says nothing about the next one), growing by at most 16x,
 // as the ingest path sizes its runs.  The voxels a call visits are a prefix of the LoadingManager's remaining order, and the
-// return value counts them, as in the reference.
+// return value counts them, as in the reference.  What the route leaves known about the grid: LoadState (load_state.hpp),
+// device_route_entered and records_packed.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -58,8 +59,6 @@ struct SDFViewer::DeviceRuns {
     }
 };
 
-void SDFViewer::DeviceRunsDeleter::operator()(DeviceRuns* p) const { delete p; }
-
 size_t SDFViewer::update_device(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time) {
     const size_t start_iter = loading_mgr.total_iterations();
     const auto start_time = std::chrono::steady_clock::now();
@@ -71,38 +70,26 @@ size_t SDFViewer::update_device(SDFSurface& sdf, std::chrono::nanoseconds max_de
         error_ = "device-sampled grids are addressed with 32-bit voxel indices: at most 2^32 voxels";
         return 0;
     }
-    if (!dist_synced_) {
+    if (!load_.has_volume()) {
         error_ = "device-sampled loads read the distance volume, which this viewer could not allocate";
         return 0;
     }
     hipStream_t st = (hipStream_t)stream;
-    host_mirror_valid_ = false;  // (the ingest path's mirror of tex0.r no longer holds what the device holds)
+    load_.device_route_entered();
     // update_required reads the distance volume: the rows of a virgin grid no pass has written must hold AIR first
-    if (material.materialize(stream) != 0) {
-        error_ = sdfv_last_error();
-        return 0;
-    }
-    if (!device_runs_) device_runs_.reset(new DeviceRuns());
+    if (!materialize_grid()) return 0;
+    if (!device_runs_) device_runs_ = std::make_shared<DeviceRuns>();
     DeviceRuns& dr = *device_runs_;
     if (!dr.reserve(ingest_capacity ? ingest_capacity : std::min(n_voxels, kDefaultCapacity))) {
         error_ = "cannot allocate the device-sampled load's buffers";
         return 0;
     }
-    // this load is no longer one the device path can make assumptions about (SDFV_PASS_SAME_LOAD / FRESH_GRID)
-    same_load_ = false;
-    load_sdf_.reset();
-    fresh_ = false;
-    material.pairs_valid = false;
+    load_.records_packed();
 
-    const uint32_t flags = material.dist_interleaved ? SDFV_PASS_VOLUME_INTERLEAVED : 0u;
+    const uint32_t flags = load_.layout_flag();
     float* dist = material.dist->f32();
     float box[6];
-    const float* box_ptr = nullptr;
-    if (changed_box) {
-        box[0] = (*changed_box)[0].x; box[1] = (*changed_box)[0].y; box[2] = (*changed_box)[0].z;
-        box[3] = (*changed_box)[1].x; box[4] = (*changed_box)[1].y; box[5] = (*changed_box)[1].z;
-        box_ptr = box;
-    }
+    const float* box_ptr = box_floats(changed_box, box);
     if (dr.cost_sdf != &sdf) {
         dr.cost_sdf = &sdf;
         dr.sample_cost = 0.0;
@@ -139,15 +126,7 @@ size_t SDFViewer::update_device(SDFSurface& sdf, std::chrono::nanoseconds max_de
                 sdf.sample_batch_device(dr.points.f32(), count, samples, stream);  // :193, the caller's kernel
             } catch (...) {
                 // nothing of this run has reached the textures and the LoadingManager stays where it is
-                visited_before_throw_ = loading_mgr.total_iterations() - start_iter;
-                error_ = "device sampling: the SDF's sample_batch_device failed";
-                try {
-                    throw;
-                } catch (const std::exception& e) {
-                    error_ += std::string(": ") + e.what();
-                } catch (...) {
-                }
-                throw;
+                rethrow_described("device sampling: the SDF's sample_batch_device failed", start_iter);
             }
             if (sdfv_pack_samples(&g, 0, static_cast<const uint32_t*>(dr.indices.get()), samples, count, tex0_device(),
                                   tex1_device(), dist, flags, stream) != 0) {
@@ -160,10 +139,8 @@ size_t SDFViewer::update_device(SDFSurface& sdf, std::chrono::nanoseconds max_de
                 break;
             }
         }
-        loading_mgr.advance(n);
-        if (loading_mgr.step_size() == 0) loaded_once_ = true;
-        publish_lod();
-        // ---- the next run: sized to end within half of the budget that is left even if every voxel of it needs a sample ----
+        finish_step(n);
+        // ---- the next run (next_run_length): every voxel of it may need a sample ----
         const auto now = std::chrono::steady_clock::now();
         const double scan_cost = std::chrono::duration<double>(scanned - run_start).count() / (double)n;
         if (count >= kCostSamples)
@@ -171,9 +148,7 @@ size_t SDFViewer::update_device(SDFSurface& sdf, std::chrono::nanoseconds max_de
         const double per_voxel = std::max(std::chrono::duration<double>(now - run_start).count() / (double)n,
                                           scan_cost + dr.sample_cost);
         const double left = std::chrono::duration<double>(max_delta_time - (now - start_time)).count();
-        double want = per_voxel > 0.0 ? 0.5 * left / per_voxel : (double)dr.capacity;
-        want = std::min(want, 16.0 * (double)n);
-        run_len = want < 1.0 ? 1 : (size_t)std::min(want, (double)dr.capacity);
+        run_len = next_run_length(left, per_voxel, 16.0 * (double)n, dr.capacity);
     }
     return loading_mgr.total_iterations() - start_iter;
 }

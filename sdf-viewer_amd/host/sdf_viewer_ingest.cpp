@@ -8,7 +8,8 @@
 //     threads (sample_concurrency() of them; the calling thread is worker 0, and the only one for an SDF that does not
 //     say it tolerates more), each writing the records it produces into its own stretch of a PINNED buffer;
 //   - update_required reads a host mirror of tex0.r (4 B/voxel, kept by this file; rebuilt from the device's distance
-//     volume when the device path has written the grid in between) -- never the device textures;
+//     volume when the device path has written the grid in between: LoadState::mirror, load_state.hpp) -- never the device
+//     textures;
 //   - a finished run is copied to the device (async, the viewer's stream) and sdfv_pack_samples packs it into tex0 / tex1 /
 //     the distance volume while the workers sample the next run into the other buffer;
 //   - the time budget: the first run is one voxel per worker ("performs at least one update"), every further run is sized to
@@ -95,8 +96,6 @@ struct SDFViewer::Ingest {
     }
 };
 
-void SDFViewer::IngestDeleter::operator()(Ingest* p) const { delete p; }
-
 size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delta_time) {
     const size_t start_iter = loading_mgr.total_iterations();
     const auto start_time = std::chrono::steady_clock::now();
@@ -110,7 +109,7 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
         return 0;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (!ingest_) ingest_.reset(new Ingest());
+    if (!ingest_) ingest_ = std::make_shared<Ingest>();
     Ingest& in = *ingest_;
     unsigned threads = sdf.sample_concurrency();
     const unsigned hw = WorkerPool::usable_cpus();
@@ -122,21 +121,18 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
     }
     // A record only rewrites tex0 and tex1.rgb of ITS voxel: everything else must already hold what the reference's
     // textures hold (new_voxels' [AIR_DIST; 4] wherever nothing has been sampled, and tex1.a everywhere).
-    if (material.materialize(st) != 0) {
-        error_ = sdfv_last_error();
-        return 0;
-    }
+    if (!materialize_grid()) return 0;
     const float air = sdfv_air_dist();
     // ---- the host mirror of tex0.r ----
-    if (!host_mirror_valid_) {
-        if (fresh_) {  // nothing has been sampled into this grid yet
+    if (const LoadState::Mirror mirror = load_.mirror(); mirror != LoadState::Mirror::Valid) {
+        if (mirror == LoadState::Mirror::AllAir) {
             in.mirror.assign(n_voxels, air);
         } else {  // the device path wrote it: fetch the 4 B/voxel volume (or derive one from tex0)
             in.mirror.resize(n_voxels);
             DeviceBuffer derived;
             const float* src = nullptr;
             bool ilv = false;
-            if (dist_synced_) {
+            if (load_.has_volume()) {
                 src = material.dist->f32();
                 ilv = material.dist_interleaved;
             } else {
@@ -162,30 +158,17 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
                 for (size_t row = 0; row < H * D; ++row)
                     for (size_t x = 0; x < W; ++x) in.mirror[row * W + x] = tmp[((row >> 1) * W + x) * 2 + (row & 1)];
         }
-        host_mirror_valid_ = true;
+        load_.mirror_rebuilt();
     }
-    // ---- voxel coordinates: idx as f32 / (dim - 1) * size + min, three separately rounded steps (scene/sdf/mod.rs:179-182) ----
-    const float bbmin[3] = {bounding_box[0].x, bounding_box[0].y, bounding_box[0].z};
-    const float bbmax[3] = {bounding_box[1].x, bounding_box[1].y, bounding_box[1].z};
+    // ---- voxel coordinates, per axis ----
     for (int a = 0; a < 3; ++a) {
         in.coords[a].resize(g.dims[a]);
-        const float dm1 = (float)g.dims[a] - 1.0f, size = bbmax[a] - bbmin[a];
-        for (uint32_t i = 0; i < g.dims[a]; ++i) {
-            float p = (float)i;
-            p = p / dm1;
-            p = p * size;
-            p = p + bbmin[a];
-            in.coords[a][i] = p;
-        }
+        for (uint32_t i = 0; i < g.dims[a]; ++i) in.coords[a][i] = voxel_coordinate((float)i, g.dims[a], g.bb_min[a], g.bb_max[a]);
     }
-    // this load is no longer one the device path can make assumptions about (SDFV_PASS_SAME_LOAD / FRESH_GRID)
-    same_load_ = false;
-    load_sdf_.reset();
-    fresh_ = false;
-    material.pairs_valid = false;
+    load_.records_packed();
 
-    const uint32_t pack_flags = (dist_synced_ && material.dist_interleaved) ? SDFV_PASS_VOLUME_INTERLEAVED : 0u;
-    float* dist_dev = dist_synced_ ? material.dist->f32() : nullptr;
+    const uint32_t pack_flags = load_.layout_flag();
+    float* dist_dev = load_.has_volume() ? material.dist->f32() : nullptr;
     const bool has_box = changed_box.has_value();
     const BoundingBox box = has_box ? *changed_box : BoundingBox{};
     if (has_box) in.journal.resize(in.capacity);  // (a run without a box only samples voxels whose mirror entry is AIR)
@@ -233,7 +216,7 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
         if (failed) {
             (void)hipGetLastError();
             error_ = std::string("ingest: ") + sdfv_last_error();
-            host_mirror_valid_ = false;  // the mirror holds samples the device never received
+            load_.mirror_lost();  // the mirror holds samples the device never received
         } else if (total && hipEventRecord(b.done, st) == hipSuccess) {
             b.in_flight = true;
         }
@@ -337,16 +320,8 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
         } catch (...) {
             // sample() threw on this thread (WorkerPool::run returns only once the other workers are done): this run is not
             // shipped and the LoadingManager stays where it is, but the mirror already holds some of its samples
-            host_mirror_valid_ = false;
-            visited_before_throw_ = loading_mgr.total_iterations() - start_iter;
-            error_ = "ingest: the SDF's sample() threw";
-            try {
-                throw;
-            } catch (const std::exception& e) {
-                error_ += std::string(": ") + e.what();
-            } catch (...) {
-            }
-            throw;
+            load_.mirror_lost();
+            rethrow_described("ingest: the SDF's sample() threw", start_iter);
         }
         ingest_stats.sample += std::chrono::duration<double>(std::chrono::steady_clock::now() - run_start).count();
         // ---- the run's complete prefix: every stretch up to the first one whose worker met the deadline, and what that one visited
@@ -367,9 +342,7 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
         }
         ship(run);
         if (failed) break;
-        loading_mgr.advance(visited);
-        if (loading_mgr.step_size() == 0) loaded_once_ = true;
-        publish_lod();
+        finish_step(visited);
         ingest_stats.runs += 1;
         ingest_stats.visited += visited;
         // ---- the next run: sized to end within half of the budget that is left even if every voxel of it needs a sample, at
@@ -381,9 +354,7 @@ size_t SDFViewer::update_host(SDFSurface& sdf, std::chrono::nanoseconds max_delt
         if (least >= kGather) in.record_cost = std::max(in.record_cost, record_cost);  // (long enough to be more than overhead)
         const double per_voxel = std::max({took / (double)visited, record_cost / threads, in.record_cost / threads});
         const double left = std::chrono::duration<double>(max_delta_time - (now - start_time)).count();
-        double want = per_voxel > 0.0 ? 0.5 * left / per_voxel : (double)in.capacity;
-        want = std::min(want, 8.0 * (double)n);
-        run_len = want < 1.0 ? 1 : (size_t)std::min(want, (double)in.capacity);
+        run_len = next_run_length(left, per_voxel, 8.0 * (double)n, in.capacity);
     }
     return loading_mgr.total_iterations() - start_iter;
 }

@@ -185,6 +185,33 @@ int wrap_viewer(std::unique_ptr<SDFViewer> v, sdfv_viewer** out) {
     *out = h;
     return SDFV_OK;
 }
+
+// One SDFViewer::update over the SDF that `pick` returns (or NULL and the error code it refuses with): *visited on success
+// and on a throw, last_error() as SDFV_ERR_HIP.
+template <class Pick>
+int update_viewer(sdfv_viewer* v, uint64_t budget_ns, size_t* visited, Pick&& pick) {
+    if (visited) *visited = 0;
+    if (!v || !v->v) return SDFV_ERR_INVALID_ARGUMENT;
+    return guarded(v->err, [&] {
+        int rc = SDFV_OK;
+        SDFSurface* sdf = pick(rc);
+        if (!sdf) return rc;
+        const auto budget = std::chrono::nanoseconds((long long)std::min<uint64_t>(budget_ns, (uint64_t)INT64_MAX));
+        size_t n = 0;
+        try {
+            n = v->v->update(*sdf, budget);
+        } catch (...) {
+            if (visited) *visited = v->v->visited_before_throw();  // (the runs packed before the one that failed)
+            throw;
+        }
+        if (visited) *visited = n;
+        if (v->v->last_error()[0]) {
+            v->err = v->v->last_error();
+            return (int)SDFV_ERR_HIP;
+        }
+        return (int)SDFV_OK;
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -218,42 +245,19 @@ int sdfv_viewer_new_voxels(const uint32_t dims[3], const float bb[6], uint32_t l
 }
 
 int sdfv_viewer_update(sdfv_viewer* v, const sdfv_surface* surface, uint64_t budget_ns, size_t* visited) {
-    if (visited) *visited = 0;
-    if (!v || !v->v) return SDFV_ERR_INVALID_ARGUMENT;
-    return guarded(v->err, [&] {
-        if (int rc = check_surface(surface, v->err)) return rc;
-        auto sdf = adapter_for(v->sdf, *surface);
-        const auto budget = std::chrono::nanoseconds((long long)std::min<uint64_t>(budget_ns, (uint64_t)INT64_MAX));
-        size_t n = 0;
-        try {
-            n = v->v->update(*sdf, budget);
-        } catch (...) {
-            if (visited) *visited = v->v->visited_before_throw();  // (the runs packed before the one that failed)
-            throw;
-        }
-        if (visited) *visited = n;
-        if (v->v->last_error()[0]) {
-            v->err = v->v->last_error();
-            return (int)SDFV_ERR_HIP;
-        }
-        return (int)SDFV_OK;
+    return update_viewer(v, budget_ns, visited, [&](int& rc) -> SDFSurface* {
+        rc = check_surface(surface, v->err);
+        return rc ? nullptr : adapter_for(v->sdf, *surface).get();  // (v->sdf keeps it alive)
     });
 }
 
 // include/sdfprogram.h: the same call with the editor's own class as the SDF, which opts in to whole passes
 int sdfv_viewer_update_program(sdfv_viewer* v, sdfv_program_editor* e, uint64_t budget_ns, size_t* visited) {
-    if (visited) *visited = 0;
-    if (!v || !v->v) return SDFV_ERR_INVALID_ARGUMENT;
-    return guarded(v->err, [&] {
-        if (!e || !e->sdf) return v->err = "editor is NULL", (int)SDFV_ERR_INVALID_ARGUMENT;
-        const auto budget = std::chrono::nanoseconds((long long)std::min<uint64_t>(budget_ns, (uint64_t)INT64_MAX));
-        const size_t n = v->v->update(*e->sdf, budget);
-        if (visited) *visited = n;
-        if (v->v->last_error()[0]) {
-            v->err = v->v->last_error();
-            return (int)SDFV_ERR_HIP;
-        }
-        return (int)SDFV_OK;
+    return update_viewer(v, budget_ns, visited, [&](int& rc) -> SDFSurface* {
+        if (e && e->sdf) return e->sdf.get();
+        v->err = "editor is NULL";
+        rc = SDFV_ERR_INVALID_ARGUMENT;
+        return nullptr;
     });
 }
 

@@ -22,6 +22,15 @@ for name, res, args in [
     ("sdfvh_lm_total_iterations", SZ, [C.c_void_p]), ("sdfvh_lm_passes_left", SZ, [C.c_void_p]),
     ("sdfvh_lm_step_size", SZ, [C.c_void_p]), ("sdfvh_lm_finish_pass", SZ, [C.c_void_p]),
     ("sdfvh_prev_power_of_2", C.c_uint32, [C.c_uint32]),
+    ("sdfvh_ls_new", C.c_void_p, [C.c_int, C.c_int]), ("sdfvh_ls_free", None, [C.c_void_p]),
+    ("sdfvh_ls_observe", C.c_int, [C.c_void_p, C.c_int, SZ, C.c_int]),
+    ("sdfvh_ls_next_pass", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
+    ("sdfvh_ls_dense_shortcut", C.c_int, [C.c_void_p, SZ, SZ, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("sdfvh_box_covers_grid", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("sdfvh_ls_event", None, [C.c_void_p, C.c_int, SZ]), ("sdfvh_ls_material", C.c_uint32, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("sdfvh_ls_mirror", C.c_int, [C.c_void_p]), ("sdfvh_ls_commit_derives_pairs", C.c_int, [C.c_void_p, C.c_int]),
+    ("sdfvh_voxel_coordinate", C.c_float, [C.c_float, C.c_uint32, C.c_float, C.c_float]),
+    ("sdfvh_next_run_length", SZ, [C.c_double, C.c_double, C.c_double, SZ]),
     ("sdfvh_demo_new", C.c_void_p, [C.c_int, C.POINTER(C.c_char_p), C.c_char_p, SZ]),
     ("sdfvh_provider_load", C.c_void_p, [C.c_char_p, C.c_char_p, SZ]),
     ("sdfvh_sdf_sample_concurrency", C.c_uint, [C.c_void_p]),
@@ -108,6 +117,69 @@ class LoadingManager:
         out = (SZ * 3)()
         H.sdfvh_lm_pass_point(self.h, k, out)
         return tuple(out)
+
+
+def _grid_args(dims, bb, box=None):
+    d = np.asarray(dims, np.uint32)
+    b = np.asarray(bb, np.float32).reshape(6)
+    x = None if box is None else np.asarray(box, np.float32).reshape(6)
+    return d, b, x
+
+
+def box_covers_grid(dims, bb, box):
+    d, b, x = _grid_args(dims, bb, box)
+    return bool(H.sdfvh_box_covers_grid(d.ctypes.data, b.ctypes.data, x.ctypes.data))
+
+
+def voxel_coordinate(index, dim, lo, hi):
+    return H.sdfvh_voxel_coordinate(float(index), dim, float(lo), float(hi))
+
+
+def next_run_length(time_left, per_voxel, growth_cap, capacity):
+    return H.sdfvh_next_run_length(time_left, per_voxel, growth_cap, capacity)
+
+
+class LoadState:
+    """sdfviewer::LoadState (host/load_state.hpp) over the facts a virgin material holds: events in, decisions out."""
+    EVENTS = {"pass_ran": 0, "dense_fill_ran": 1, "records_packed": 2, "materialized": 3, "manager_finished": 4,
+              "device_route_entered": 5, "mirror_rebuilt": 6, "mirror_lost": 7, "pairs_built": 8}
+
+    def __init__(self, volume=True, interleaved=False):
+        self.h = H.sdfvh_ls_new(int(volume), int(interleaved))
+
+    def __del__(self):
+        if H is not None:
+            H.sdfvh_ls_free(self.h)
+
+    def observe(self, device_sdf=None, program=0, change_reported=False):
+        """device_sdf: None or a number naming a parameter block; program: 0 or a number naming a snapshot.  -> same load?"""
+        return bool(H.sdfvh_ls_observe(self.h, -1 if device_sdf is None else device_sdf, program, int(change_reported)))
+
+    def next_pass(self, has_box=False, program=False):
+        """-> (materialize_first, flags)"""
+        flags = C.c_uint32()
+        first = H.sdfvh_ls_next_pass(self.h, int(has_box), int(program), C.byref(flags))
+        return bool(first), flags.value
+
+    def dense_shortcut(self, iterations, step, budget_seconds, dims, bb, box=None):
+        d, b, x = _grid_args(dims, bb, box)
+        return bool(H.sdfvh_ls_dense_shortcut(self.h, iterations, step, budget_seconds, d.ctypes.data, b.ctypes.data,
+                                              None if x is None else x.ctypes.data))
+
+    def event(self, name, arg=0):
+        H.sdfvh_ls_event(self.h, self.EVENTS[name], arg)
+
+    def material(self):
+        """The facts the material holds."""
+        step = C.c_uint32()
+        bits = H.sdfvh_ls_material(self.h, C.byref(step))
+        return {"pairs_valid": bool(bits & 1), "undefined_rows": bool(bits & 2), "defined_step": step.value}
+
+    def mirror(self):
+        return ["valid", "all_air", "read_back"][H.sdfvh_ls_mirror(self.h)]
+
+    def commit_derives_pairs(self, loaded):
+        return bool(H.sdfvh_ls_commit_derives_pairs(self.h, int(loaded)))
 
 
 class SDF:
