@@ -643,6 +643,50 @@ int sdfv_program_mesh_postproc(const sdfv_program *p, sdfv_vertex *vertices, siz
 /* host buffer, evaluated ON THE DEVICE, like the other *_host calls */
 int sdfv_program_mesh_postproc_host(const sdfv_program *p, sdfv_vertex *vertices_host, size_t n);
 
+/* ---- Meshing a sampled lattice (the reference's `mesh` command meshes ANY SDFSurface: all it asks is sample and normal) ----
+ * The same extractor for an SDF the library cannot evaluate: a provider library, an application's own SDFSurface, a surface the
+ * caller samples with a kernel of its own.  The caller fills the lattice with distances, the library does the rest, and the
+ * normals come from that same lattice.  Arithmetic as above: IEEE f32, every step rounded on its own, nothing contracted.
+ *   lattice    cells = max_voxels_per_axis on every axis; dist: DEVICE, (cells + 1)^3 floats, x fastest
+ *              (index (k * (cells + 1) + j) * (cells + 1) + i); point (i, j, k) lies at p = (float)i / (float)cells * bb_size + bb_min
+ *              per axis, bb_size = bb_max - bb_min: the lattice of sdfv_mesh_extract.
+ *   inside, vertices, triangles, dual contouring   sdfv_program_mesh_extract's, step for step, with normal(p) below in the SDF's
+ *              place.  For the same lattice values marching cubes' positions and indices are its positions and indices, bit for
+ *              bit, and so are dual contouring's Hermite positions, active cells and indices (its solved positions follow the
+ *              normals).  Colour and material fields are 0.
+ *   normal(p)  with D the lattice:
+ *     1. per axis a:  u = (p_a - bb_min_a) / bb_size_a * (float)cells;  u = u > 0 ? u : 0;  u = u < (float)cells ? u : (float)cells
+ *     2. c = min((uint)floor(u), cells - 1),  f = u - (float)c                       the cell and the place within it
+ *     3. component a of the gradient at lattice point q:  hi = min(q_a + 1, cells), lo = max(q_a, 1) - 1,
+ *        g_a(q) = (D[q with q_a = hi] - D[q with q_a = lo]) / (float)(hi - lo)        central, one-sided at the border
+ *     4. each component interpolated over the 8 corners of cell c with lerp(a, b, t) = a + t * (b - a): along x with f_x (four
+ *        times), then along y with f_y (twice), then along z with f_z
+ *     5. G_a = g_a * ((float)cells / bb_size_a)
+ *     6. s = (G_x*G_x + G_y*G_y) + G_z*G_z
+ *     7. !(s > 0): n = (0, 0, 0) -- the mesher's "unset" normal, which Mesh::postproc fills from the SDF (meshers/mesh.rs:25-27)
+ *        and dual contouring's solve leaves out (w > 0.5f fails)
+ *     8. otherwise inv = 1 / sqrt(s), n = G * inv per component
+ *     Central differences of the samples rather than the reference's four tetrahedral taps on an interpolant: on a sphere of
+ *     radius 0.6 in [-1, 1]^3 the worst angle to the true normal is 1.71, 0.98 and 0.23 degrees at 5, 12 and 24 cells, against
+ *     8.5, 3.8 and 2.0 for the taps at half a cell on the trilinear interpolant.
+ * Limits (1 <= cells <= 1024; marching cubes or SDFV_MESHER_DUAL_CONTOURING_PARTICLE, "Unsupported algorithm" otherwise),
+ * synchronisation, ownership (sdfv_mesh_free) and the per-thread scratch are sdfv_mesh_extract's.  Argument errors are reported
+ * first; without a device these return SDFV_ERR_NO_DEVICE and write nothing. */
+/* points[3 * t ..] = the position of lattice point first + t in flat order, t in [0, n): so that a surface sampled on the
+ * device can be fed chunk by chunk.  first + n <= (cells + 1)^3.  points: DEVICE, n x 3 floats. */
+int sdfv_lattice_points(const float bb_min[3], const float bb_max[3], uint32_t cells, size_t first, size_t n, float *points,
+                        void *stream);
+/* dist[i] = samples[i].distance for i in [0, n).  samples: DEVICE, n records of 28 bytes; dist: DEVICE, n floats. */
+int sdfv_lattice_from_samples(const sdfv_sample *samples, size_t n, float *dist, void *stream);
+/* Meshers::mesh over the lattice.  dist is read, never written, and must stay as it is until the call returns.  flags: 0. */
+int sdfv_lattice_mesh_extract(const float *dist, const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis,
+                              uint32_t algorithm, uint32_t flags, sdfv_mesh *out, void *stream);
+/* vertices[i].normal = normal(vertices[i].position) for i in [0, n): the three floats of the normal are written and nothing else
+ * of a record.  vertices: DEVICE, n x sdfv_vertex, 4-byte aligned.  Positions outside the box take the border cell's values
+ * (step 1).  Not synchronised. */
+int sdfv_lattice_normals(const float *dist, const float bb_min[3], const float bb_max[3], uint32_t cells, sdfv_vertex *vertices,
+                         size_t n, void *stream);
+
 /* ---- raymarch ----
  * ONE exported entry point, one descriptor: sdfv_raymarch_ex.  The forms earlier ABI versions exported one by one
  * (sdfv_raymarch, _accel, _depth, _pairs, _volumes, _bands) are header-only wrappers at the end of this file that fill the

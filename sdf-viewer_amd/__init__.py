@@ -220,6 +220,45 @@ def mesh_extract(params, max_voxels_per_axis=64, bb_min=(-1.0, -1.0, -1.0), bb_m
     return mesh_tensors(m)
 
 
+def lattice_points(bb, cells, first=0, n=None, stream=None, device="cuda"):
+    """sdfv_lattice_points: the positions of lattice points [first, first + n) of the `cells`-cell lattice over bb = min.xyz +
+    max.xyz, in flat order (x fastest) -> [n, 3] float32.  n None: up to the lattice's end."""
+    if n is None:
+        n = (int(cells) + 1) ** 3 - int(first)
+    out = torch.empty((max(int(n), 0), 3), dtype=torch.float32, device=device)
+    check(lib.sdfv_lattice_points(f3(bb[:3]), f3(bb[3:]), int(cells), int(first), int(n), C.c_void_p(out.data_ptr()),
+                                  _stream_ptr(stream)))
+    return out
+
+
+def lattice_from_samples(samples, stream=None):
+    """sdfv_lattice_from_samples: the distances of [n, 7] sample records -> [n] float32."""
+    assert samples.is_cuda and samples.dtype == torch.float32 and samples.is_contiguous() and samples.shape[-1] == 7
+    out = torch.empty((samples.numel() // 7,), dtype=torch.float32, device=samples.device)
+    check(lib.sdfv_lattice_from_samples(C.c_void_p(samples.data_ptr()), out.numel(), C.c_void_p(out.data_ptr()),
+                                        _stream_ptr(stream)))
+    return out
+
+
+def lattice_mesh_extract(dist, bb, cells, algorithm=0, stream=None):
+    """sdfv_lattice_mesh_extract: Meshers::mesh over a lattice of distances the caller sampled.  dist: (cells + 1)^3 float32 on
+    the device, x fastest; bb = min.xyz + max.xyz.  -> (vertices [n, 12] float32, indices int32), as mesh_extract."""
+    assert dist.numel() == (int(cells) + 1) ** 3, "dist holds (cells + 1)^3 distances"
+    m = _capi.Mesh()
+    check(lib.sdfv_lattice_mesh_extract(_dev_ptr(dist, "dist"), f3(bb[:3]), f3(bb[3:]), int(cells), int(algorithm), 0, C.byref(m),
+                                        _stream_ptr(stream)))
+    return mesh_tensors(m)
+
+
+def lattice_normals(dist, bb, cells, vertices, stream=None):
+    """sdfv_lattice_normals, in place over an [n, 12] vertex tensor: the normal of each position from the lattice."""
+    assert dist.numel() == (int(cells) + 1) ** 3, "dist holds (cells + 1)^3 distances"
+    assert vertices.dim() == 2 and vertices.shape[1] == VERTEX_FLOATS
+    check(lib.sdfv_lattice_normals(_dev_ptr(dist, "dist"), f3(bb[:3]), f3(bb[3:]), int(cells), _dev_ptr(vertices, "vertices"),
+                                   vertices.shape[0], _stream_ptr(stream)))
+    return vertices
+
+
 def mesh_tensors(m):
     """An sdfv_mesh the library has just filled -> (vertices [n, 12] float32, indices [n_indices] int32) as torch tensors of
     their own; the library's copy is freed."""

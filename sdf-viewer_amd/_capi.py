@@ -204,6 +204,14 @@ PROTOTYPES = {
                                             C.c_uint32, C.POINTER(Mesh), C.c_void_p]),
     "sdfv_program_mesh_postproc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sdfv_program_mesh_postproc_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    # meshing a sampled lattice
+    "sdfv_lattice_points": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_size_t, C.c_size_t, C.c_void_p,
+                                      C.c_void_p]),
+    "sdfv_lattice_from_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "sdfv_lattice_mesh_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.POINTER(Mesh), C.c_void_p]),
+    "sdfv_lattice_normals": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
 }
 MESH_WITH_MATERIALS = 1
 MESHER_MARCHING_CUBES = 0

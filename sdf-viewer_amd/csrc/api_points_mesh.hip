@@ -7,6 +7,7 @@
 #include "points_kernels.h"
 #include "program_mesh_kernels.h"
 #include "dual_contour_kernels.h"
+#include "lattice_mesh_kernels.h"
 
 using namespace sdfv;
 
@@ -23,8 +24,9 @@ struct MeshScratch {
 };
 thread_local MeshScratch g_mesh_scratch;  // freed by sdfv_mesh_trim(); a thread that exits without it leaks the block
 
-// Meshers::mesh for any SDF the device can evaluate: the arguments are checked by the caller.  An SDF kind supplies two things:
-// `lattice(g, w, stream)` writes the distances of the lattice points, and `attributes(vertices, n, final, stream)` everything but
+// Meshers::mesh for any kind of SDF: the arguments are checked by the caller.  An SDF kind supplies two things:
+// `lattice(g, w, stream)` writes the distances of the lattice points into w.dist (or points w.dist at distances that exist: a
+// caller's lattice, which no step writes), and `attributes(vertices, n, final, stream)` everything but
 // the position of n vertices whose positions are written.  Counting, the scans, the positions of the crossing edges, the
 // triangles (mesh_kernels.h) and dual contouring's solve and quads (dual_contour_kernels.h) do not depend on the SDF.  `final` is
 // false only for dual contouring's Hermite records: crossing-edge vertices in a temporary, of which the solve reads position and
@@ -206,6 +208,76 @@ int sdfv_program_mesh_extract(const sdfv_program* p, const float bb_min[3], cons
         },
         [&](sdfv_vertex* vertices, size_t n, bool final, hipStream_t st) {  // the materials belong to the output vertices only
             return sdfv::launch_program_vertex_normals(dev_ops, n_ops, vertices, n, materials && final, st);
+        });
+}
+
+// ---- meshing a sampled lattice: the SDF is the caller's, the library sees (cells + 1)^3 distances ----
+namespace {
+int check_lattice(const float* dist, const float bb_min[3], const float bb_max[3]) {
+    if (!dist) return set_error(SDFV_ERR_INVALID_ARGUMENT, "dist is NULL");
+    if (!bb_min || !bb_max) return set_error(SDFV_ERR_INVALID_ARGUMENT, "bounding box is NULL");
+    return check_word_aligned("dist", dist);
+}
+sdfv::MeshGrid lattice_grid(const float bb_min[3], const float bb_max[3], uint32_t cells) {
+    sdfv::MeshGrid g;
+    for (int i = 0; i < 3; ++i) {
+        g.cells[i] = cells;
+        g.bb_min[i] = bb_min[i];
+        g.bb_size[i] = bb_max[i] - bb_min[i];
+    }
+    return g;
+}
+}  // namespace
+
+int sdfv_lattice_points(const float bb_min[3], const float bb_max[3], uint32_t cells, size_t first, size_t n, float* points,
+                        void* stream) {
+    if (!bb_min || !bb_max) return set_error(SDFV_ERR_INVALID_ARGUMENT, "bounding box is NULL");
+    if (int rc = check_mesher(SDFV_MESHER_MARCHING_CUBES, cells)) return rc;
+    const sdfv::MeshGrid g = lattice_grid(bb_min, bb_max, cells);
+    if (first > g.n_points() || n > g.n_points() - first)
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "points [%zu, %zu + %zu) are not all among the lattice's %zu", first, first, n,
+                         g.n_points());
+    if (int rc = check_point_buffers(points, points, n)) return rc;
+    if (int rc = check_word_aligned("points", points)) return rc;
+    if (int rc = need_device()) return rc;
+    SDFV_HIP_RETURN(sdfv::launch_lattice_points(g, (uint32_t)first, (uint32_t)n, points, (hipStream_t)stream));
+}
+
+int sdfv_lattice_from_samples(const sdfv_sample* samples, size_t n, float* dist, void* stream) {
+    if (int rc = check_point_buffers(samples, dist, n)) return rc;
+    if (int rc = check_word_aligned("samples and dist", samples, dist)) return rc;
+    if (int rc = need_device()) return rc;
+    SDFV_HIP_RETURN(sdfv::launch_lattice_from_samples(samples, n, dist, (hipStream_t)stream));
+}
+
+int sdfv_lattice_normals(const float* dist, const float bb_min[3], const float bb_max[3], uint32_t cells, sdfv_vertex* vertices,
+                         size_t n, void* stream) {
+    if (int rc = check_lattice(dist, bb_min, bb_max)) return rc;
+    if (int rc = check_mesher(SDFV_MESHER_MARCHING_CUBES, cells)) return rc;
+    if (int rc = check_point_buffers(vertices, vertices, n)) return rc;
+    if (int rc = check_word_aligned("vertices", vertices)) return rc;
+    if (n > 0xffffffffull) return set_error(SDFV_ERR_INVALID_ARGUMENT, "%zu vertices are too many for one launch", n);
+    if (int rc = need_device()) return rc;
+    SDFV_HIP_RETURN(sdfv::launch_lattice_normals(dist, lattice_grid(bb_min, bb_max, cells), vertices, n, false, (hipStream_t)stream));
+}
+
+int sdfv_lattice_mesh_extract(const float* dist, const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis,
+                              uint32_t algorithm, uint32_t flags, sdfv_mesh* out, void* stream) {
+    if (!out) return set_error(SDFV_ERR_INVALID_ARGUMENT, "out is NULL");
+    memset(out, 0, sizeof(*out));
+    if (int rc = check_lattice(dist, bb_min, bb_max)) return rc;
+    if (int rc = check_mesher(algorithm, max_voxels_per_axis)) return rc;
+    if (flags) return set_error(SDFV_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
+    if (int rc = need_device()) return rc;
+    const sdfv::MeshGrid grid = lattice_grid(bb_min, bb_max, max_voxels_per_axis);
+    return extract_mesh(
+        bb_min, bb_max, max_voxels_per_axis, algorithm, out, (hipStream_t)stream,
+        [&](const sdfv::MeshGrid&, sdfv::MeshWork& w, hipStream_t) {  // read in place: every step takes w.dist as const
+            w.dist = const_cast<float*>(dist);
+            return hipSuccess;
+        },
+        [&](sdfv_vertex* vertices, size_t n, bool final, hipStream_t st) {  // the zero material belongs to the output vertices
+            return sdfv::launch_lattice_normals(dist, grid, vertices, n, final, st);
         });
 }
 

@@ -12,10 +12,12 @@
 // Flag names and defaults are the reference's: CliApp (src/app/cli/mod.rs:10-22: max_voxels_side 64,
 // loading_passes 2) and the demo SDF's flags (src/sdf/demo/cube.rs:15-18, sphere.rs:11-14, demo/mod.rs:26-29).
 //   sdf-viewer-gpu mesh [-o mesh.ply] [-v 64] [marching-cubes] [demo flags after `demo`]
+//   sdf-viewer-gpu mesh [...] url <library.so | file://library.so>
 //
 // `mesh` is the reference's CliMesher (src/sdf/meshers/mod.rs:22-89): -o/--output (default mesh.ply, "-" = stdout,
 // refuses to overwrite), -v/--max-voxels-per-axis (default 64), the mesher subcommand (default marching-cubes); the
-// input is the embedded demo SDF instead of -i <wasm>.  Mesh -> postproc -> serialize_ply, as run_custom_out does.
+// input is the embedded demo SDF, or a provider library under `app`'s URL rules, instead of -i <wasm>.  Mesh -> postproc ->
+// serialize_ply, as run_custom_out does (mesh_any_sdf / postproc_any: the provider is sampled on the host, the device meshes).
 // Where the reference opens a window, this loads the SDF into the two device textures
 // (SDFViewer::from_bb/update/commit), renders the default scene camera (scene/mod.rs:82-95) with the raymarch
 // kernel and writes the frame as a binary PPM.  The log lines follow scene/mod.rs:180-197.
@@ -48,9 +50,22 @@ static int usage(const char* msg) {
             "                                                     program renders after the load has finished, so its frame does not change\n"
             "    sdf-viewer-gpu app [...] url <library.so>      a native SDF provider (include/sdf_provider.h), sampled on the host\n"
             "    sdf-viewer-gpu mesh [-o <mesh.ply|->] [-v <max-voxels-per-axis>] [marching-cubes] [demo [demo flags]]\n"
+            "    sdf-viewer-gpu mesh [...] url <library.so>     the same for a native SDF provider\n"
             "demo flags: -t/--cube-material <brick|normal>  -c/--cube-half-side <f>  -l/--sphere-material <brick|normal>\n"
             "            -s/--sphere-radius <f>  -m/--max-distance-custom-material <f>  -d/--disable-sphere <true|false>\n");
     return msg ? 2 : 0;
+}
+
+// `url <URL>` of both commands: a local provider library (CliSDFProvider::Url's place).  nullptr with the text in *err; *bad_usage
+// tells a URL this program does not take from a library that does not load.
+static std::shared_ptr<SDFSurface> load_url(std::string url, std::string* err, bool* bad_usage) {
+    *bad_usage = url.rfind("http://", 0) == 0 || url.rfind("https://", 0) == 0;
+    if (*bad_usage) {
+        *err = "url: only local provider libraries are supported (no network, no wasm runtime)";
+        return nullptr;
+    }
+    if (url.rfind("file://", 0) == 0) url = url.substr(7);
+    return ProviderSDF::load(url, err);
 }
 
 // CliMesher::run_cli / run_custom_out, src/sdf/meshers/mod.rs:40-89
@@ -59,6 +74,7 @@ static int run_mesh(const std::vector<std::string>& args) {
     MesherConfig cfg;                   // -v default 64, meshers/mod.rs:96-97
     Meshers mesher = Meshers::MarchingCubes;  // Default for Meshers, meshers/mod.rs:130-134
     std::vector<std::string> demo_args;
+    std::string url;
     bool in_demo = false;
     for (size_t i = 1; i < args.size(); ++i) {
         const std::string& a = args[i];
@@ -74,12 +90,24 @@ static int run_mesh(const std::vector<std::string>& args) {
         else if (a == "-v" || a == "--max-voxels-per-axis") cfg.max_voxels_per_axis = strtoul(next("--max-voxels-per-axis").c_str(), nullptr, 10);
         else if (a == "-i" || a == "--input") return usage("-i <wasm>: arbitrary wasm cannot run on the GPU; the input is the embedded demo SDF");
         else if (a == "demo") in_demo = true;
+        else if (a == "url") url = next("url <URL>");
         else if (auto m = mesher_from_name(a)) mesher = *m;
         else return usage(("Found argument '" + a + "' which wasn't expected").c_str());
     }
     std::string err;
-    auto sdf = SDFDemo::from_args(demo_args, &err);
-    if (!sdf) return usage(err.c_str());
+    std::shared_ptr<SDFSurface> sdf;
+    if (!url.empty()) {
+        bool bad_usage = false;
+        sdf = load_url(url, &err, &bad_usage);
+        if (bad_usage) return usage(err.c_str());
+        if (!sdf) {
+            fprintf(stderr, "error: %s\n", err.c_str());
+            return 1;
+        }
+    } else {
+        sdf = SDFDemo::from_args(demo_args, &err);
+        if (!sdf) return usage(err.c_str());
+    }
     if (sdfv_device_count() == 0) {
         fprintf(stderr, "error: no HIP device visible: sdf-viewer-gpu has no CPU path\n");
         return 1;
@@ -91,14 +119,19 @@ static int run_mesh(const std::vector<std::string>& args) {
     }
     fprintf(stderr, "Running the meshing algorithm with Config { max_voxels_per_axis: %zu }...\n", cfg.max_voxels_per_axis);
     const auto t0 = std::chrono::steady_clock::now();
-    auto mesh = mesh_sdf(mesher, *sdf, cfg, &err);
+    auto mesh = mesh_any_sdf(mesher, *sdf, cfg, &err);
     if (!mesh) {
         fprintf(stderr, "error: %s\n", err.c_str());
         return 1;
     }
     fprintf(stderr, "Post-processing the mesh (%zu vertices, %zu triangles)...\n", mesh->vertices.size(), mesh->indices.size() / 3);
-    if (mesh->postproc(*sdf) != 0) {
-        fprintf(stderr, "error: %s\n", sdfv_last_error());
+    try {
+        if (postproc_any(*mesh, *sdf) != 0) {
+            fprintf(stderr, "error: %s\n", sdfv_last_error());
+            return 1;
+        }
+    } catch (const std::exception& e) {
+        fprintf(stderr, "error: the SDF's sample() threw: %s\n", e.what());
         return 1;
     }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -163,10 +196,9 @@ int main(int argc, char** argv) {
     std::string err;
     std::shared_ptr<SDFSurface> sdf;
     if (!url.empty()) {
-        if (url.rfind("http://", 0) == 0 || url.rfind("https://", 0) == 0)
-            return usage("url: only local provider libraries are supported (no network, no wasm runtime)");
-        if (url.rfind("file://", 0) == 0) url = url.substr(7);
-        sdf = ProviderSDF::load(url, &err);
+        bool bad_usage = false;
+        sdf = load_url(url, &err, &bad_usage);
+        if (bad_usage) return usage(err.c_str());
         if (!sdf) {
             fprintf(stderr, "error: %s\n", err.c_str());
             return 1;

@@ -3,8 +3,10 @@
 //   Mesh::postproc                  meshers/mesh.rs:22-33     -> sdfv_mesh_postproc / sdfv_program_mesh_postproc (device)
 //   Mesh::serialize_ply             meshers/mesh.rs:37-129    (ASCII PLY through the un-vendored ply-rs crate)
 //   Config, Meshers, Mesher::mesh   meshers/mod.rs:92-149     -> sdfv_mesh_extract / sdfv_program_mesh_extract (device)
-// Only SDFs with a device form (SDFSurface::device_sdf, or SDFSurface::device_program: an SDF program) can be meshed: there is
-// no CPU path.
+// mesh_sdf / Mesh::postproc serve the SDFs with a device form (SDFSurface::device_sdf, or SDFSurface::device_program: an SDF
+// program); mesh_any_sdf / postproc_any serve every SDFSurface: one without a device form is SAMPLED -- on the host, or by its own
+// kernel -- into a lattice that the device meshes (include/sdfgrid.h, "Meshing a sampled lattice").  The extraction itself has no
+// CPU path.
 #pragma once
 
 #include <cstdint>
@@ -47,6 +49,18 @@ struct Mesh {
 // Mesher::mesh (meshers/mod.rs:136-149).  MarchingCubes and DualContouringParticleBasedMinimization have a device
 // implementation; the other two report "Unsupported algorithm" (isosurface.rs:49).  nullopt on error, text in *err.
 std::optional<Mesh> mesh_sdf(Meshers mesher, const SDFSurface& sdf, const MesherConfig& cfg, std::string* err);
+
+// Mesher::mesh for ANY SDFSurface.  One with a device form goes through mesh_sdf unchanged.  Any other is sampled at the
+// (max_voxels_per_axis + 1)^3 lattice points -- has_device_sampler(): by sample_batch_device, chunk after chunk on one stream;
+// otherwise on the host by sample_batch(..., distance_only = true) on sample_concurrency() threads, z-plane by z-plane, checked
+// with check_samples() and uploaded while the next chunk is sampled -- and the lattice is meshed by sdfv_lattice_mesh_extract:
+// positions and indices as the SDF's own distances give them, normals from the lattice, material fields zero until postproc_any.
+// A sample() that throws ends the call with its text in *err.
+std::optional<Mesh> mesh_any_sdf(Meshers mesher, const SDFSurface& sdf, const MesherConfig& cfg, std::string* err);
+// Mesh::postproc for ANY SDFSurface: the device forms through Mesh::postproc, any other on the host (mesh.rs:22-33), sampled
+// with one sample_batch(..., false); normal(p, nullopt) is asked only where the mesher left |n|^2 < 1e-4.  Whatever the SDF
+// throws passes through.  Returns 0 or the sdfv status.
+int postproc_any(Mesh& mesh, const SDFSurface& sdf);
 
 // f32 Display as Rust prints it (shortest digits that round-trip, never an exponent): what ply-rs writes for floats.
 std::string format_f32(float v);
