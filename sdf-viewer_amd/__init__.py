@@ -105,6 +105,20 @@ def _dev_ptr(t, what):
     return C.c_void_p(t.data_ptr())
 
 
+def _out_tensor(out, shape, dtype, device, what):
+    """The tensor a wrapper writes its result into: `out` when the caller passes one (checked like _dev_ptr checks an input:
+    on the device, contiguous, of the result's type and element count), a fresh allocation otherwise."""
+    shape = tuple(int(d) for d in shape)
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    n = 1
+    for d in shape:
+        n *= d
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == dtype and out.numel() == n):
+        raise TypeError(f"{what} must be a contiguous {str(dtype).replace('torch.', '')} CUDA(HIP) tensor of {n} elements {shape}")
+    return out
+
+
 def grid_init(grid, tex0, tex1, stream=None):
     check(lib.sdfv_grid_init(C.byref(grid), _dev_ptr(tex0, "tex0"), _dev_ptr(tex1, "tex1"), _stream_ptr(stream)))
 
@@ -148,19 +162,20 @@ def pack_samples(grid, samples, tex0, tex1, indices=None, index_base=0, dist=Non
                                 None if dist is None else _dev_ptr(dist, "dist"), int(flags), _stream_ptr(stream)))
 
 
-def sample_points(params, points, distance_only=False, sdf_id=SDF_DEMO, stream=None):
-    """Batched SDFSurface::sample.  points: [n,3] CUDA tensor -> [n,7] (distance, rgb, metallic, roughness, occlusion)."""
+def sample_points(params, points, distance_only=False, sdf_id=SDF_DEMO, stream=None, out=None):
+    """Batched SDFSurface::sample.  points: [n,3] CUDA tensor -> [n,7] (distance, rgb, metallic, roughness, occlusion).
+    out: optional tensor that receives the result (and is returned) instead of a fresh allocation."""
     n = points.shape[0]
-    out = torch.empty((n, 7), dtype=torch.float32, device=points.device)
+    out = _out_tensor(out, (n, 7), torch.float32, points.device, "out")
     check(lib.sdfv_sample_points(C.byref(params), sdf_id, _dev_ptr(points, "points"), n, int(bool(distance_only)),
                                  C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
     return out
 
 
-def normal_points(params, points, eps=None, use_default=False, sdf_id=SDF_DEMO, stream=None):
-    """Batched SDFSurface::normal(p, eps) (eps None -> <= 0 over the ABI, ffi.rs:326)."""
+def normal_points(params, points, eps=None, use_default=False, sdf_id=SDF_DEMO, stream=None, out=None):
+    """Batched SDFSurface::normal(p, eps) (eps None -> <= 0 over the ABI, ffi.rs:326).  out: optional [n, 3] result tensor."""
     n = points.shape[0]
-    out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+    out = _out_tensor(out, (n, 3), torch.float32, points.device, "out")
     check(lib.sdfv_normal_points(C.byref(params), sdf_id, _dev_ptr(points, "points"), n,
                                  float(eps) if eps else 0.0, int(bool(use_default)), C.c_void_p(out.data_ptr()),
                                  _stream_ptr(stream)))
@@ -173,10 +188,11 @@ VERTEX_FLOATS = 12  # sdfv_vertex: position, normal, color, metallic, roughness,
 
 
 def source_sample_scalar(params, unit_points, bb_min=(-1.0, -1.0, -1.0), bb_max=(1.0, 1.0, 1.0), sdf_id=SDF_DEMO,
-                         stream=None):
-    """ScalarSource::sample_scalar over unit-cube points (meshers/isosurface.rs:78-84) -> [n] distances."""
+                         stream=None, out=None):
+    """ScalarSource::sample_scalar over unit-cube points (meshers/isosurface.rs:78-84) -> [n] distances (out: optional result
+    tensor)."""
     n = unit_points.shape[0]
-    out = torch.empty((n,), dtype=torch.float32, device=unit_points.device)
+    out = _out_tensor(out, (n,), torch.float32, unit_points.device, "out")
     check(lib.sdfv_source_sample_scalar(C.byref(params), sdf_id, f3(bb_min), f3(bb_max),
                                         _dev_ptr(unit_points, "unit_points"), n, C.c_void_p(out.data_ptr()),
                                         _stream_ptr(stream)))
@@ -184,10 +200,11 @@ def source_sample_scalar(params, unit_points, bb_min=(-1.0, -1.0, -1.0), bb_max=
 
 
 def source_sample_normal(params, unit_points, bb_min=(-1.0, -1.0, -1.0), bb_max=(1.0, 1.0, 1.0), sdf_id=SDF_DEMO,
-                         stream=None):
-    """HermiteSource::sample_normal over unit-cube points (meshers/isosurface.rs:87-92) -> [n, 3]."""
+                         stream=None, out=None):
+    """HermiteSource::sample_normal over unit-cube points (meshers/isosurface.rs:87-92) -> [n, 3] (out: optional result
+    tensor)."""
     n = unit_points.shape[0]
-    out = torch.empty((n, 3), dtype=torch.float32, device=unit_points.device)
+    out = _out_tensor(out, (n, 3), torch.float32, unit_points.device, "out")
     check(lib.sdfv_source_sample_normal(C.byref(params), sdf_id, f3(bb_min), f3(bb_max),
                                         _dev_ptr(unit_points, "unit_points"), n, C.c_void_p(out.data_ptr()),
                                         _stream_ptr(stream)))
@@ -220,21 +237,21 @@ def mesh_extract(params, max_voxels_per_axis=64, bb_min=(-1.0, -1.0, -1.0), bb_m
     return mesh_tensors(m)
 
 
-def lattice_points(bb, cells, first=0, n=None, stream=None, device="cuda"):
+def lattice_points(bb, cells, first=0, n=None, stream=None, device="cuda", out=None):
     """sdfv_lattice_points: the positions of lattice points [first, first + n) of the `cells`-cell lattice over bb = min.xyz +
-    max.xyz, in flat order (x fastest) -> [n, 3] float32.  n None: up to the lattice's end."""
+    max.xyz, in flat order (x fastest) -> [n, 3] float32.  n None: up to the lattice's end.  out: optional result tensor."""
     if n is None:
         n = (int(cells) + 1) ** 3 - int(first)
-    out = torch.empty((max(int(n), 0), 3), dtype=torch.float32, device=device)
+    out = _out_tensor(out, (max(int(n), 0), 3), torch.float32, device, "out")
     check(lib.sdfv_lattice_points(f3(bb[:3]), f3(bb[3:]), int(cells), int(first), int(n), C.c_void_p(out.data_ptr()),
                                   _stream_ptr(stream)))
     return out
 
 
-def lattice_from_samples(samples, stream=None):
-    """sdfv_lattice_from_samples: the distances of [n, 7] sample records -> [n] float32."""
+def lattice_from_samples(samples, stream=None, out=None):
+    """sdfv_lattice_from_samples: the distances of [n, 7] sample records -> [n] float32 (out: optional result tensor)."""
     assert samples.is_cuda and samples.dtype == torch.float32 and samples.is_contiguous() and samples.shape[-1] == 7
-    out = torch.empty((samples.numel() // 7,), dtype=torch.float32, device=samples.device)
+    out = _out_tensor(out, (samples.numel() // 7,), torch.float32, samples.device, "out")
     check(lib.sdfv_lattice_from_samples(C.c_void_p(samples.data_ptr()), out.numel(), C.c_void_p(out.data_ptr()),
                                         _stream_ptr(stream)))
     return out
@@ -407,7 +424,7 @@ def upload_cameras(cameras, device="cuda"):
 
 
 def raymarch(rp, tex0, tex1, cameras, width, height, y0=0, y1=None, want_aux=False, stream=None, out=None, dist=None,
-             want_depth=False, depth_out=None, pairs=None, ilv=None, bands=None, rgba8=None, f32=True):
+             want_depth=False, depth_out=None, pairs=None, ilv=None, bands=None, rgba8=None, f32=True, aux_out=None):
     """material.frag main() over rows [y0,y1) -- or, bands=(first, step), over the 16-row tile bands first, first + step, ...
     stored one after the other (sdfv_march_desc.band_first / band_step).  Returns rgba [n_cam, rows, W, 4] (+ aux [n_cam, rows, W, 18] words).
     cameras: a Camera, a list of them, or upload_cameras()'s device tensor (any number of cameras).
@@ -415,7 +432,9 @@ def raymarch(rp, tex0, tex1, cameras, width, height, y0=0, y1=None, want_aux=Fal
     (sdfv_march_desc.pairs), `ilv` = the y-interleaved volume (desc.ilv).  want_depth / depth_out: also return the
     gl_FragDepth plane [n_cam, rows, W] (desc.depth); return order: rgba[, depth][, aux].  One export: sdfv_raymarch_ex.
     rgba8: "both" or a uint8 tensor [n_cam, rows, W, 4] -> the 8-bit UNORM plane is written too (desc.rgba8) and returned last;
-    f32=False (or rgba8="only") -> the fp32 plane is NOT written (desc.rgba = NULL: 4 B per pixel stored instead of 16)."""
+    f32=False (or rgba8="only") -> the fp32 plane is NOT written (desc.rgba = NULL: 4 B per pixel stored instead of 16).
+    out / depth_out / aux_out (an int32 tensor of [n_cam, rows, W, 18] words; implies want_aux): the caller's tensors for the
+    planes instead of fresh allocations."""
     if isinstance(cameras, Camera):
         cameras = [cameras]
     y1 = height if y1 is None else y1
@@ -445,8 +464,9 @@ def raymarch(rp, tex0, tex1, cameras, width, height, y0=0, y1=None, want_aux=Fal
         img8 = rgba8 if isinstance(rgba8, torch.Tensor) else torch.empty((n, rows, width, 4), dtype=torch.uint8, device=tex0.device)
         assert img8.dtype == torch.uint8 and img8.is_contiguous() and img8.numel() == n * rows * width * 4
     only8 = (isinstance(rgba8, str) and rgba8 == "only") or (img8 is not None and not f32)
+    want_aux = want_aux or aux_out is not None
     rgba = None if only8 else (out if out is not None else torch.empty((n, rows, width, 4), dtype=torch.float32, device=tex0.device))
-    aux = torch.empty((n, rows, width, AUX_FLOATS), dtype=torch.int32, device=tex0.device) if want_aux else None
+    aux = _out_tensor(aux_out, (n, rows, width, AUX_FLOATS), torch.int32, tex0.device, "aux_out") if want_aux else None
     depth = depth_out
     if depth is None and want_depth:
         depth = torch.empty((n, rows, width), dtype=torch.float32, device=tex0.device)

@@ -190,12 +190,13 @@ class CompiledProgram:
         dt = np.dtype([("op", "<u4"), ("reserved", "<u4", (3,)), ("a", "<f4", (12,))])
         return np.frombuffer(raw, dtype=dt).copy(), tuple(bb)
 
-    def sample_points(self, points, distance_only=False, stream=None):
-        """points: [n, 3] float32 CUDA tensor -> [n, 7] records (distance, r, g, b, metallic, roughness, occlusion)."""
+    def sample_points(self, points, distance_only=False, stream=None, out=None):
+        """points: [n, 3] float32 CUDA tensor -> [n, 7] records (distance, r, g, b, metallic, roughness, occlusion); out: optional
+        tensor that receives them."""
         import torch
-        from . import _dev_ptr, _stream_ptr
+        from . import _dev_ptr, _out_tensor, _stream_ptr
         n = points.shape[0]
-        out = torch.empty((n, 7), dtype=torch.float32, device=points.device)
+        out = _out_tensor(out, (n, 7), torch.float32, points.device, "out")
         check(lib.sdfv_program_sample_points(self.h, _dev_ptr(points, "points") if n else None, n, int(bool(distance_only)),
                                              C.c_void_p(out.data_ptr()) if n else None, _stream_ptr(stream)))
         return out
@@ -220,12 +221,13 @@ class CompiledProgram:
                                             _stream_ptr(stream)))
         return mesh_tensors(m)
 
-    def normal_points(self, points, eps=0.0, stream=None):
-        """SDFSurface::normal(p, eps) of the program (eps <= 0: None): [n, 3] float32 CUDA tensor -> [n, 3]."""
+    def normal_points(self, points, eps=0.0, stream=None, out=None):
+        """SDFSurface::normal(p, eps) of the program (eps <= 0: None): [n, 3] float32 CUDA tensor -> [n, 3] (out: optional result
+        tensor)."""
         import torch
-        from . import _dev_ptr, _stream_ptr
+        from . import _dev_ptr, _out_tensor, _stream_ptr
         n = points.shape[0]
-        out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+        out = _out_tensor(out, (n, 3), torch.float32, points.device, "out")
         check(lib.sdfv_program_normal_points(self.h, _dev_ptr(points, "points") if n else None, n, float(eps),
                                              C.c_void_p(out.data_ptr()) if n else None, _stream_ptr(stream)))
         return out
@@ -273,17 +275,20 @@ class CompiledProgram:
         return d, (arr, rp)
 
     def render(self, cameras, width, height, rp=None, normal_h=0.0, want_aux=False, want_depth=False, rgba8=False, stream=None,
-               y0=0, y1=None):
+               y0=0, y1=None, out=None, aux_out=None, depth_out=None):
         """sdfv_program_raymarch: rows [y0, y1) of n_cameras width x height images sphere-traced directly on the device.
         Returns the colour -- [n, rows, width, 4] float32, or [n, rows, width] uint32-as-int32 packed RGBA8 with rgba8=True -- or a
-        tuple (colour[, aux: [n, rows, width, 18] float32 view of sdfv_march_aux][, depth: [n, rows, width]])."""
+        tuple (colour[, aux: [n, rows, width, 18] float32 view of sdfv_march_aux][, depth: [n, rows, width]]).  out / aux_out /
+        depth_out: the caller's tensors for the colour, aux and depth planes (the latter two imply want_aux / want_depth)."""
         import torch
+        from . import _out_tensor
         d, keep = self.march_desc(cameras, width, height, rp, normal_h, y0, y1)
         shape = (d.n_cameras, d.y1 - d.y0, d.width)
         dev = torch.device("cuda", torch.cuda.current_device())
-        colour = torch.empty(shape if rgba8 else shape + (4,), dtype=torch.int32 if rgba8 else torch.float32, device=dev)
-        aux = torch.empty(shape + (18,), dtype=torch.float32, device=dev) if want_aux else None
-        depth = torch.empty(shape, dtype=torch.float32, device=dev) if want_depth else None
+        want_aux, want_depth = want_aux or aux_out is not None, want_depth or depth_out is not None
+        colour = _out_tensor(out, shape if rgba8 else shape + (4,), torch.int32 if rgba8 else torch.float32, dev, "out")
+        aux = _out_tensor(aux_out, shape + (18,), torch.float32, dev, "aux_out") if want_aux else None
+        depth = _out_tensor(depth_out, shape, torch.float32, dev, "depth_out") if want_depth else None
         if rgba8:
             d.rgba8 = colour.data_ptr()
         else:
