@@ -53,12 +53,27 @@ inline void set_voxel_coords(Args& a, const sdfv_grid& g) {
     }
 }
 
-// Exact division of a 32-bit index by a launch constant (fill_kernels.hip div_u32).
+// Exact division of a 32-bit index by a launch constant: make_div on the host, div_u32 in the kernel.
 struct DivU32 {
     unsigned long long magic;  // floor((2^64 - 1) / d) + 1
     uint32_t shift;            // log2(d) when d is a power of two
     uint32_t pow2;
 };
+inline DivU32 make_div(uint32_t d) {
+    DivU32 v;
+    v.pow2 = d != 0 && (d & (d - 1)) == 0;
+    v.shift = 0;
+    while (v.pow2 && (1u << v.shift) < d) ++v.shift;
+    v.magic = d > 1 ? (~0ull / d) + 1ull : 0ull;  // d == 1 is a power of two: the multiply is never taken
+    return v;
+}
+// Exact v / d for v < 2^32: a shift for powers of two, otherwise the 64-bit multiply-high with M = floor((2^64 - 1) / d) + 1
+// the flat dense kernel uses.  All fields are wave-uniform (SGPRs): one scalar branch.
+__device__ __forceinline__ uint32_t div_u32(uint32_t v, const DivU32& d) {
+    if (d.pow2) return v >> d.shift;
+    const unsigned long long t = ((unsigned long long)v * (uint32_t)d.magic) >> 32;
+    return (uint32_t)(((unsigned long long)v * (uint32_t)(d.magic >> 32) + t) >> 32);
+}
 
 struct PassArgs {
     uint32_t step;

@@ -151,14 +151,6 @@ __global__ __launch_bounds__(kBlock) void copy_segments_kernel(CopySegments c) {
     }
 }
 
-// Exact v / d for v < 2^32 (DivU32 made by the launcher): a shift for powers of two, otherwise the 64-bit multiply-high
-// with M = floor((2^64 - 1) / d) + 1 the flat dense kernel uses.  All fields are wave-uniform (SGPRs): one scalar branch.
-__device__ __forceinline__ uint32_t div_u32(uint32_t v, const DivU32& d) {
-    if (d.pow2) return v >> d.shift;
-    const unsigned long long t = ((unsigned long long)v * (uint32_t)d.magic) >> 32;
-    return (uint32_t)(((unsigned long long)v * (uint32_t)(d.magic >> 32) + t) >> 32);
-}
-
 // update_required (scene/sdf/mod.rs:184-190) for one visited voxel whose stored tex0.r is not AIR_DIST: inside the
 // changed box?  A cheap estimate of the coordinates (one multiply-add per axis; the exact ones differ from it by less than
 // approx_margin) rejects what is clearly outside before anyone pays for three correctly rounded divides.
@@ -175,26 +167,10 @@ __device__ __forceinline__ bool maybe_in_box(const FillArgs& a, const PassArgs& 
 // workgroups of a pass over a loaded grid have nothing to update and would pay the staging and its barrier for nothing; the
 // few lookups (the "normal" material only) read the 1 KiB table through the caches.
 template <typename Cfg>
-__device__ __forceinline__ void pass_store(const FillArgs& a, const PassArgs& p, float px, float py, float pz, uint64_t flat,
-                                           uint64_t row, uint32_t x) {
-    const LdsLut lut{c_srgb_lut};
+__device__ __forceinline__ void pass_store(const FillArgs& a, const PassArgs& p, float px, float py, float pz, uint64_t row, uint32_t x) {
     float4 v0, v1;
-    fill_voxel<Cfg>(a.prm, a.sdf_id, px, py, pz, lut, a.air_dist, v0, v1);
-    // Texture stores stream past L2 (nt), like the fused dense fill's: nothing re-reads them before the march's few texels
-    // under the hits, while the volume -- which this very pass READS -- keeps the cache.  tools/ubench/rw_mix.hip: a
-    // 4 B/voxel read stream next to the 36 B/voxel store stream costs 0.108 ms with plain stores and 0.094 with nt at 256^3.
-    store_texel<true>(a.tex0 + flat, v0);
-    if (p.dist) {
-        // The volume's contract: the textures were initialised / filled by this library, so tex1.a holds AIR_DIST
-        // everywhere (update() never writes it, scene/sdf/mod.rs:205-208) and need not be read back.
-        p.dist[vol_index(a.dist_ilv, row, x, a.W)] = v0.x;
-        v1.w = a.air_dist;
-    } else {
-        // tex1.a is not update()'s to touch: carry the stored value through a full 16-byte store (12-byte partial
-        // stores make the memory side read-modify-write the line; ~10 % slower on the step-1 pass)
-        v1.w = reinterpret_cast<const float*>(a.tex1 + flat)[3];
-    }
-    store_texel<true>(a.tex1 + flat, v1);
+    fill_voxel<Cfg>(a.prm, a.sdf_id, px, py, pz, LdsLut{c_srgb_lut}, a.air_dist, v0, v1);
+    pass_store_texels(a, p.dist, row, x, v0, v1);
 }
 
 // One LoadingManager pass, any step: one thread per visited voxel (x, y, z multiples of `step`; z is GLOBAL), workgroups in
@@ -218,11 +194,11 @@ __global__ __launch_bounds__(kBlock) void fill_pass_kernel(FillArgs a, PassArgs 
         const float pz = voxel_coord(z, a.dm1[2], a.bb_size[2], a.bb_min[2]);
         if (!is_air && !(px >= p.box[0] && px <= p.box[3] && py >= p.box[1] && py <= p.box[4] && pz >= p.box[2] && pz <= p.box[5]))
             return;
-        pass_store<Cfg>(a, p, px, py, pz, flat, row, x);
+        pass_store<Cfg>(a, p, px, py, pz, row, x);
         return;
     }
     pass_store<Cfg>(a, p, voxel_coord(x, a.dm1[0], a.bb_size[0], a.bb_min[0]), voxel_coord(y, a.dm1[1], a.bb_size[1], a.bb_min[1]),
-                    voxel_coord(z, a.dm1[2], a.bb_size[2], a.bb_min[2]), flat, row, x);
+                    voxel_coord(z, a.dm1[2], a.bb_size[2], a.bb_min[2]), row, x);
 }
 
 // The step-1 pass over a grid with its distance volume.  A pass over a loaded grid is bound by per-wave latency (one
@@ -292,7 +268,7 @@ __global__ __launch_bounds__(kBlock) void fill_pass_quad_kernel(FillArgs a, Pass
         const float px = voxel_coord(x, a.dm1[0], a.bb_size[0], a.bb_min[0]);
         if (!is_air && !(px >= p.box[0] && px <= p.box[3] && py >= p.box[1] && py <= p.box[4] && pz >= p.box[2] && pz <= p.box[5]))
             continue;
-        pass_store<Cfg>(a, p, px, py, pz, v, r, x);
+        pass_store<Cfg>(a, p, px, py, pz, r, x);
     }
 }
 
@@ -408,7 +384,7 @@ __global__ __launch_bounds__(kBlock) void fill_pass_rows_adaptive_kernel(FillArg
         if (!in) continue;
         const uint64_t row = (uint64_t)(z - a.z_begin) * a.H + y, flat = row * a.W + x;
         if (!whole) {
-            if (need) pass_store<Cfg>(a, p, voxel_coord(x, a.dm1[0], a.bb_size[0], a.bb_min[0]), py, pz, flat, row, x);
+            if (need) pass_store<Cfg>(a, p, voxel_coord(x, a.dm1[0], a.bb_size[0], a.bb_min[0]), py, pz, row, x);
             continue;
         }
         float4 v0 = make_float4(a.air_dist, a.air_dist, a.air_dist, a.air_dist), v1 = v0;
@@ -521,10 +497,9 @@ hipError_t launch_dense_cfg(const FillArgs& args, hipStream_t stream) {
     FillArgs a = args;
     a.x_chunks = (a.W + TX - 1) / TX;
     const uint64_t n_rows = (uint64_t)a.H * a.slab_d;
-    const uint64_t blocks = a.x_chunks * ((n_rows + TY - 1) / TY);
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    dim3 grid((uint32_t)blocks, 1, 1);
-    SDFV_LAUNCH_CFG(a, (fill_dense_kernel<TX, NT, Cfg>), grid, dim3(kBlock), 0, stream, a);
+    const uint32_t blocks = grid_size(a.x_chunks * ((n_rows + TY - 1) / TY));
+    if (!blocks) return hipErrorInvalidValue;
+    SDFV_LAUNCH_CFG(a, (fill_dense_kernel<TX, NT, Cfg>), dim3(blocks), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -532,9 +507,9 @@ template <bool NT>
 hipError_t launch_dense_pairrows(const FillArgs& args, hipStream_t stream) {
     FillArgs a = args;
     a.x_chunks = a.W / kBlock;
-    const uint64_t blocks = a.x_chunks * ((uint64_t)a.H * a.slab_d / 2);
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    SDFV_LAUNCH_CFG(a, (fill_dense_pairrows_kernel<NT, Cfg>), dim3((uint32_t)blocks), dim3(kBlock), 0, stream, a);
+    const uint32_t blocks = grid_size(a.x_chunks * ((uint64_t)a.H * a.slab_d / 2));
+    if (!blocks) return hipErrorInvalidValue;
+    SDFV_LAUNCH_CFG(a, (fill_dense_pairrows_kernel<NT, Cfg>), dim3(blocks), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -543,9 +518,9 @@ hipError_t launch_dense_ilv_paired(const FillArgs& args, hipStream_t stream) {
     FillArgs a = args;
     a.x_chunks = a.W / kBlock;
     const uint64_t units = a.x_chunks * ((uint64_t)a.H * a.slab_d / 2);
-    const uint64_t blocks = ((units + 7) / 8) * 16;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    SDFV_LAUNCH_CFG(a, (fill_dense_ilv_paired_kernel<NT, Cfg>), dim3((uint32_t)blocks), dim3(kBlock), 0, stream, a, (uint32_t)units);
+    const uint32_t blocks = grid_size(((units + 7) / 8) * 16);  // (units < blocks: both fit)
+    if (!blocks) return hipErrorInvalidValue;
+    SDFV_LAUNCH_CFG(a, (fill_dense_ilv_paired_kernel<NT, Cfg>), dim3(blocks), dim3(kBlock), 0, stream, a, (uint32_t)units);
     return hipGetLastError();
 }
 
@@ -559,10 +534,10 @@ hipError_t launch_dense_tx(const FillArgs& a, const FillLaunch& cfg, hipStream_t
 template <bool NT>
 hipError_t launch_dense_flat(const FillArgs& args, hipStream_t stream) {
     FillArgs a = args;
-    const uint64_t n_vox = (uint64_t)a.W * a.H * a.slab_d;
     // floor((2^64 - 1) / W) + 1: floor(2^64 / W) + 1 when W does not divide 2^64, exactly 2^64 / W when it does
     a.w_magic = a.W > 1 ? (~0ull / a.W) + 1ull : 0ull;
-    const uint32_t blocks = (uint32_t)((n_vox + kBlock - 1) / kBlock);
+    const uint32_t blocks = blocks_for((uint64_t)a.W * a.H * a.slab_d, 0xffffffffull);  // the kernel's flat index has 32 bits
+    if (!blocks) return hipErrorInvalidValue;
     SDFV_LAUNCH_CFG(a, (fill_dense_flat_kernel<NT, Cfg>), dim3(blocks), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
@@ -635,7 +610,7 @@ hipError_t launch_copy_segments(const CopySegments& c, hipStream_t stream) {
             if (c.n[i] > n_max) n_max = c.n[i];
         }
     if (segs == 0) return hipSuccess;
-    const uint32_t bx = (n_max + kBlock - 1) / kBlock;
+    const uint32_t bx = blocks_for(n_max);
     hipLaunchKernelGGL(copy_segments_kernel, dim3(bx < 4096 ? bx : 4096, segs), dim3(kBlock), 0, stream, c);
     return hipGetLastError();
 }
@@ -644,9 +619,9 @@ hipError_t launch_fill_slices(const FillArgs& args, hipStream_t stream) {
     FillArgs a = args;
     const uint64_t n_vox = (uint64_t)a.W * a.H * a.slab_d;
     if (n_vox == 0) return hipSuccess;
-    if (n_vox >= (1ull << 32) || a.z_step == 0) return hipErrorInvalidValue;
+    const uint32_t blocks = blocks_for(n_vox, 0xffffffffull);
+    if (a.z_step == 0 || !blocks) return hipErrorInvalidValue;
     a.w_magic = a.W > 1 ? (~0ull / a.W) + 1ull : 0ull;
-    const uint32_t blocks = (uint32_t)((n_vox + kBlock - 1) / kBlock);
     SDFV_LAUNCH_CFG(a, (fill_dense_flat_kernel<false, Cfg, true>), dim3(blocks), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
@@ -677,15 +652,6 @@ hipError_t launch_fill_dense(const FillArgs& a, const FillLaunch& cfg, hipStream
     if (a.W <= 64) return launch_dense_tx<64>(a, cfg, stream);
     if (a.W <= 128) return launch_dense_tx<128>(a, cfg, stream);
     return launch_dense_tx<256>(a, cfg, stream);
-}
-
-static DivU32 make_div(uint32_t d) {
-    DivU32 v;
-    v.pow2 = d != 0 && (d & (d - 1)) == 0;
-    v.shift = 0;
-    while (v.pow2 && (1u << v.shift) < d) ++v.shift;
-    v.magic = d > 1 ? (~0ull / d) + 1ull : 0ull;  // d == 1 is a power of two: the multiply is never taken
-    return v;
 }
 
 hipError_t launch_fill_pass(const FillArgs& a, const PassArgs& pass, const FillLaunch& dense_cfg, hipStream_t stream) {
@@ -737,7 +703,8 @@ hipError_t launch_fill_pass(const FillArgs& a, const PassArgs& pass, const FillL
     p.div_w = make_div(a.W);
     if (p.all_required && (p.step <= 8 || p.virgin)) {  // (a virgin grid has nothing to read back: whole rows at any step)
         // whole visited rows: one of every `step` texels computed, the rest re-stored (a constant over a fresh grid)
-        const uint32_t blocks = (uint32_t)(((uint64_t)a.W * p.ny * p.nz + kBlock - 1) / kBlock);
+        const uint32_t blocks = blocks_for((uint64_t)a.W * p.ny * p.nz, 0xffffffffull);  // (at most the slab's voxels: the limit held above)
+        if (!blocks) return hipErrorInvalidValue;
         if (p.fresh) {
             SDFV_LAUNCH_CFG(a, (fill_pass_rows_kernel<Cfg, true>), dim3(blocks), dim3(kBlock), 0, stream, a, p);
         } else {
@@ -751,7 +718,8 @@ hipError_t launch_fill_pass(const FillArgs& a, const PassArgs& pass, const FillL
         // step 8, like the all_required rows form: the rows hold W * ny * nz voxels against the lattice's nx * ny * nz, so at
         // larger steps a no-op pass would scan step / 4 times the lanes of the per-voxel kernel below
         const uint64_t lanes = ((uint64_t)a.W * p.ny * p.nz + (a.dist_ilv ? 1 : 3)) / (a.dist_ilv ? 2 : 4);
-        const uint32_t blocks = (uint32_t)((lanes + kBlock - 1) / kBlock);
+        const uint32_t blocks = blocks_for(lanes, 0xffffffffull);
+        if (!blocks) return hipErrorInvalidValue;
         if (a.dist_ilv) {
             SDFV_LAUNCH_CFG(a, (fill_pass_rows_adaptive_kernel<Cfg, 2>), dim3(blocks), dim3(kBlock), 0, stream, a, p);
         } else {
@@ -760,8 +728,8 @@ hipError_t launch_fill_pass(const FillArgs& a, const PassArgs& pass, const FillL
         return hipGetLastError();
     }
     const bool quad = p.step == 1 && vol16;
-    const uint64_t threads = quad ? (n + 3) / 4 : n;
-    const uint32_t blocks = (uint32_t)((threads + kBlock - 1) / kBlock);
+    const uint32_t blocks = blocks_for(quad ? (n + 3) / 4 : n, 0xffffffffull);
+    if (!blocks) return hipErrorInvalidValue;
     if (quad) {
         SDFV_LAUNCH_CFG(a, (fill_pass_quad_kernel<Cfg>), dim3(blocks), dim3(kBlock), 0, stream, a, p);
     } else {
@@ -772,9 +740,9 @@ hipError_t launch_fill_pass(const FillArgs& a, const PassArgs& pass, const FillL
 
 hipError_t launch_commit_distance(const float* tex0, float* dist, uint64_t n_voxels, hipStream_t stream) {
     if (n_voxels == 0) return hipSuccess;
-    uint64_t blocks = (n_voxels + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(commit_distance_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, stream,
+    const uint32_t blocks = blocks_for(n_voxels);
+    if (!blocks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(commit_distance_kernel, dim3(blocks), dim3(kBlock), 0, stream,
                        reinterpret_cast<const float4*>(tex0), dist, n_voxels);
     return hipGetLastError();
 }
@@ -799,9 +767,9 @@ hipError_t launch_commit_pairs(const float* dist, float* pairs, uint32_t W, uint
 hipError_t launch_commit_interleaved(const float* dist, float* ilv, uint32_t W, uint64_t n_voxels, hipStream_t stream) {
     const uint64_t n_pairs = n_voxels / 2;
     if (n_pairs == 0) return hipSuccess;
-    const uint64_t blocks = (n_pairs + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(commit_interleaved_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, stream, dist, reinterpret_cast<float2*>(ilv),
+    const uint32_t blocks = blocks_for(n_pairs);
+    if (!blocks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(commit_interleaved_kernel, dim3(blocks), dim3(kBlock), 0, stream, dist, reinterpret_cast<float2*>(ilv),
                        W, n_pairs);
     return hipGetLastError();
 }
@@ -818,9 +786,9 @@ hipError_t launch_grid_init_unvisited(float* tex0, float* tex1, float* dist, uin
 
 hipError_t launch_grid_init(float* tex0, float* tex1, uint64_t n_voxels, float air, hipStream_t stream) {
     if (n_voxels == 0) return hipSuccess;
-    const uint64_t blocks = (n_voxels + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(grid_init_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, stream,
+    const uint32_t blocks = blocks_for(n_voxels);
+    if (!blocks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(grid_init_kernel, dim3(blocks), dim3(kBlock), 0, stream,
                        reinterpret_cast<float4*>(tex0), reinterpret_cast<float4*>(tex1), n_voxels, air);
     return hipGetLastError();
 }

@@ -59,12 +59,12 @@ __global__ __launch_bounds__(kBlock) void pack_samples_kernel(PackArgs a) {
 
 hipError_t launch_pack_samples(const PackArgs& a, hipStream_t stream) {
     if (a.n == 0) return hipSuccess;
-    const uint64_t blocks = (a.n + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const uint32_t blocks = blocks_for(a.n);
+    if (!blocks) return hipErrorInvalidValue;
     if (a.srgb_round)
-        hipLaunchKernelGGL(pack_samples_kernel<true>, dim3((uint32_t)blocks), dim3(kBlock), 0, stream, a);
+        hipLaunchKernelGGL(pack_samples_kernel<true>, dim3(blocks), dim3(kBlock), 0, stream, a);
     else
-        hipLaunchKernelGGL(pack_samples_kernel<false>, dim3((uint32_t)blocks), dim3(kBlock), 0, stream, a);
+        hipLaunchKernelGGL(pack_samples_kernel<false>, dim3(blocks), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 

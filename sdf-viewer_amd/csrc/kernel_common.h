@@ -1,15 +1,20 @@
 // kernel_common.h -- what the SDF kernels share on the device: the small helpers every .hip file used to restate, the
-// 28-byte sample record, the LDS staging of arrays of structures, and the two skeletons that are instantiated once per
-// way of evaluating an SDF (the demo tree of demo_sdf_device.h, the interpreter of program_eval.h):
+// 28-byte sample record, the LDS staging of arrays of structures, the store of one voxel a pass rewrites (pass_store_texels),
+// the block-count rule of every launcher (blocks_for), and the skeletons that are instantiated once per way of evaluating
+// an SDF (the demo tree of demo_sdf_device.h, the interpreter of program_eval.h):
 //  * dense_fill_rows: the dense row-chunk fill (fill_dense_kernel and the sdfprog_fill_* kernels);
-//  * sample_points / sample_points_staged: points in, records out (the demo's and the program's samplers).
+//  * map_elements / map_elements_staged: IN words per element in, OUT words out (the samplers, the batched normals, the
+//    source scalars and the demo's Mesh::postproc).
 // An evaluator is a small object of wave-uniform state: for the fill `void operator()(px, py, pz, lut, air_dist, t0, t1)`
-// writes the two texels, for the samplers `Sample operator()(px, py, pz)`.  Everything here is __forceinline__ and takes its
-// arguments by reference: a kernel built from these pieces is the kernel that spelled them out.
+// writes the two texels, for the element map `void operator()(float* v, bool live)` turns an element into its result in
+// place.  Everything here is __forceinline__ and takes its arguments by reference: a kernel built from these pieces is the
+// kernel that spelled them out.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "demo_sdf_device.h"
 #include "fill_kernels.h"
@@ -69,6 +74,28 @@ __device__ __forceinline__ Index vol_index(uint32_t ilv, Index row, X x, uint32_
     return ilv ? ((row >> 1) * W + x) * 2 + (row & 1) : row * W + x;
 }
 
+// The rewrite of voxel x of slab row `row` by a LoadingManager pass: the texel pair (v0, v1) an evaluation gave, and the
+// entry of the distance volume `vol` (nullptr = the grid has none).  Args = FillArgs or ProgramPassArgs.
+template <typename Args>
+__device__ __forceinline__ void pass_store_texels(const Args& a, float* vol, uint64_t row, uint32_t x, const float4& v0, float4 v1) {
+    const uint64_t flat = row * a.W + x;
+    // Texture stores stream past L2 (nt), like the fused dense fill's: nothing re-reads them before the march's few texels
+    // under the hits, while the volume -- which this very pass READS -- keeps the cache.  tools/ubench/rw_mix.hip: a
+    // 4 B/voxel read stream next to the 36 B/voxel store stream costs 0.108 ms with plain stores and 0.094 with nt at 256^3.
+    store_texel<true>(a.tex0 + flat, v0);
+    if (vol) {
+        // The volume's contract: the textures were initialised / filled by this library, so tex1.a holds AIR_DIST
+        // everywhere (update() never writes it, scene/sdf/mod.rs:205-208) and need not be read back.
+        vol[vol_index(a.dist_ilv, row, (uint64_t)x, a.W)] = v0.x;
+        v1.w = a.air_dist;
+    } else {
+        // tex1.a is not update()'s to touch: carry the stored value through a full 16-byte store (12-byte partial
+        // stores make the memory side read-modify-write the line; ~10 % slower on the step-1 pass)
+        v1.w = reinterpret_cast<const float*>(a.tex1 + flat)[3];
+    }
+    store_texel<true>(a.tex1 + flat, v1);
+}
+
 // The (y, z) coordinates of slab row `row` (= z_local * H + y; local slice k is global slice z_begin + k * z_step): an IEEE
 // divide per axis, so once per row (through LDS) instead of once per voxel.
 template <typename Args>
@@ -125,31 +152,61 @@ __device__ __forceinline__ void tile_store(float4* global, const float* lds) {
             __builtin_nontemporal_store(reinterpret_cast<const v4f*>(lds)[r + t], reinterpret_cast<v4f*>(global) + tile + r + t);
 }
 
-// ---- point samplers: SDFSurface::sample for n arbitrary points, one thread per point ----
-// Scalar form: any alignment, any n (also finishes the last partial workgroup of the staged form).
-template <typename Eval>
-__device__ __forceinline__ void sample_points(const Eval& eval, const float* __restrict__ points, size_t first, size_t n,
-                                              float* __restrict__ out) {
+// ---- the element map: n elements of IN words in, OUT words out, one thread per element ----
+// Every per-element kernel over caller arrays (samples, normals, source scalars, Mesh::postproc; the demo tree's and the
+// program's) is one of these two calls around an evaluator `void operator()(float* v, bool live)`: v[0 .. IN) holds the
+// element, the evaluator leaves the result in v[0 .. OUT), and words [SKIP, OUT) of it are written.  `live` is false under
+// the lanes beyond n, whose v is zero: an evaluator either leaves them at once or, where its loop is the wave's (the
+// interpreter), runs them under the mask.  The element is read whole before anything is written: in == out is allowed.
+// Scalar form: any 4-byte alignment, any n -- element first + workgroup * kBlock + thread; it also finishes what the staged
+// form leaves over (launch_staged_then_tail).
+template <int IN, int OUT, int SKIP = 0, typename Eval>
+__device__ __forceinline__ void map_elements(const Eval& eval, const float* in, size_t first, size_t n, float* out) {
     const size_t i = first + (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float px = points[i * 3 + 0], py = points[i * 3 + 1], pz = points[i * 3 + 2];
-    write_record(out + i * 7, eval(px, py, pz));
+    const bool live = i < n;
+    float v[IN > OUT ? IN : OUT] = {};
+    if (live)
+        for (int k = 0; k < IN; ++k) v[k] = in[i * IN + k];
+    eval(v, live);
+    if (live)
+        for (int k = SKIP; k < OUT; ++k) out[i * OUT + k] = v[k];
 }
 
-// Staged form for whole workgroups of 256 points: the 12-byte points and the 28-byte samples are arrays of structures, so
-// per-lane accesses would be 3 and 7 dword operations at a 12 / 28-byte stride; a workgroup's 3 KiB in and 7 KiB out go
-// through tile_load / tile_store instead.  Memory order, one point per thread.
-template <typename Eval>
-__device__ __forceinline__ void sample_points_staged(const Eval& eval, const float4* __restrict__ points, float4* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float s_in[kBlock * 3];
-    __shared__ __attribute__((aligned(16))) float s_out[kBlock * 7];
+// Staged form: WHOLE workgroups of kBlock elements through 16-byte aligned arrays, and nothing else -- per-lane accesses to
+// an array of structures would be IN and OUT dword operations at an IN * 4 / OUT * 4-byte stride, so a workgroup's tile goes
+// through tile_load / tile_store instead.  The way out follows from the sizes: OUT == IN -- the result goes back into the
+// thread's own words of the input tile (no barrier in between), which is stored whole; OUT == 1 -- the 4-byte results are
+// coalesced as they are, one streamed dword per lane; otherwise a second tile.
+template <int OUT>
+using StagedOut = std::conditional_t<OUT == 1, float, float4>;
+template <int IN, int OUT, int SKIP = 0, typename Eval>
+__device__ __forceinline__ void map_elements_staged(const Eval& eval, const float4* in, StagedOut<OUT>* out) {
+    __shared__ __attribute__((aligned(16))) float s_in[kBlock * IN];
     const uint32_t t = threadIdx.x;
-    tile_load<3>(s_in, points);
+    tile_load<IN>(s_in, in);
     __syncthreads();
-    const float px = s_in[t * 3 + 0], py = s_in[t * 3 + 1], pz = s_in[t * 3 + 2];
-    write_record(s_out + t * 7, eval(px, py, pz));
-    __syncthreads();
-    tile_store<7>(out, s_out);
+    float v[IN > OUT ? IN : OUT];
+    for (int k = 0; k < IN; ++k) v[k] = s_in[t * IN + k];
+    eval(v, true);
+    if constexpr (OUT == 1) {
+        __builtin_nontemporal_store(v[0], out + (size_t)blockIdx.x * kBlock + t);
+    } else if constexpr (OUT == IN) {
+        for (int k = SKIP; k < OUT; ++k) s_in[t * OUT + k] = v[k];
+        __syncthreads();
+        tile_store<OUT>(out, s_in);
+    } else {
+        __shared__ __attribute__((aligned(16))) float s_out[kBlock * OUT];
+        for (int k = SKIP; k < OUT; ++k) s_out[t * OUT + k] = v[k];
+        __syncthreads();
+        tile_store<OUT>(out, s_out);
+    }
+}
+
+// Mesh::postproc's rule (meshers/mesh.rs:22-33): the normal is recomputed where the mesher left |n|^2 < 1e-4 (distance2 to the
+// zero vector).
+__device__ __forceinline__ bool normal_unset(float nx, float ny, float nz) {
+    const float dx = nx - 0.0f, dy = ny - 0.0f, dz = nz - 0.0f;
+    return dx * dx + dy * dy + dz * dz < 0.0001f;
 }
 
 // ---- the dense row-chunk fill ----
@@ -260,21 +317,26 @@ struct DemoFillEval {
     }
 };
 
-// Launch helpers of the host side.
-inline uint32_t blocks_for(size_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
+// ---- how many workgroups, and is that launchable ----
+// A launch takes 2^31 - 1 workgroups at the most: here a 64-bit count of them becomes a grid, or 0 = not launchable.
+inline uint32_t grid_size(uint64_t blocks) { return blocks > 0x7fffffffull ? 0u : (uint32_t)blocks; }
+// n >= 1 elements, one per thread: ceil(n / kBlock) workgroups.  A kernel that indexes its elements with 32 bits names the
+// largest n it can take as well.  0 = refuse with hipErrorInvalidValue; where the caller has held n to 32 bits already
+// (MeshGrid::launchable(), a uint32_t kernel argument) it goes straight into the launch, which takes no empty grid.
+inline uint32_t blocks_for(uint64_t n, uint64_t max_n = ~0ull) { return n > max_n ? 0u : grid_size(n / kBlock + (n % kBlock != 0)); }
 
 // n elements through a kernel with a staged form: whole workgroups of kBlock through `staged(whole)` if `aligned` (the
 // pointers allow 16-byte accesses), the rest -- [done, n) -- through `scalar(blocks, done)`, which takes any alignment.
-// More than 2^31 - 1 workgroups in either launch are refused before anything is launched.
+// An n that needs more workgroups than one launch takes is refused before anything is launched, whatever the alignment.
 template <typename Staged, typename Scalar>
 hipError_t launch_staged_then_tail(size_t n, bool aligned, Staged&& staged, Scalar&& scalar) {
     if (n == 0) return hipSuccess;
-    const size_t whole = aligned ? n / kBlock : 0;
-    const size_t done = whole * kBlock;
-    const size_t tail_blocks = (n - done + kBlock - 1) / kBlock;
-    if (whole > 0x7fffffffull || tail_blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    if (whole > 0) staged((uint32_t)whole);
-    if (done < n) scalar((uint32_t)tail_blocks, done);
+    const uint32_t all = blocks_for(n);
+    if (!all) return hipErrorInvalidValue;
+    const uint32_t whole = aligned ? (uint32_t)(n / kBlock) : 0u;  // <= all
+    const size_t done = (size_t)whole * kBlock;
+    if (whole > 0) staged(whole);
+    if (done < n) scalar(all - whole, done);
     return hipGetLastError();
 }
 

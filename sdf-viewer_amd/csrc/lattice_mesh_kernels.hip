@@ -141,9 +141,9 @@ hipError_t launch_lattice_points(const MeshGrid& g, uint32_t first, uint32_t n, 
 
 hipError_t launch_lattice_from_samples(const sdfv_sample* samples, size_t n, float* dist, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    const size_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lattice_from_samples, dim3((uint32_t)blocks), dim3(kBlock), 0, stream, reinterpret_cast<const float*>(samples),
+    const uint32_t blocks = blocks_for(n);
+    if (!blocks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lattice_from_samples, dim3(blocks), dim3(kBlock), 0, stream, reinterpret_cast<const float*>(samples),
                        n, dist);
     return hipGetLastError();
 }

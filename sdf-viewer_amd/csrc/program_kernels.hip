@@ -6,7 +6,7 @@
 //  * sdfprog_fill_tx{64,128,256}[_nt]: dense_fill_rows -- one voxel per thread, x fastest, the sRGB table and the rows' (y, z)
 //    coordinates in LDS, pack_sample() for the texels, 16-byte stores front to back, the distance volume in either layout
 //    from the same launch.  The store policy stays a template parameter;
-//  * sdfprog_sample_points{,_staged}: sample_points{,_staged} -- points in, 28-byte records out.
+//  * sdfprog_sample_points{,_staged}: map_elements{,_staged}<3, 7> -- points in, 28-byte records out.
 // The instruction stream is read through wave-uniform addresses: scalar loads, no vector memory traffic per instruction, and
 // no kernel arguments beyond a pointer and a count (the handle owns a device copy of the instructions).
 // The kernels carry C names: tests and profiles find them under the same symbol whatever the toolchain mangles.
@@ -34,13 +34,13 @@ struct ProgramFillEval {
     }
 };
 
-// ... and as the samplers'
+// ... and as the element map's for the samplers: a point in, its 28-byte record out
 struct ProgramSampleEval {
     const sdfv_prog_op* ops;
     uint32_t n_ops;
     bool distance_only;
-    __device__ __forceinline__ Sample operator()(float px, float py, float pz) const {
-        return resolve(ops, prog::run(ops, n_ops, px, py, pz), distance_only);
+    __device__ __forceinline__ void operator()(float* v, bool live) const {
+        if (live) write_record(v, resolve(ops, prog::run(ops, n_ops, v[0], v[1], v[2]), distance_only));
     }
 };
 
@@ -58,13 +58,13 @@ __global__ __launch_bounds__(kBlock) void sdfprog_fill_tx256_nt(ProgramFillArgs 
 __global__ __launch_bounds__(kBlock) void sdfprog_sample_points(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
                                                                 const float* __restrict__ points, size_t first, size_t n,
                                                                 bool distance_only, float* __restrict__ out) {
-    sample_points(ProgramSampleEval{ops, n_ops, distance_only}, points, first, n, out);
+    map_elements<3, 7>(ProgramSampleEval{ops, n_ops, distance_only}, points, first, n, out);
 }
 
 __global__ __launch_bounds__(kBlock) void sdfprog_sample_points_staged(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
                                                                        const float4* __restrict__ points, bool distance_only,
                                                                        float4* __restrict__ out) {
-    sample_points_staged(ProgramSampleEval{ops, n_ops, distance_only}, points, out);
+    map_elements_staged<3, 7>(ProgramSampleEval{ops, n_ops, distance_only}, points, out);
 }
 
 }  // extern "C"
@@ -79,11 +79,11 @@ hipError_t launch_program_fill(const ProgramFillArgs& args, hipStream_t stream) 
     const uint32_t ty = kBlock / tx;
     a.x_chunks = (a.W + tx - 1) / tx;
     const uint64_t n_rows = (uint64_t)a.H * a.slab_d;
-    const uint64_t blocks = (uint64_t)a.x_chunks * ((n_rows + ty - 1) / ty);
-    if (n_rows > 0x7fffffffull || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const uint32_t blocks = grid_size((uint64_t)a.x_chunks * ((n_rows + ty - 1) / ty));  // (the rows fit: check_one_launch)
+    if (!blocks) return hipErrorInvalidValue;
     auto kernel = a.nontemporal ? (tx == 64 ? sdfprog_fill_tx64_nt : (tx == 128 ? sdfprog_fill_tx128_nt : sdfprog_fill_tx256_nt))
                                 : (tx == 64 ? sdfprog_fill_tx64 : (tx == 128 ? sdfprog_fill_tx128 : sdfprog_fill_tx256));
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 

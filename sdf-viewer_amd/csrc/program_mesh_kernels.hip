@@ -10,7 +10,8 @@
 //    mesh_edge_positions (mesh_kernels.hip, SDF-free) or dual contouring's solve has written -- dense waves.  Reads the
 //    position, runs the four taps of normal_default_impl through ONE copy of the interpreter in a loop (tap_normal; _mat adds a
 //    fifth, full run at the position itself + resolve(): material_at), writes the 48-byte record as three 16-byte stores;
-//  * sdfprog_normal_points[_staged], sdfprog_mesh_postproc[_unaligned]: the same per-lane function over caller arrays.
+//  * sdfprog_normal_points[_staged] (the element map of kernel_common.h), sdfprog_mesh_postproc[_unaligned]: the same per-lane
+//    function over caller arrays.
 // Every live lane runs the whole program, so the instruction stream stays wave-uniform: scalar loads, as in program_kernels.hip.
 // The kernels carry C names: tests and profiles find them under the same symbol whatever the toolchain mangles.
 #include "program_mesh_kernels.h"
@@ -88,12 +89,18 @@ __device__ __forceinline__ void mesh_vertices(const sdfv_prog_op* __restrict__ o
     }
 }
 
-// Mesh::postproc's rule (meshers/mesh.rs:22-33): the normal is recomputed where the mesher left |n|^2 < 1e-4 (distance2 to the
-// zero vector, as points_kernels.hip's postproc_vertex spells it).
-__device__ __forceinline__ bool normal_unset(float nx, float ny, float nz) {
-    const float dx = nx - 0.0f, dy = ny - 0.0f, dz = nz - 0.0f;
-    return dx * dx + dy * dy + dz * dz < 0.0001f;
-}
+// The batched normal as the element map's evaluator (kernel_common.h): a point in, the normal there out.  EVERY lane goes into
+// tap_normal, the lanes beyond n (whose point is zero) under its mask: the interpreter's loop is the wave's.
+struct ProgramNormalEval {
+    const sdfv_prog_op* ops;
+    uint32_t n_ops;
+    float eps;
+    __device__ __forceinline__ void operator()(float* v, bool live) const {
+        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+        tap_normal(ops, n_ops, v[0], v[1], v[2], eps, live, nx, ny, nz);
+        v[0] = nx; v[1] = ny; v[2] = nz;
+    }
+};
 
 }  // namespace
 
@@ -121,37 +128,16 @@ __global__ __launch_bounds__(kBlock) void sdfprog_mesh_vertices_mat(const sdfv_p
     mesh_vertices<true>(ops, n_ops, vertices, n);
 }
 
-// Scalar form: any alignment, any n (also finishes the last partial workgroup of the staged form).
 __global__ __launch_bounds__(kBlock) void sdfprog_normal_points(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
                                                                 const float* __restrict__ points, size_t first, size_t n,
                                                                 float eps, float* __restrict__ out) {
-    const size_t i = first + (size_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool live = i < n;
-    float px = 0.0f, py = 0.0f, pz = 0.0f;
-    if (live) {
-        px = points[i * 3 + 0]; py = points[i * 3 + 1]; pz = points[i * 3 + 2];
-    }
-    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-    tap_normal(ops, n_ops, px, py, pz, eps, live, nx, ny, nz);
-    if (live) {
-        out[i * 3 + 0] = nx; out[i * 3 + 1] = ny; out[i * 3 + 2] = nz;
-    }
+    map_elements<3, 3>(ProgramNormalEval{ops, n_ops, eps}, points, first, n, out);
 }
 
-// Whole workgroups of 256 points: 3 KiB in, 3 KiB out through LDS (tile_load / tile_store), like normal_points_staged_kernel.
 __global__ __launch_bounds__(kBlock) void sdfprog_normal_points_staged(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
                                                                        const float4* __restrict__ points, float eps,
                                                                        float4* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float s_io[kBlock * 3];
-    const uint32_t t = threadIdx.x;
-    tile_load<3>(s_io, points);
-    __syncthreads();
-    const float px = s_io[t * 3 + 0], py = s_io[t * 3 + 1], pz = s_io[t * 3 + 2];
-    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-    tap_normal(ops, n_ops, px, py, pz, eps, true, nx, ny, nz);
-    s_io[t * 3 + 0] = nx; s_io[t * 3 + 1] = ny; s_io[t * 3 + 2] = nz;  // a thread's own three words: no barrier in between
-    __syncthreads();
-    tile_store<3>(out, s_io);
+    map_elements_staged<3, 3>(ProgramNormalEval{ops, n_ops, eps}, points, out);
 }
 
 // 16-byte aligned vertices: 16-byte accesses.  A kept normal goes back as it was read.
@@ -231,13 +217,13 @@ hipError_t launch_program_normal_points(const sdfv_prog_op* ops, uint32_t n_ops,
 hipError_t launch_program_mesh_postproc(const sdfv_prog_op* ops, uint32_t n_ops, sdfv_vertex* vertices, size_t n,
                                         hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    const size_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const uint32_t blocks = blocks_for(n);
+    if (!blocks) return hipErrorInvalidValue;
     if (((uintptr_t)vertices & 15) == 0)
-        hipLaunchKernelGGL(sdfprog_mesh_postproc, dim3((uint32_t)blocks), dim3(kBlock), 0, stream, ops, n_ops,
+        hipLaunchKernelGGL(sdfprog_mesh_postproc, dim3(blocks), dim3(kBlock), 0, stream, ops, n_ops,
                            reinterpret_cast<float4*>(vertices), n);
     else
-        hipLaunchKernelGGL(sdfprog_mesh_postproc_unaligned, dim3((uint32_t)blocks), dim3(kBlock), 0, stream, ops, n_ops,
+        hipLaunchKernelGGL(sdfprog_mesh_postproc_unaligned, dim3(blocks), dim3(kBlock), 0, stream, ops, n_ops,
                            reinterpret_cast<float*>(vertices), n);
     return hipGetLastError();
 }

@@ -22,24 +22,8 @@ namespace sdfv {
 
 namespace {
 
-// Exact v / d for v < 2^32 (DivU32, fill_kernels.h): the demo pass kernels' division, for this translation unit.
-__device__ __forceinline__ uint32_t div_u32(uint32_t v, const DivU32& d) {
-    if (d.pow2) return v >> d.shift;
-    const unsigned long long t = ((unsigned long long)v * (uint32_t)d.magic) >> 32;
-    return (uint32_t)(((unsigned long long)v * (uint32_t)(d.magic >> 32) + t) >> 32);
-}
-
-DivU32 make_div(uint32_t d) {
-    DivU32 v;
-    v.pow2 = d != 0 && (d & (d - 1)) == 0;
-    v.shift = 0;
-    while (v.pow2 && (1u << v.shift) < d) ++v.shift;
-    v.magic = d > 1 ? (~0ull / d) + 1ull : 0ull;  // d == 1 is a power of two: the multiply is never taken
-    return v;
-}
-
 // The rewrite of one lattice voxel (the demo's pass_store with the interpreter as the SDF): the texel pair the dense program
-// fill writes, streamed past L2; with a volume its entry and tex1.a = AIR_DIST, without one tex1.a carried through.
+// fill writes, stored as every pass stores (pass_store_texels).
 template <typename Lut>
 __device__ __forceinline__ void program_pass_store(const ProgramPassArgs& a, const Lut& lut, float px, float py, float pz, uint64_t row,
                                                    uint32_t x) {
@@ -47,15 +31,7 @@ __device__ __forceinline__ void program_pass_store(const ProgramPassArgs& a, con
     float4 v0, v1;
     if (a.srgb_round) pack_sample<true>(s, lut, a.air_dist, v0, v1);
     else pack_sample<false>(s, lut, a.air_dist, v0, v1);
-    const uint64_t flat = row * a.W + x;
-    store_texel<true>(a.tex0 + flat, v0);
-    if (a.dist) {
-        a.dist[vol_index(a.dist_ilv, row, (uint64_t)x, a.W)] = v0.x;
-        v1.w = a.air_dist;
-    } else {
-        v1.w = reinterpret_cast<const float*>(a.tex1 + flat)[3];
-    }
-    store_texel<true>(a.tex1 + flat, v1);
+    pass_store_texels(a, a.dist, row, x, v0, v1);
 }
 
 // STREAM: the one load is nontemporal (a template policy like store_texel's: as a run-time choice the two loads are merged
@@ -113,13 +89,6 @@ __global__ __launch_bounds__(kBlock) void sdfprog_pass_scan_nt(ProgramPassArgs a
 }  // extern "C"
 
 namespace {
-// Lattice points -> workgroups; more than 2^32 points (or 2^31 - 1 workgroups) are the caller's to refuse.
-hipError_t pass_blocks(uint64_t n, uint32_t* blocks) {
-    const uint64_t b = (n + kBlock - 1) / kBlock;
-    if (n > (1ull << 32) || b > 0x7fffffffull) return hipErrorInvalidValue;
-    *blocks = (uint32_t)b;
-    return hipSuccess;
-}
 bool lattice_in_slab(const ProgramPassArgs& a) {
     return a.step >= 1 && (uint64_t)(a.nx - 1) * a.step < a.W && (uint64_t)(a.ny - 1) * a.step < a.H && a.z_first >= a.z_begin &&
            (uint64_t)(a.z_first - a.z_begin) + (uint64_t)(a.nz - 1) * a.step < a.slab_d;
@@ -134,8 +103,8 @@ hipError_t launch_program_pass_box(const ProgramPassArgs& args, hipStream_t stre
     if ((uint64_t)a.bx0 + a.bnx > a.nx || (uint64_t)a.by0 + a.bny > a.ny || (uint64_t)a.bz0 + a.bnz > a.nz || !lattice_in_slab(a))
         return hipErrorInvalidValue;
     if (a.dist == nullptr) a.dist_ilv = 0;
-    uint32_t blocks = 0;
-    if (hipError_t e = pass_blocks(a.n, &blocks)) return e;
+    const uint32_t blocks = blocks_for(a.n, 1ull << 32);  // the kernel's 32-bit index covers 2^32 points
+    if (!blocks) return hipErrorInvalidValue;
     a.div_x = make_div(a.bnx);
     a.div_y = make_div(a.bny);
     hipLaunchKernelGGL(sdfprog_pass_box, dim3(blocks), dim3(kBlock), 0, stream, a);
@@ -148,8 +117,8 @@ hipError_t launch_program_pass_scan(const ProgramPassArgs& args, hipStream_t str
     if (a.n == 0) return hipSuccess;
     if (!lattice_in_slab(a)) return hipErrorInvalidValue;
     if (a.dist == nullptr) a.dist_ilv = 0;
-    uint32_t blocks = 0;
-    if (hipError_t e = pass_blocks(a.n, &blocks)) return e;
+    const uint32_t blocks = blocks_for(a.n, 1ull << 32);  // the kernel's 32-bit index covers 2^32 points
+    if (!blocks) return hipErrorInvalidValue;
     a.div_x = make_div(a.nx);
     a.div_y = make_div(a.ny);
     hipLaunchKernelGGL(a.stream_loads ? sdfprog_pass_scan_nt : sdfprog_pass_scan, dim3(blocks), dim3(kBlock), 0, stream, a);
