@@ -17,7 +17,22 @@
  *     thread-local message.  Nothing aborts (reference convention: log + zero result, ffi.rs:46-49).
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Calls only enqueue work;
  *     the caller synchronises the stream.  A handle/stream pair is single-owner, like the reference's
- *     thread-local registry (ffi.rs:15-17).
+ *     thread-local registry (ffi.rs:15-17).  HOST arguments (parameter structs, grids, descriptors, changed boxes,
+ *     camera arrays) are read before the call returns and are free again then.  Every entry that takes a `stream` is
+ *     in one of three classes (held by tests/test_gpu_stream_*.py):
+ *       enqueue-only, capturable:  sdfv_grid_init[_unvisited[_ex]], sdfv_fill_grid[_commit], sdfv_fill_grid_pass_ex,
+ *         sdfv_commit_distance / _pairs / _interleaved, sdfv_pack_samples, sdfv_emit_update_points;
+ *         sdfv_sample_points, sdfv_normal_points, sdfv_source_sample_scalar / _normal, sdfv_mesh_postproc;
+ *         sdfv_lattice_points / _from_samples / _normals; sdfv_raymarch_slab[_round], sdfv_bands_scatter.
+ *       enqueue-only after a first-use cost, capturable once that is paid:  every sdfv_program_* call with a stream
+ *         (the program's device copy, synchronous, on the first use per device); sdfv_raymarch_ex (the camera ring
+ *         of a HOST array of more than 16 cameras and the side streams of a batch that takes several launches --
+ *         more than 64 cameras, or more than 16 where the ring is not used -- are made on the calling thread's
+ *         first such call; under capture a host array goes out as launches of 16 instead).
+ *       synchronise `stream`:  sdfv_mesh_extract, sdfv_program_mesh_extract, sdfv_lattice_mesh_extract (the output
+ *         size is data dependent).  Not capturable.
+ *     The *_host forms take no stream and return when their result is in host memory; sdfv_slab_* and sdfv_comm_*
+ *     say below what they enqueue on the communicator's own streams.
  *   - textures are RGBA32F, row-major with x fastest: flat = (z*H + y)*W + x (scene/sdf/mod.rs:177);
  *     tex0 = (clamped distance + 0.1, linear r, g, b), tex1 = (metallic, roughness, occlusion, AIR_DIST).
  */

@@ -223,13 +223,26 @@ class Arena:
             return f"below view {near.name!r}: byte {byte - near.offset} relative to its start"
         return f"above view {near.name!r}: byte {byte - near.offset} relative to its start, {byte - near.end + 1} past its {near.nbytes} bytes"
 
-    def check(self, expected):
+    def poison_of(self, name, kind):
+        """The poison `kind` of the bytes of view `name`, a uint8 tensor on the arena's device: what tests/stream_gate.py puts
+        into an input before the real bits arrive late, and (kind "canary") into an output after an early store."""
+        v = self.view(name)
+        return torch.from_numpy(self._poison_host(kind).view(np.uint8)[v.offset:v.end].copy()).to(self.device)
+
+    def bytes_of(self, name):
+        """View `name` as the uint8 slice of the arena it is."""
+        v = self.view(name)
+        return self.raw[v.offset:v.end]
+
+    def check(self, expected, raw=None):
         """One copy of the whole arena to the host, then: every byte outside the output views holds its poison (or, inside an
         input, the uploaded bits), and each output view equals expected[name] bit for bit (an ndarray, or Untouched).  Returns
-        {name: the output's bytes} for comparisons between runs."""
+        {name: the output's bytes} for comparisons between runs.  raw: a copy of self.raw taken earlier (on a stream, between
+        other work) to be held to the same instead of the arena as it is now."""
         if self.device.type == "cuda":
             torch.cuda.synchronize()
-        got = self.raw.cpu().numpy()
+        got = (self.raw if raw is None else raw).cpu().numpy()
+        assert got.shape == (self.nbytes,)
         need = band_for(*[(v.shape, v.dtype) for v in self.views])
         assert self.band >= need, f"arena band {self.band} is below the {need} bytes its widest view asks for"
         want = self._poison_host(self.kind).view(np.uint8).copy()

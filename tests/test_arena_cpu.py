@@ -167,6 +167,22 @@ def test_expected_value_equal_to_the_canary_is_refused():
         ar.twin(lambda: clean(ar), {"dst": want})
 
 
+def test_a_copy_taken_earlier_is_held_like_the_arena_itself():
+    """check(raw=...): what tests/stream_gate.py holds its on-stream snapshot with; poison_of / bytes_of: a view's poison and bytes."""
+    ar, src_host, src, dst = make()
+    early = ar.raw.clone()                      # before the kernel: dst still holds its canary
+    clean(ar)
+    late = ar.raw.clone()
+    ar.check({"dst": 2.0 * src_host})
+    ar.check({"dst": 2.0 * src_host}, raw=late)
+    with pytest.raises(A.ArenaError, match="never written"):
+        ar.check({"dst": 2.0 * src_host}, raw=early)
+    v = ar.view("dst")
+    assert np.array_equal(ar.poison_of("dst", "canary").numpy(), early.numpy()[v.offset:v.end])
+    assert (ar.poison_of("src", "nan").numpy().view(np.uint32) == A.NAN_BITS).all()
+    assert ar.bytes_of("src").data_ptr() == src.data_ptr() and ar.bytes_of("src").numel() == 4 * N
+
+
 def test_band_rule_and_arena_size():
     tex = ((6, 64, 256, 4), np.float32)
     assert A.band_for(tex) == 2 * 64 * 256 * 16 and A.band_for(((513, 7), np.float32)) == A.MIN_BAND

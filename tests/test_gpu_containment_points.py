@@ -145,9 +145,9 @@ def built_program():
     return R.catalogue(importlib.import_module("sdf-viewer_amd.program"))["all_ops"].build()
 
 
-def launch(pkg, PM, entry, t, n):
-    """The call under test over the arena's tensors t[name]."""
-    prm = pkg.default_params()
+def launch(pkg, PM, entry, t, n, prm=None):
+    """The call under test over the arena's tensors t[name]; prm: the caller's sdfv_demo_params instead of fresh defaults."""
+    prm = pkg.default_params() if prm is None else prm
     if entry.startswith("program_"):
         prog = built_program()
     if entry == "sample_points":
