@@ -23,14 +23,15 @@
  *       enqueue-only, capturable:  sdfv_grid_init[_unvisited[_ex]], sdfv_fill_grid[_commit], sdfv_fill_grid_pass_ex,
  *         sdfv_commit_distance / _pairs / _interleaved, sdfv_pack_samples, sdfv_emit_update_points;
  *         sdfv_sample_points, sdfv_normal_points, sdfv_source_sample_scalar / _normal, sdfv_mesh_postproc;
- *         sdfv_lattice_points / _from_samples / _normals; sdfv_raymarch_slab[_round], sdfv_bands_scatter.
+ *         sdfv_lattice_points / _from_samples / _normals; sdfv_grid_vertex_materials; sdfv_raymarch_slab[_round],
+ *         sdfv_bands_scatter.
  *       enqueue-only after a first-use cost, capturable once that is paid:  every sdfv_program_* call with a stream
  *         (the program's device copy, synchronous, on the first use per device); sdfv_raymarch_ex (the camera ring
  *         of a HOST array of more than 16 cameras and the side streams of a batch that takes several launches --
  *         more than 64 cameras, or more than 16 where the ring is not used -- are made on the calling thread's
  *         first such call; under capture a host array goes out as launches of 16 instead).
- *       synchronise `stream`:  sdfv_mesh_extract, sdfv_program_mesh_extract, sdfv_lattice_mesh_extract (the output
- *         size is data dependent).  Not capturable.
+ *       synchronise `stream`:  sdfv_mesh_extract, sdfv_program_mesh_extract, sdfv_lattice_mesh_extract,
+ *         sdfv_grid_mesh_extract (the output size is data dependent).  Not capturable.
  *     The *_host forms take no stream and return when their result is in host memory; sdfv_slab_* and sdfv_comm_*
  *     say below what they enqueue on the communicator's own streams.
  *   - textures are RGBA32F, row-major with x fastest: flat = (z*H + y)*W + x (scene/sdf/mod.rs:177);
@@ -701,6 +702,47 @@ int sdfv_lattice_mesh_extract(const float *dist, const float bb_min[3], const fl
  * (step 1).  Not synchronised. */
 int sdfv_lattice_normals(const float *dist, const float bb_min[3], const float bb_max[3], uint32_t cells, sdfv_vertex *vertices,
                          size_t n, void *stream);
+
+/* ---- Meshing a loaded grid (the reference's GUI points the mesher at "the current root SDF", meshers/mod.rs:24-25; here the
+ * current SDF's samples are on the device) ----
+ * The same extractor over the grid a viewer has loaded, materials included, without sampling the SDF again.  The grid is read
+ * and never written; the caller has materialised it (no virgin rows, sdfv_grid_init_unvisited).
+ *   lattice    point (i, j, k) is voxel (i, j, k) * lod, n_a = (dims_a - 1) / lod + 1 points and cells_a = n_a - 1 cells per axis:
+ *              the points a load has published at step lod (LoadingManager::lattice_point).  Its distance is d = s - 0.1f, one
+ *              rounded f32 operation, s the stored distance of the voxel (0.1f: the float the fill adds, scene/sdf/mod.rs:196):
+ *              tex0.r, or the entry of the distance volume `dist` (volume_flags: its layout, 0 or SDFV_PASS_VOLUME_INTERLEAVED
+ *              -- H even, 8-byte aligned, as elsewhere).  So inside is s < 0.1f (up to the rounding of 0.1f + d), a voxel still at
+ *              AIR_DIST is outside, and the distances are the clamped ones, d in [-0.1, 0.9]: the surface as the viewer renders
+ *              it.  A vertex moves off the SDF's own crossing only on an edge one of whose ends was clamped, which needs an edge
+ *              longer than 0.1.
+ *   box        [bb_min, position of voxel cells_a * lod] per axis, that corner as the fill computes it: (float)idx / ((float)dims_a
+ *              - 1) * (bb_max_a - bb_min_a) + bb_min_a.  Where lod divides dims_a - 1 this is the grid's box up to the rounding of
+ *              (bb_max - bb_min) + bb_min.
+ *   inside, vertices, triangles, dual contouring, normal   sdfv_lattice_mesh_extract's over that lattice and box, with cells_a
+ *              in the place of cells on axis a: for a cubic grid the positions, normals and indices are the ones that call gives
+ *              for the unpacked lattice, bit for bit.
+ *   material   of a vertex at p (SDFV_MESH_WITH_MATERIALS; zero without it):
+ *     1. u, c, f per axis: steps 1-2 of normal(p) above
+ *     2. the nearest lattice point q_a = c_a + (f_a > 0.5f ? 1 : 0); its voxel is q * lod
+ *     3. that voxel's tex0 and tex1 texels
+ *     4. per colour channel x = tex0.g, .b, .a: idx = the number of entries of the 256-entry sRGB -> linear table that are < x
+ *        (at the most 255; 0 for a NaN), colour = (float)idx / 255.0f.  The table increases strictly, so for a texel the fill
+ *        wrote this is the 8-bit colour the fill quantised to, exactly.
+ *     5. metallic, roughness, occlusion = tex1.r, .g, .b as stored
+ *     These are the shader's own values (its nearest filter while a grid loads), not Mesh::postproc's on the SDF: the colours are
+ *     the 8-bit ones, a black sample arrives as the grid's 0.5 grey, occlusion <= 0 arrives as 1, and the material is the nearest
+ *     voxel's, not the vertex point's.
+ * Refused as SDFV_ERR_INVALID_ARGUMENT, before SDFV_ERR_NO_DEVICE: a slab (z_begin != 0, or z_end neither 0 nor dims[2]), a NULL
+ * tex0 or out (tex1 may be NULL only when flags == 0), unknown flags, a lod that is not a power of two, cells_a outside [1, 1024],
+ * a lattice of 2^32 points or more, an algorithm other than the two above ("Unsupported algorithm").  Synchronisation, ownership
+ * (sdfv_mesh_free) and the per-thread scratch (sdfv_mesh_trim) are sdfv_mesh_extract's. */
+/* Meshers::mesh + materials over a loaded grid's own samples. */
+int sdfv_grid_mesh_extract(const sdfv_grid *grid, const float *tex0, const float *tex1, const float *dist,
+                           uint32_t volume_flags, uint32_t lod, uint32_t algorithm, uint32_t flags,
+                           sdfv_mesh *out, void *stream);
+/* the material fields (and nothing else) of n vertices from the grid, rule as above; not synchronised */
+int sdfv_grid_vertex_materials(const sdfv_grid *grid, const float *tex0, const float *tex1, uint32_t lod,
+                               sdfv_vertex *vertices, size_t n, void *stream);
 
 /* ---- raymarch ----
  * ONE exported entry point, one descriptor: sdfv_raymarch_ex.  The forms earlier ABI versions exported one by one

@@ -276,6 +276,26 @@ def lattice_normals(dist, bb, cells, vertices, stream=None):
     return vertices
 
 
+def grid_mesh_extract(grid, tex0, tex1=None, dist=None, volume_flags=0, lod=1, algorithm=0, materials=False, stream=None):
+    """sdfv_grid_mesh_extract: Meshers::mesh over the grid's own samples, at the voxels a load has published at step `lod`.
+    dist: the compact distance volume (volume_flags: _capi.PASS_VOLUME_INTERLEAVED for the y-interleaved layout) or None (tex0.r is
+    read); materials: the vertices take the grid's material (tex1 is needed).  -> (vertices [n, 12], indices), as mesh_extract."""
+    m = _capi.Mesh()
+    check(lib.sdfv_grid_mesh_extract(C.byref(grid), _dev_ptr(tex0, "tex0"), None if tex1 is None else _dev_ptr(tex1, "tex1"),
+                                     None if dist is None else _dev_ptr(dist, "dist"), int(volume_flags), int(lod), int(algorithm),
+                                     _capi.MESH_WITH_MATERIALS if materials else 0, C.byref(m), _stream_ptr(stream)))
+    return mesh_tensors(m)
+
+
+def grid_vertex_materials(grid, tex0, tex1, vertices, lod=1, stream=None):
+    """sdfv_grid_vertex_materials, in place over an [n, 12] vertex tensor: the six material fields of each position from the
+    grid's nearest published voxel."""
+    assert vertices.dim() == 2 and vertices.shape[1] == VERTEX_FLOATS
+    check(lib.sdfv_grid_vertex_materials(C.byref(grid), _dev_ptr(tex0, "tex0"), _dev_ptr(tex1, "tex1"), int(lod),
+                                         _dev_ptr(vertices, "vertices"), vertices.shape[0], _stream_ptr(stream)))
+    return vertices
+
+
 def mesh_tensors(m):
     """An sdfv_mesh the library has just filled -> (vertices [n, 12] float32, indices [n_indices] int32) as torch tensors of
     their own; the library's copy is freed."""

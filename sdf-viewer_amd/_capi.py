@@ -212,6 +212,11 @@ PROTOTYPES = {
                                             C.c_uint32, C.POINTER(Mesh), C.c_void_p]),
     "sdfv_lattice_normals": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_size_t,
                                        C.c_void_p]),
+    # meshing a loaded grid
+    "sdfv_grid_mesh_extract": (C.c_int, [C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.POINTER(Mesh), C.c_void_p]),
+    "sdfv_grid_vertex_materials": (C.c_int, [C.POINTER(Grid), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                             C.c_void_p]),
 }
 MESH_WITH_MATERIALS = 1
 MESHER_MARCHING_CUBES = 0

@@ -8,6 +8,7 @@
 #include "program_mesh_kernels.h"
 #include "dual_contour_kernels.h"
 #include "lattice_mesh_kernels.h"
+#include "grid_mesh_kernels.h"
 
 using namespace sdfv;
 
@@ -33,16 +34,11 @@ thread_local MeshScratch g_mesh_scratch;  // freed by sdfv_mesh_trim(); a thread
 // normal and nothing else.  The scratch is the calling thread's one block.
 // An SDF kind whose attributes are cheap enough to write under the positions' sparse mask may also give
 // `fused(g, w, vertices, n, stream)`: marching cubes then calls it in the place of positions + attributes (the demo tree does).
+// The lattice is `g`: any number of cells per axis (MeshGrid::launchable).
 template <typename LatticeFn, typename AttributesFn, typename FusedFn = std::nullptr_t>
-int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis, uint32_t algorithm, sdfv_mesh* out,
-                 hipStream_t st, LatticeFn&& lattice, AttributesFn&& attributes, FusedFn&& fused = nullptr) {
+int extract_mesh(const sdfv::MeshGrid& g, uint32_t algorithm, sdfv_mesh* out, hipStream_t st, LatticeFn&& lattice,
+                 AttributesFn&& attributes, FusedFn&& fused = nullptr) {
     const bool dual = algorithm == SDFV_MESHER_DUAL_CONTOURING_PARTICLE;
-    sdfv::MeshGrid g;
-    for (int i = 0; i < 3; ++i) {
-        g.cells[i] = max_voxels_per_axis;
-        g.bb_min[i] = bb_min[i];
-        g.bb_size[i] = bb_max[i] - bb_min[i];
-    }
     const size_t n_points = g.n_points(), n_cells = g.n_cells();
     // One scratch block per host thread, grown on demand and kept between calls (allocating ~13 B per lattice point
     // afresh costs more than the extraction itself); sdfv_mesh_trim() gives it back.
@@ -113,6 +109,22 @@ int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxe
     }
     *out = m;
     return SDFV_OK;
+}
+
+// ... over the cube every mesher of the reference takes: max_voxels_per_axis cells on each axis of the box
+sdfv::MeshGrid lattice_grid(const float bb_min[3], const float bb_max[3], uint32_t cells) {
+    sdfv::MeshGrid g;
+    for (int i = 0; i < 3; ++i) {
+        g.cells[i] = cells;
+        g.bb_min[i] = bb_min[i];
+        g.bb_size[i] = bb_max[i] - bb_min[i];
+    }
+    return g;
+}
+template <typename LatticeFn, typename AttributesFn, typename FusedFn = std::nullptr_t>
+int extract_mesh(const float bb_min[3], const float bb_max[3], uint32_t max_voxels_per_axis, uint32_t algorithm, sdfv_mesh* out,
+                 hipStream_t st, LatticeFn&& lattice, AttributesFn&& attributes, FusedFn&& fused = nullptr) {
+    return extract_mesh(lattice_grid(bb_min, bb_max, max_voxels_per_axis), algorithm, out, st, lattice, attributes, fused);
 }
 
 }  // namespace
@@ -218,15 +230,6 @@ int check_lattice(const float* dist, const float bb_min[3], const float bb_max[3
     if (!bb_min || !bb_max) return set_error(SDFV_ERR_INVALID_ARGUMENT, "bounding box is NULL");
     return check_word_aligned("dist", dist);
 }
-sdfv::MeshGrid lattice_grid(const float bb_min[3], const float bb_max[3], uint32_t cells) {
-    sdfv::MeshGrid g;
-    for (int i = 0; i < 3; ++i) {
-        g.cells[i] = cells;
-        g.bb_min[i] = bb_min[i];
-        g.bb_size[i] = bb_max[i] - bb_min[i];
-    }
-    return g;
-}
 }  // namespace
 
 int sdfv_lattice_points(const float bb_min[3], const float bb_max[3], uint32_t cells, size_t first, size_t n, float* points,
@@ -279,6 +282,81 @@ int sdfv_lattice_mesh_extract(const float* dist, const float bb_min[3], const fl
         [&](sdfv_vertex* vertices, size_t n, bool final, hipStream_t st) {  // the zero material belongs to the output vertices
             return sdfv::launch_lattice_normals(dist, grid, vertices, n, final, st);
         });
+}
+
+// ---- meshing a loaded grid: the lattice is the grid's own voxels at step `lod`, the materials are its texels' ----
+namespace {
+// The checks both entry points share, and what they derive: the lattice (cells per axis, the sub-box [bb_min, position of voxel
+// cells * lod]) and where the kernels read.
+int grid_lattice_of(const sdfv_grid* grid, const float* tex0, const float* tex1, bool need_tex1, const float* dist,
+                    uint32_t volume_flags, uint32_t lod, sdfv::MeshGrid& g, sdfv::GridTexels& t) {
+    if (int rc = check_grid(grid)) return rc;
+    if (grid->z_begin != 0 || (grid->z_end != 0 && grid->z_end != grid->dims[2]))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "slab [%u,%u) of depth %u: meshing takes a whole grid", grid->z_begin, grid->z_end,
+                         grid->dims[2]);
+    if (!tex0 || (need_tex1 && !tex1)) return set_error(SDFV_ERR_INVALID_ARGUMENT, "texture pointer is NULL");
+    if (int rc = check_texel_alignment(tex0, tex1)) return rc;
+    if (int rc = check_word_aligned("dist", dist)) return rc;
+    if (volume_flags & ~SDFV_PASS_VOLUME_INTERLEAVED) return set_error(SDFV_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", volume_flags);
+    if (int rc = check_interleaved_volume(grid, dist, volume_flags)) return rc;
+    if (lod == 0 || (lod & (lod - 1u))) return set_error(SDFV_ERR_INVALID_ARGUMENT, "lod %u is not a power of two", lod);
+    for (int a = 0; a < 3; ++a) {
+        g.cells[a] = grid->dims[a] ? (grid->dims[a] - 1u) / lod : 0u;
+        if (g.cells[a] < 1 || g.cells[a] > 1024)
+            return set_error(SDFV_ERR_INVALID_ARGUMENT, "%u cells along axis %d (dims %u at lod %u) are outside [1, 1024]", g.cells[a], a,
+                             grid->dims[a], lod);
+        // voxel_coord of the lattice's last voxel: idx / (dim - 1) * size + min, three separately rounded steps
+        const float last = (float)(g.cells[a] * lod) / ((float)grid->dims[a] - 1.0f) * (grid->bb_max[a] - grid->bb_min[a]) + grid->bb_min[a];
+        g.bb_min[a] = grid->bb_min[a];
+        g.bb_size[a] = last - grid->bb_min[a];
+    }
+    if (g.n_points() > 0xffffffffull)
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "a lattice of %zu points is too large for one launch", g.n_points());
+    t.tex0 = reinterpret_cast<const float4*>(tex0);
+    t.tex1 = reinterpret_cast<const float4*>(tex1);
+    t.vol = dist;
+    t.ilv = (volume_flags & SDFV_PASS_VOLUME_INTERLEAVED) ? 1u : 0u;
+    t.W = grid->dims[0];
+    t.H = grid->dims[1];
+    t.lod = lod;
+    return SDFV_OK;
+}
+}  // namespace
+
+int sdfv_grid_mesh_extract(const sdfv_grid* grid, const float* tex0, const float* tex1, const float* dist, uint32_t volume_flags,
+                           uint32_t lod, uint32_t algorithm, uint32_t flags, sdfv_mesh* out, void* stream) {
+    if (!out) return set_error(SDFV_ERR_INVALID_ARGUMENT, "out is NULL");
+    memset(out, 0, sizeof(*out));
+    if (flags & ~SDFV_MESH_WITH_MATERIALS) return set_error(SDFV_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
+    const bool materials = (flags & SDFV_MESH_WITH_MATERIALS) != 0;
+    sdfv::MeshGrid g{};
+    sdfv::GridTexels t{};
+    if (int rc = grid_lattice_of(grid, tex0, tex1, materials, dist, volume_flags, lod, g, t)) return rc;
+    if (int rc = check_mesher(algorithm, g.cells[0])) return rc;
+    if (int rc = need_device()) return rc;
+    const float* lattice = nullptr;
+    return extract_mesh(
+        g, algorithm, out, (hipStream_t)stream,
+        [&](const sdfv::MeshGrid&, const sdfv::MeshWork& w, hipStream_t st) {
+            lattice = w.dist;
+            return sdfv::launch_grid_lattice(t, g, w.dist, st);
+        },
+        [&](sdfv_vertex* vertices, size_t n, bool final, hipStream_t st) {  // the materials belong to the output vertices only
+            if (final && materials) return sdfv::launch_grid_normals_materials(lattice, t, g, vertices, n, st);
+            return sdfv::launch_lattice_normals(lattice, g, vertices, n, final, st);
+        });
+}
+
+int sdfv_grid_vertex_materials(const sdfv_grid* grid, const float* tex0, const float* tex1, uint32_t lod, sdfv_vertex* vertices,
+                               size_t n, void* stream) {
+    sdfv::MeshGrid g{};
+    sdfv::GridTexels t{};
+    if (int rc = grid_lattice_of(grid, tex0, tex1, true, nullptr, 0, lod, g, t)) return rc;
+    if (int rc = check_point_buffers(vertices, vertices, n)) return rc;
+    if (int rc = check_word_aligned("vertices", vertices)) return rc;
+    if (n > 0xffffffffull) return set_error(SDFV_ERR_INVALID_ARGUMENT, "%zu vertices are too many for one launch", n);
+    if (int rc = need_device()) return rc;
+    SDFV_HIP_RETURN(sdfv::launch_grid_vertex_materials(t, g, vertices, n, (hipStream_t)stream));
 }
 
 int sdfv_mesh_trim(void) {

@@ -2,6 +2,7 @@
 //
 //   sdf-viewer-gpu app [--max-voxels-side N] [--loading-passes P] demo [-t M] [-c F] [-l M] [-s F] [-m F] [-d B]
 //                  [--width W] [--height H] [--out image.ppm] [--dump-textures prefix] [--frames K] [--lod-filter nearest|linear]
+//                  [--mesh-out grid.ply] [--mesher marching-cubes]
 //   sdf-viewer-gpu app [...] url <library.so | file://library.so>
 //
 // `url` is the reference's second provider (CliSDFProvider::Url, src/app/cli/mod.rs:41-46: a WebAssembly file exporting the
@@ -46,6 +47,7 @@ static int usage(const char* msg) {
     fprintf(stderr,
             "USAGE:\n    sdf-viewer-gpu app [--max-voxels-side <N>] [--loading-passes <P>] demo [demo flags]\n"
             "                   [--width <W>] [--height <H>] [--out <file.ppm>] [--dump-textures <prefix>] [--frames <K>]\n"
+            "                   [--mesh-out <file.ply>] [--mesher <NAME>]   the PLY of the loaded grid (SDFViewer::mesh)\n"
             "                   [--lod-filter <nearest|linear>]   how a grid that is still loading is sampled (default nearest); this\n"
             "                                                     program renders after the load has finished, so its frame does not change\n"
             "    sdf-viewer-gpu app [...] url <library.so>      a native SDF provider (include/sdf_provider.h), sampled on the host\n"
@@ -161,7 +163,8 @@ int main(int argc, char** argv) {
     size_t max_voxels_side = 64, loading_passes = 2;  // src/app/cli/mod.rs:13-18
     uint32_t width = 1280, height = 720;
     int frames = 1;
-    std::string out = "sdf-viewer-gpu.ppm", dump, url, lod_filter = "nearest";
+    std::string out = "sdf-viewer-gpu.ppm", dump, url, lod_filter = "nearest", mesh_out;
+    Meshers mesher = Meshers::MarchingCubes;
     std::vector<std::string> demo_args;
     bool in_demo = false;
     for (size_t i = 1; i < args.size(); ++i) {
@@ -180,6 +183,13 @@ int main(int argc, char** argv) {
         else if (a == "--frames") frames = atoi(next("--frames"));
         else if (a == "--out") out = next("--out");
         else if (a == "--dump-textures") dump = next("--dump-textures");
+        else if (a == "--mesh-out") mesh_out = next("--mesh-out <FILE>");
+        else if (a == "--mesher") {
+            const std::string name = next("--mesher <NAME>");
+            const auto m = mesher_from_name(name);
+            if (!m) return usage(("--mesher: '" + name + "' is not a mesher").c_str());
+            mesher = *m;
+        }
         else if (a == "--lod-filter") lod_filter = next("--lod-filter <nearest|linear>");
         else if (a == "demo") in_demo = true;
         else if (a == "url") url = next("url <URL>");
@@ -212,6 +222,10 @@ int main(int argc, char** argv) {
         fprintf(stderr, "error: no HIP device visible: sdf-viewer-gpu has no CPU path\n");
         return 1;
     }
+    if (!mesh_out.empty() && std::ifstream(mesh_out).good()) {  // before anything is loaded, as `mesh` does
+        fprintf(stderr, "Error: Output file already exists\n");  // meshers/mod.rs:52-54
+        return 1;
+    }
     // set_root_sdf -> scene.set_sdf -> SDFViewer::from_bb (app/mod.rs:99-109, scene/mod.rs:139-156)
     auto viewer = SDFViewer::from_bb(sdf->bounding_box(), max_voxels_side, loading_passes);
     if (!viewer) {
@@ -234,6 +248,25 @@ int main(int argc, char** argv) {
     }
     viewer->commit();
     fprintf(stderr, "Loaded last SDF chunk (lod %g)\n", (double)viewer->material.lod_dist_between_samples);
+
+    if (!mesh_out.empty()) {  // the grid the frames below show, materials from its texels: no sample is taken again
+        const auto t0 = std::chrono::steady_clock::now();
+        Mesh mesh;
+        if (!viewer->mesh(mesher, true, &mesh, &err)) {
+            fprintf(stderr, "error: %s\n", err.c_str());
+            return 1;
+        }
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        fprintf(stderr, "Meshed the loaded grid (%zu vertices, %zu triangles) in %.3fms on the GPU\n", mesh.vertices.size(),
+                mesh.indices.size() / 3, ms);
+        std::ofstream f(mesh_out, std::ios::binary | std::ios::trunc);
+        if (!f) {
+            perror(mesh_out.c_str());
+            return 1;
+        }
+        const size_t bytes = mesh.serialize_ply(f, "sdf-viewer-gpu 0.1.0 (MI355X)");
+        fprintf(stderr, "Wrote %zu bytes to %s\n", bytes, mesh_out.c_str());
+    }
 
     Camera cam;  // scene/mod.rs:82-95 defaults
     cam.set_viewport(width, height);

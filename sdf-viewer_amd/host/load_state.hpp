@@ -100,6 +100,16 @@ class LoadState {
     uint32_t layout_flag() const { return volume_ && m_.dist_interleaved ? SDFV_PASS_VOLUME_INTERLEAVED : 0u; }
     bool has_volume() const { return volume_; }
 
+    // Meshing the loaded grid (SDFViewer::mesh): where the lattice's distances are read.  The volume, where it exists, equals
+    // tex0.r after every fill, pass, pack and materialisation, at every LOD -- 4 B/voxel against tex0's 16; without one, tex0.
+    struct MeshSource {
+        bool volume;
+        uint32_t layout;  // SDFV_PASS_VOLUME_INTERLEAVED or 0
+    };
+    MeshSource mesh_source() const { return MeshSource{volume_, layout_flag()}; }
+    // ... and whether the rows no pass has reached must be written first: the extraction reads every published voxel's texels.
+    bool mesh_materializes_first() const { return m_.undefined_rows; }
+
     // Does `box` contain every voxel of the grid?  Decided on the voxels' own coordinates, first and last index per axis.  A NaN
     // (a bound, or the 0/0 of an axis with one voxel) fails every comparison: not covered.
     static bool box_covers_grid(const sdfv_grid& g, const BoundingBox& box) {

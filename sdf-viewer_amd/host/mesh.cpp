@@ -23,8 +23,6 @@ std::optional<Meshers> mesher_from_name(const std::string& k) {
     return std::nullopt;
 }
 
-namespace {
-
 // The device mesh an extraction has just returned -> a host Mesh; the library's copy is freed either way.
 std::optional<Mesh> take_mesh(sdfv_mesh& m, std::string* err) {
     Mesh out;
@@ -46,6 +44,8 @@ std::optional<uint32_t> device_algorithm(Meshers mesher) {
     if (mesher == Meshers::DualContouringParticleBasedMinimization) return SDFV_MESHER_DUAL_CONTOURING_PARTICLE;
     return std::nullopt;  // isosurface.rs:49
 }
+
+namespace {
 
 std::string describe(std::exception_ptr e) {
     try {

@@ -62,6 +62,12 @@ std::optional<Mesh> mesh_any_sdf(Meshers mesher, const SDFSurface& sdf, const Me
 // throws passes through.  Returns 0 or the sdfv status.
 int postproc_any(Mesh& mesh, const SDFSurface& sdf);
 
+// What every route to a host Mesh shares (SDFViewer::mesh, sdf_viewer.cpp, is the fourth): the device extractor's number of a
+// mesher, nullopt for the two without a device implementation ("Unsupported algorithm", isosurface.rs:49), and the device mesh
+// an extraction has just returned -> a host Mesh; the library's copy is freed either way.
+std::optional<uint32_t> device_algorithm(Meshers mesher);
+std::optional<Mesh> take_mesh(sdfv_mesh& m, std::string* err);
+
 // f32 Display as Rust prints it (shortest digits that round-trip, never an exponent): what ply-rs writes for floats.
 std::string format_f32(float v);
 // (c * 255.9999) as u8, mesh.rs:106-108

@@ -317,6 +317,44 @@ void SDFViewer::commit() {
     }
 }
 
+int SDFViewer::mesh_device(uint32_t algorithm, uint32_t flags, sdfv_mesh* out) {
+    if (out) *out = sdfv_mesh{};
+    if (load_.mesh_materializes_first()) {
+        if (const int rc = material.materialize(stream)) {  // its own status goes through
+            error_ = sdfv_last_error();
+            return rc;
+        }
+    }
+    // 2^passes_left as a float: a step a grid can have fits 32 bits (the conversion of anything else is not defined)
+    const float published = material.lod_dist_between_samples;
+    if (!(published >= 1.0f && published <= 2147483648.0f)) {
+        error_ = "lod_dist_between_samples " + std::to_string(published) + " is no step of a grid";
+        return SDFV_ERR_INVALID_ARGUMENT;
+    }
+    const LoadState::MeshSource src = load_.mesh_source();
+    const sdfv_grid g = grid();
+    const int rc = sdfv_grid_mesh_extract(&g, tex0_device(), tex1_device(), src.volume && material.dist ? material.dist->f32() : nullptr,
+                                          src.volume && material.dist ? src.layout : 0u, (uint32_t)published, algorithm, flags, out, stream);
+    if (rc != SDFV_OK) error_ = sdfv_last_error();
+    return rc;
+}
+
+bool SDFViewer::mesh(Meshers mesher, bool with_materials, Mesh* out, std::string* err) {
+    auto fail = [&](const std::string& m) {
+        if (err) *err = m;
+        return false;
+    };
+    if (!out) return fail("out is NULL");
+    const auto algorithm = device_algorithm(mesher);
+    if (!algorithm) return fail("Unsupported algorithm");
+    sdfv_mesh m{};
+    if (mesh_device(*algorithm, with_materials ? SDFV_MESH_WITH_MATERIALS : 0u, &m) != SDFV_OK) return fail(error_);
+    auto host = take_mesh(m, err);
+    if (!host) return false;
+    *out = std::move(*host);
+    return true;
+}
+
 int SDFViewer::download(float* tex0_host, float* tex1_host) const {
     if (material.materialize(stream) != 0) return -1;  // a virgin grid shows new_voxels' [AIR_DIST; 4] like any other
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return -1;

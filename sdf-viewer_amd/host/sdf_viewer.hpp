@@ -25,6 +25,7 @@
 
 #include "load_state.hpp"
 #include "loading_manager.hpp"
+#include "mesh.hpp"
 #include "sdf_surface.hpp"
 
 namespace sdfviewer {
@@ -155,6 +156,15 @@ class SDFViewer {
     float* tex0_device() const { return material.tex0->f32(); }
     float* tex1_device() const { return material.tex1->f32(); }
     int download(float* tex0_host, float* tex1_host) const;  // D2H copy of both textures (debug / GL interop)
+    // Meshers::mesh over the grid as it is loaded NOW (the reference's GUI meshes "the current root SDF", meshers/mod.rs:24-25;
+    // here its samples are on the device): sdfv_grid_mesh_extract over the voxels published at the current
+    // lod_dist_between_samples, on the viewer's stream, read from the volume and layout LoadState says are valid (tex0
+    // otherwise), the rows no pass has reached materialised first.  with_materials: the vertices take the grid's material
+    // (include/sdfgrid.h, "Meshing a loaded grid") -- no postproc is needed, and none could give these values.  Not while an
+    // update() is running.  false on error, text in *err.
+    bool mesh(Meshers mesher, bool with_materials, Mesh* out, std::string* err);
+    // ... the device mesh itself (sdfv_mesh_free): algorithm and flags as sdfv_grid_mesh_extract takes them; returns its status.
+    int mesh_device(uint32_t algorithm, uint32_t flags, sdfv_mesh* out);
     const char* last_error() const { return error_.c_str(); }  // of the most recent update(): "" when it went through
     // An update() that threw: the LoadingManager iterations it had consumed (and packed) before the run that failed.
     size_t visited_before_throw() const { return visited_before_throw_; }

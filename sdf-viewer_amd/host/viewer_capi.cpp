@@ -14,6 +14,7 @@
 
 #include "../../include/sdfprogram.h"
 #include "../../include/sdfviewer.h"
+#include "../../include/sdfviewer_mesh.h"
 #include "program_editor.hpp"
 #include "scene.hpp"
 #include "sdf_viewer.hpp"
@@ -258,6 +259,17 @@ int sdfv_viewer_update_program(sdfv_viewer* v, sdfv_program_editor* e, uint64_t 
         v->err = "editor is NULL";
         rc = SDFV_ERR_INVALID_ARGUMENT;
         return nullptr;
+    });
+}
+
+// include/sdfviewer_mesh.h: SDFViewer::mesh_device
+int sdfv_viewer_mesh(sdfv_viewer* v, uint32_t algorithm, uint32_t flags, sdfv_mesh* out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!v || !v->v || !out) return SDFV_ERR_INVALID_ARGUMENT;
+    return guarded(v->err, [&] {
+        const int rc = v->v->mesh_device(algorithm, flags, out);
+        if (rc != SDFV_OK) v->err = v->v->last_error();
+        return rc;
     });
 }
 

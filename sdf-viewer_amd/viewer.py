@@ -88,6 +88,9 @@ def load(path=LIB_PATH):
 
 
 lib = load()
+# include/sdfviewer_mesh.h: the viewer's mesh call, beside sdfviewer.h's (PROTOTYPES is that header's list)
+lib.sdfv_viewer_mesh.restype = C.c_int
+lib.sdfv_viewer_mesh.argtypes = [VP, C.c_uint32, C.c_uint32, C.POINTER(_capi.Mesh)]
 
 
 def _check(rc, message):
@@ -244,6 +247,15 @@ class Viewer:
         t0, t1 = np.empty(shape, np.float32), np.empty(shape, np.float32)
         _check(lib.sdfv_viewer_download(self.h, t0.ctypes.data, t1.ctypes.data), lib.sdfv_viewer_last_error(self.h))
         return t0, t1
+
+    def mesh(self, algorithm=0, materials=True):
+        """sdfv_viewer_mesh: the grid as it is loaded now -> (vertices [n, 12] float32, indices int32) torch tensors on the GPU
+        (the library's copy is freed)."""
+        from . import mesh_tensors
+        m = _capi.Mesh()
+        _check(lib.sdfv_viewer_mesh(self.h, int(algorithm), _capi.MESH_WITH_MATERIALS if materials else 0, C.byref(m)),
+               lib.sdfv_viewer_last_error(self.h))
+        return mesh_tensors(m)
 
     def render(self, width, height, view=None):
         """-> [height, width, 4] float32 tensor on the GPU."""
