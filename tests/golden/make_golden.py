@@ -15,7 +15,12 @@ oracle they are used to pin:
   3. raymarch_12cube_40x30.npz -- the same kind of restatement of material.frag (sphere tracing, texel-centre
                             trilinear, ambient shading, ACES, sRGB) for two cameras over a 12^3 grid.
 
-Run from the repo root:  python tests/golden/make_golden.py
+  4. mesh_ref_pins.json  -- sha256 digests of what the mesh restatement of tests/ (tests/mesh_ref.py behind the adapter of
+                            every SDF kind) returns on the inputs the GPU parity tests use; tests/test_mesh_ref_pins.py
+                            holds the restatement to them.  Needs oracle/liboracle.so (the demo tree's distances).
+
+Run from the repo root:  python tests/golden/make_golden.py            (everything)
+                         python tests/golden/make_golden.py mesh_ref_pins   (the digests alone)
 """
 import json
 import os
@@ -371,7 +376,100 @@ def make_raymarch_fixture():
     np.savez_compressed(os.path.join(HERE, "raymarch_12cube_40x30.npz"), tex0=tex0, tex1=tex1, width=W, height=H, **out)
 
 
+# ---------------------------------------------------------------------------------------------------------
+# mesh_ref_pins.json: what the mesh restatements of tests/ return, as sha256 digests.  Recorded results only.
+# ---------------------------------------------------------------------------------------------------------
+PIN_BOX = (-1.0, -1.0, -1.0, 1.0, 1.0, 1.0)
+PIN_SLAB_BOX = (-1.0, -0.5, -0.75, 1.0, 0.5, 0.75)
+PIN_DEMO_ROWS = [                                                    # tests/test_gpu_mesh_extract.py's four rows
+    (2, dict(sphere_radius=0.8), ((-1, -1, -1), (1, 1, 1)), 12),
+    (0, dict(), ((-1, -1, -1), (1, 1, 1)), 16),
+    (1, dict(cube_half_side=0.6), ((-1.0, -0.75, -1.25), (1.0, 1.0, 0.5)), 9),
+    (0, dict(cube_half_side=0.7, sphere_radius=0.8), ((-1, -1, -1), (1, 1, 1)), 11),
+]
+
+
+def digest(*arrays):
+    """sha256 over the raw bytes of the arrays in the order given: floats as float32, integers as int64."""
+    import hashlib
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.asarray(a)
+        h.update(np.ascontiguousarray(a, np.float32 if a.dtype.kind == "f" else np.int64).tobytes())
+    return h.hexdigest()
+
+
+def mesh_digest(v, i, info):
+    """vertices, indices, then `cases` (marching cubes) or `hermite, cells, mass, used, edges` (dual contouring)."""
+    names = ("hermite", "cells", "mass", "used", "edges") if "hermite" in info else ("cases",)
+    assert v.ndim == 2 and v.shape[1] == 12 and len(v) > 20 and len(i) > 20
+    return digest(v, i, *[info[k] for k in names])
+
+
+def mesh_ref_pin_cases():
+    """name -> a function without arguments that returns the case's digest: every route into tests/mesh_ref.py, on the inputs the
+    GPU parity tests use.  The committed digests were recorded from the restatements as they stood before mesh_ref.py (one copy
+    per SDF kind; the demo's marching cubes from scalar loops written independently of the vectorised ones)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(HERE))
+    import demo_mesh_ref as DM
+    import grid_mesh_ref as G
+    import lattice_mesh_ref as L
+    import mesh_ref as MR
+    import oracle_binding as oracle
+    import program_mesh_ref as M
+    import program_ref as R
+    cases = {}
+    programs = {"cube": ((R.CUBE, (0.6,)),), "cube-sphere": ((R.CUBE, (0.6,)), (R.SPHERE, (0.7,)), (R.SUBTRACT, ()))}
+    for name, ops in programs.items():
+        for algorithm in (0, MR.DUAL):
+            for materials in (False, True):
+                cases[f"program-{name}-{algorithm}-{'materials' if materials else 'plain'}"] = \
+                    lambda ops=ops, algorithm=algorithm, materials=materials: mesh_digest(*M.extract(ops, 12, PIN_BOX, materials, algorithm))
+    lattices = {"gyroid9": lambda: (L.gyroid_lattice(9, PIN_BOX), PIN_BOX), "gyroid12slab": lambda: (L.gyroid_lattice(12, PIN_SLAB_BOX), PIN_SLAB_BOX),
+                "sphere9": lambda: (L.sphere_lattice(9, PIN_BOX), PIN_BOX)}
+    for name, make in lattices.items():
+        for algorithm in (0, MR.DUAL):
+            cases[f"lattice-{name}-{algorithm}"] = lambda make=make, algorithm=algorithm: mesh_digest(*L.extract(*make(), algorithm))
+    for name, n in (("gyroid9", 9), ("gyroid12slab", 12)):
+        def normals(make=lattices[name], n=n):
+            p = np.random.default_rng(n).uniform(-1.5, 1.5, size=(500, 3)).astype(F)
+            return digest(MR.lattice_normals(*make(), p))
+        cases[f"lattice_normals-{name}"] = normals
+
+    def per_axis(algorithm):
+        cells, bb = (8, 6, 4), (-1.0, -0.9, -0.8, 1.0, 0.9, 0.8)
+        _, _, _, axes = MR.axes_of(cells, bb)
+        zz, yy, xx = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+        d = (np.sqrt(xx.astype(np.float64) ** 2 + yy ** 2 + zz ** 2) - 0.6).astype(F)
+        return mesh_digest(*L.extract(d, bb, algorithm))
+
+    for algorithm in (0, MR.DUAL):
+        cases[f"per_axis-sphere8x6x4-{algorithm}"] = lambda algorithm=algorithm: per_axis(algorithm)
+        for lod in (1, 2):
+            cases[f"grid-9x8x5-lod{lod}-{algorithm}"] = lambda algorithm=algorithm, lod=lod: mesh_digest(
+                *G.extract(*G.synthetic_grid((9, 8, 5), PIN_BOX, lod), PIN_BOX, lod, algorithm))
+    for row, (sdf_id, kw, box, n) in enumerate(PIN_DEMO_ROWS):
+        cases[f"demo-row{row}-0"] = lambda sdf_id=sdf_id, kw=kw, box=box, n=n: mesh_digest(
+            *DM.extract_demo(oracle, oracle.default_params(**kw), n, box, sdf_id, 0))
+    cases[f"demo-default9-{MR.DUAL}"] = lambda: mesh_digest(
+        *DM.extract_demo(oracle, oracle.default_params(), 9, ((-1, -1, -1), (1, 1, 1)), 0, MR.DUAL))
+    return cases
+
+
+def make_mesh_ref_pins():
+    pins = {name: case() for name, case in mesh_ref_pin_cases().items()}
+    with open(os.path.join(HERE, "mesh_ref_pins.json"), "w") as f:
+        json.dump(pins, f, indent=1)
+        f.write("\n")
+    print("wrote", len(pins), "digests to mesh_ref_pins.json")
+
+
 def main():
+    import sys
+    if sys.argv[1:] == ["mesh_ref_pins"]:
+        return make_mesh_ref_pins()
+    make_mesh_ref_pins()
     make_raymarch_fixture()
     make_mesh_front_fixture()
     with open(os.path.join(HERE, "demo_sdf_kat.json"), "w") as f:

@@ -27,10 +27,11 @@ def voxel_positions(dims, bb_min, bb_max):
 
 
 def interleave(vol):
-    """texture-order volume [D, H, W] -> the y-interleaved layout (entry ((row >> 1) * W + x) * 2 + (row & 1))"""
+    """texture-order volume [D, H, W], a numpy array or a torch tensor -> the y-interleaved layout as a flat contiguous one: entry
+    ((row >> 1) * W + x) * 2 + (row & 1), row = z * H + y.  The one restatement of the layout for every test."""
     D, H, W = vol.shape
-    rows = vol.reshape(D * H // 2, 2, W)
-    return np.ascontiguousarray(rows.transpose(0, 2, 1)).reshape(-1)
+    assert H % 2 == 0
+    return vol.reshape(D * H // 2, 2, W).swapaxes(1, 2).reshape(-1)
 
 
 def expected_textures(pkg, grid, dims, samples, srgb, layout):

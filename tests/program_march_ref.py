@@ -20,12 +20,13 @@ SIZES = ((160, 120), (67, 41))
 
 
 def srgb_table():
-    """sRGB u8 -> linear, the 256 floats the library compiles in (held to the oracle's by tests/test_abi.py)."""
+    """sRGB u8 -> linear, the 256 floats of sdf-viewer_amd/csrc/srgb_lut.inc that the library compiles in (C99 hexadecimal floats:
+    exact; held to the oracle's by tests/test_abi.py).  The one parser of that file: tests/grid_mesh_ref.py inverts this table."""
     text = open(os.path.join(ROOT, "sdf-viewer_amd", "csrc", "srgb_lut.inc")).read()
-    text = re.sub(r"//.*|/\*.*?\*/", "", text, flags=re.S)
-    vals = [F(float.fromhex(t) if "x" in t.lower() else float(t)) for t in re.findall(r"[-+0-9.eExXa-fA-FpP]+(?=f?\s*,|f?\s*$)", text, flags=re.M)]
-    assert len(vals) == 256, len(vals)
-    return np.array(vals, F)
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    t = np.array([float.fromhex(x) for x in re.findall(r"[-+]?0x[0-9a-fA-F.]+p[-+]?\d+", text)], np.float64)
+    assert t.shape == (256,) and (t.astype(F) == t).all()
+    return t.astype(F)
 
 
 def cam_fields(cam):

@@ -56,13 +56,6 @@ def expected(before, dense, mask, air, volume):
     return t0, t1, t0[..., 0].copy()
 
 
-def interleave(vol):
-    """texture-order volume [D, H, W] -> the y-interleaved layout (entry ((row >> 1) * W + x) * 2 + (row & 1))"""
-    D, H, W = vol.shape
-    rows = vol.reshape(D * H // 2, 2, W)
-    return np.ascontiguousarray(rows.transpose(0, 2, 1)).reshape(-1)
-
-
 def boxes(step, dims=DIMS, bb_min=BB_MIN, bb_max=BB_MAX):
     """name -> (box, what the mask inside the lattice must be: "some", "none" or "all") for a loaded grid."""
     cx, cy, cz = axis_coords(dims, bb_min, bb_max)

@@ -1,6 +1,6 @@
 """CPU tests of dual contouring (include/sdfgrid.h, "Dual contouring"; SDFV_MESHER_DUAL_CONTOURING_PARTICLE = 4): what the entry
 points accept and refuse without a device, the sanity of the numpy restatement the GPU tests compare against
-(tests/dual_contour_ref.py) on geometry whose answer is known, and what the built kernels look like.  No device needed."""
+(tests/mesh_ref.py through tests/program_mesh_ref.py and tests/demo_mesh_ref.py) on geometry whose answer is known, and what the built kernels look like.  No device needed."""
 import ctypes as C
 import functools
 import importlib
@@ -11,7 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
-import dual_contour_ref as D
+import demo_mesh_ref as DM
+import mesh_ref as MR
 import program_mesh_ref as M
 import program_ref as R
 from kernel_objects import code_objects, disassembly, kernel_table  # noqa: F401 (code_objects is a fixture)
@@ -27,7 +28,7 @@ def PM(pkg):
 
 
 def test_the_constant_is_the_reference_algorithm_number(pkg):
-    assert pkg.MESHER_DUAL_CONTOURING_PARTICLE == pkg._capi.MESHER_DUAL_CONTOURING_PARTICLE == D.DUAL == 4
+    assert pkg.MESHER_DUAL_CONTOURING_PARTICLE == pkg._capi.MESHER_DUAL_CONTOURING_PARTICLE == MR.DUAL == 4
     assert pkg.MESHER_MARCHING_CUBES == 0
     header = open(os.path.join(ROOT, "include", "sdfgrid.h")).read()
     assert re.search(r"#define SDFV_MESHER_DUAL_CONTOURING_PARTICLE 4u\b", header)
@@ -89,7 +90,7 @@ def test_cpp_host_refuses_host_only_surfaces_and_the_two_other_meshers(tmp_path)
 # ---- the restatement against geometry: it is the yardstick of tests/test_gpu_dual_contour.py ----
 @functools.lru_cache(maxsize=None)
 def restated(kind, size, n):
-    v, i, s = D.extract_program(D.primitive(kind, size), n, BOX)
+    v, i, s = M.extract(M.primitive(kind, size), n, BOX, algorithm=MR.DUAL)
     v.setflags(write=False)
     i.setflags(write=False)
     return v, i, s
@@ -100,7 +101,7 @@ def test_the_hermite_records_are_the_marching_cubes_vertices(PM):
     normals: the Hermite data is what is already pinned."""
     b = R.catalogue(PM)["deep"]
     mv, _, _ = M.extract(b.ops, 12, b.bb)
-    _, _, s = D.extract_program(b.ops, 12, b.bb)
+    _, _, s = M.extract(b.ops, 12, b.bb, algorithm=MR.DUAL)
     assert mv.shape[0] == 173 and (M.bits(mv[:, :6]) == M.bits(s["hermite"])).all()
 
 
@@ -134,7 +135,7 @@ def test_a_sphere_stays_within_the_second_order_bound(n):
 def test_restated_meshes_are_closed_and_face_outward(kind, size, n):
     v, i, _ = restated(kind, size, n)
     assert i.min() == 0 and i.max() == v.shape[0] - 1 and len(np.unique(i)) == v.shape[0]
-    D.assert_closed_and_oriented(i)
+    MR.assert_closed_and_oriented(i)
     tri = v[i.reshape(-1, 3), :3].astype(np.float64)
     face_n = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
     solid = np.linalg.norm(face_n, axis=1) > 1e-12                     # a quad on a crease may fold one triangle to a line
@@ -152,9 +153,9 @@ def test_restated_meshes_are_closed_and_face_outward(kind, size, n):
 def test_the_restated_demo_is_closed(oracle):
     """The demo (cube 0.95 - sphere 1.05) at 24 cells, from the oracle's distances and normals."""
     prm = oracle.default_params()
-    v, i, s = D.extract_demo(oracle, prm, 24, ((-1, -1, -1), (1, 1, 1)))
+    v, i, s = DM.extract_demo(oracle, prm, 24, ((-1, -1, -1), (1, 1, 1)), algorithm=MR.DUAL)
     assert v.shape[0] == 4528 and i.shape[0] == 3 * 9072
-    D.assert_closed_and_oriented(i)
+    MR.assert_closed_and_oriented(i)
     assert np.isfinite(v).all()
 
 

@@ -13,6 +13,7 @@ import pytest
 
 import arena as A
 import grid_mesh_ref as G
+from program_fill_check import interleave
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -45,7 +46,7 @@ def test_grid_mesh_extract_reads_the_grid_only(pkg, lod, source, algorithm):
     if source == "volume":
         dist = ar.input(vol, align=4, misalign=4, name="dist")
     elif source == "interleaved":
-        dist = ar.input(G.interleave(vol), align=8, name="dist")
+        dist = ar.input(interleave(vol), align=8, name="dist")
     grid = pkg.make_grid(DIMS, BB[:3], BB[3:])
     meshes = []
 

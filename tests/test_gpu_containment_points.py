@@ -11,6 +11,7 @@ import pytest
 
 import arena as A
 import lattice_mesh_ref as LM
+import mesh_ref as MR
 import program_mesh_ref as M
 import program_ref as R
 
@@ -120,7 +121,7 @@ def reference(entry):
         assert_postproc_contract(v, want)
         return {}, {"vertices": v}, {"vertices": want}
     if entry == "lattice_points":
-        return {}, {}, {"out": LM.lattice_points(CELLS, BB)[FIRST:FIRST + SIZES[-1]]}
+        return {}, {}, {"out": MR.lattice_points(CELLS, BB)[FIRST:FIRST + SIZES[-1]]}
     if entry == "lattice_from_samples":
         s = oracle.sample_many(prm, pts)
         return {"samples": s}, {}, {"out": np.ascontiguousarray(s[:, 0])}
@@ -128,7 +129,7 @@ def reference(entry):
         d = LM.gyroid_lattice(CELLS, BB)
         v = vertices_over(pts, 7)   # positions inside and outside the box (the border cell's values)
         want = v.copy()
-        want[:, 3:6] = LM.normals(d, BB, v[:, :3])
+        want[:, 3:6] = MR.lattice_normals(d, BB, v[:, :3])
         assert np.isfinite(want).all()
         return {"dist": np.ascontiguousarray(d, F).reshape(-1)}, {"vertices": v}, {"vertices": want}
     raise KeyError(entry)

@@ -1,5 +1,5 @@
 """Dual contouring on the device (include/sdfgrid.h, "Dual contouring"; algorithm 4) against the numpy restatement of
-tests/dual_contour_ref.py, bit for bit, for SDF programs and for the demo tree: positions, normals, materials, indices; a
+tests/mesh_ref.py (through tests/program_mesh_ref.py and tests/demo_mesh_ref.py), bit for bit, for SDF programs and for the demo tree: positions, normals, materials, indices; a
 program whose gradient vanishes on its surface, an empty surface, a box that cuts the surface, the fused materials, the shared
 scratch, the C++ host and the CLI."""
 import functools
@@ -11,14 +11,15 @@ import numpy as np
 import pytest
 import torch
 
-import dual_contour_ref as D
+import demo_mesh_ref as DM
+import mesh_ref as MR
 import program_mesh_ref as M
 import program_ref as R
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-DUAL = D.DUAL
+DUAL = MR.DUAL
 UNIT_BOX = ((-1, -1, -1), (1, 1, 1))
 
 
@@ -47,7 +48,7 @@ def built(cat):
 def _restated(name, n, materials):
     PM = importlib.import_module("sdf-viewer_amd.program")
     b = R.catalogue(PM)[name]
-    return D.extract_program(b.ops, n, b.bb, materials)
+    return M.extract(b.ops, n, b.bb, materials, DUAL)
 
 
 def restated(name, n, materials=False):
@@ -110,7 +111,7 @@ def test_programs_are_the_restatement_bit_for_bit(built, name, n):
 ])
 def test_the_demo_tree_is_the_restatement_bit_for_bit(pkg, oracle, kw, n, box, sdf_id, count):
     prm = pkg.default_params(**kw)
-    want_v, want_i, s = D.extract_demo(oracle, oracle.params_from(prm), n, box, sdf_id)
+    want_v, want_i, s = DM.extract_demo(oracle, oracle.params_from(prm), n, box, sdf_id, DUAL)
     assert (want_v.shape[0], s["quads"]) == count
     got_v, got_i = arrays(*pkg.mesh_extract(prm, n, *box, sdf_id=sdf_id, algorithm=DUAL))
     assert_mesh_equal(got_v, got_i, want_v, want_i, ("demo", n, sdf_id))
@@ -125,11 +126,11 @@ def test_a_gradient_that_vanishes_on_the_surface(PM):
     b = PM.Program((-1.0, -1.0, -1.0, 1.0, 1.0, 1.0)).sphere(0.8).plane(1.0, 0.0, 0.0, 0.0).shell(0.0).subtract()
     n = 8
     _, d = M.lattice(b.ops, n, b.bb)
-    hp = D.hermite_positions(d, b.bb)
+    hp = MR.edge_positions(d, b.bb)
     h = np.zeros((len(hp), 6), F)
     h[:, :3] = hp
     h[:, 3:6] = M.normals(b.ops, hp)
-    s = D.solve(d, b.bb, h)
+    s = MR.solve(d, b.bb, h)
     unsolved = s["used"] == 0
     assert np.isnan(h[:, 3:6]).any() and unsolved.sum() == 32 and (s["used"] < s["edges"]).sum() == 88 and len(s["pos"]) == 240
     assert np.isfinite(s["pos"]).all() and (M.bits(s["pos"][unsolved]) == M.bits(s["mass"][unsolved])).all()
@@ -151,7 +152,7 @@ def test_a_box_that_cuts_the_surface_leaves_it_open_there(pkg, oracle):
     the INTERIOR crossing edges (fewer than the Hermite records), and every index is a vertex."""
     prm = pkg.default_params()
     box = ((-1, -1, -1), (0.5, 1, 1))
-    want_v, want_i, s = D.extract_demo(oracle, oracle.params_from(prm), 16, box)
+    want_v, want_i, s = DM.extract_demo(oracle, oracle.params_from(prm), 16, box, algorithm=DUAL)
     assert (want_v.shape[0], s["quads"], len(s["hermite"])) == (1436, 1400, 1480)
     got_v, got_i = arrays(*pkg.mesh_extract(prm, 16, *box, algorithm=DUAL))
     assert got_i.shape[0] == 3 * 2 * s["quads"] and got_i.min() >= 0 and got_i.max() < got_v.shape[0]

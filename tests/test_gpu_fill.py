@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from program_fill_check import interleave
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 PARAM_KEYS = ["cube_half_side", "cube_material", "sphere_radius", "sphere_material",
@@ -281,11 +283,11 @@ def test_randomised_parameters_and_grids(pkg, oracle):
                 torch.cuda.synchronize()
                 assert torch.equal(c0, a0) and torch.equal(c1, a1), (trial, kw, dims, steps, step, "virgin state")
                 if trial % 4:
-                    assert torch.equal(cv, interleave_rows(a0[..., 0]) if ilv else a0[..., 0]), (trial, dims, steps, step, "virgin volume")
+                    assert torch.equal(cv, interleave(a0[..., 0]).reshape(a0[..., 0].shape) if ilv else a0[..., 0]), (trial, dims, steps, step, "virgin volume")
         torch.cuda.synchronize()
         assert torch.equal(p0, t0) and torch.equal(p1, t1), (trial, kw, dims, steps, "virgin load")
         if trial % 4:
-            assert torch.equal(dvol, interleave_rows(t0[..., 0]) if ilv else t0[..., 0]), (trial, dims, steps, "virgin load's volume")
+            assert torch.equal(dvol, interleave(t0[..., 0]).reshape(t0[..., 0].shape) if ilv else t0[..., 0]), (trial, dims, steps, "virgin load's volume")
         # round 5: a load the caller says NOTHING about, over a volume in either layout, on a width the whole-rows kernel of
         # step >= 2 takes (W % 4 == 0: four random dimensions are widened to it) -- every intermediate state against the
         # plain path's (the per-voxel kernels over tex0.r)
@@ -303,7 +305,7 @@ def test_randomised_parameters_and_grids(pkg, oracle):
             pkg.fill_grid_pass(prm, g5, step, w0, w1, sdf_id=sdf_id)
             torch.cuda.synchronize()
             assert torch.equal(u0.view(torch.int32), w0.view(torch.int32)) and torch.equal(u1.view(torch.int32), w1.view(torch.int32)), (trial, kw, dims5, steps5, step, "unflagged")
-            assert torch.equal(v5, interleave_rows(w0[..., 0]) if ilv5 else w0[..., 0]), (trial, dims5, steps5, step, "unflagged volume")
+            assert torch.equal(v5, interleave(w0[..., 0]).reshape(w0[..., 0].shape) if ilv5 else w0[..., 0]), (trial, dims5, steps5, step, "unflagged volume")
         del u0, u1, w0, w1, v5
         if trial % 2 == 0:
             flag = oracle.EXT_VARIANTS["srgb_quant_round"]
@@ -657,12 +659,6 @@ def test_passes_over_slabs_beyond_32_bit_indices_run_in_pieces(pkg, oracle):
         pkg.set_option(K.OPT_PASS_INDEX_LIMIT, 1)
 
 
-def interleave_rows(d):
-    """[D, H, W] -> the y-interleaved volume's layout as a [D, H, W]-shaped tensor (rows 2p, 2p + 1 as one row of pairs)."""
-    D, H, W = d.shape
-    return torch.stack([d[:, 0::2], d[:, 1::2]], dim=-1).reshape(D, H, W).contiguous()
-
-
 @pytest.mark.parametrize("dims,z_range", [((64, 64, 64), (0, 64)), ((128, 6, 5), (0, 5)), ((256, 4, 7), (2, 7)), ((300, 10, 3), (0, 3)),
                                           ((40, 12, 29), (7, 22)), ((20, 18, 12), (0, 12)), ((512, 2, 2), (0, 2)),
                                           ((768, 4, 3), (1, 3)), ((512, 6, 4), (0, 4))])
@@ -681,7 +677,7 @@ def test_fill_and_passes_maintain_the_interleaved_volume(pkg, oracle, dims, z_ra
         torch.cuda.synchronize()
         if ref0 is not None:
             assert torch.equal(t0, ref0) and torch.equal(t1, ref1)
-        assert torch.equal(vol, interleave_rows(t0[..., 0]))
+        assert torch.equal(vol, interleave(t0[..., 0]).reshape(t0[..., 0].shape))
 
     t0, t1 = pkg.alloc_textures(g)
     t0.fill_(-7.0)
@@ -757,7 +753,7 @@ def test_unflagged_strided_passes_decide_per_wave(pkg, oracle, dims, z_range, il
     lo, hi = (-1.0, -0.75, -1.0), (1.0, 1.0, 0.5)
     g = pkg.make_grid(dims, lo, hi, *z_range)
     prm, other = pkg.default_params(), pkg.default_params(sphere_radius=0.8, cube_material=1)
-    layout = interleave_rows if ilv else (lambda d: d)
+    layout = (lambda d: interleave(d).reshape(d.shape)) if ilv else (lambda d: d)
 
     def fresh():
         t0, t1 = pkg.alloc_textures(g)
@@ -788,7 +784,7 @@ def test_unflagged_strided_passes_decide_per_wave(pkg, oracle, dims, z_range, il
     for t in (a, b):
         v = torch.empty(tuple(t[0][:half].shape[:-1]), dtype=torch.float32, device="cuda")
         pkg.fill_grid(other, gh, t[0][:half], t[1][:half], dist=v)
-        t[2][:half] = layout(v) if (not ilv) else interleave_rows(v)
+        t[2][:half] = layout(v) if (not ilv) else interleave(v).reshape(v.shape)
     for step in (4, 2):
         pkg.fill_grid_pass(prm, g, step, a[0], a[1], dist=a[2], flags=flags)
         with pkg.options({K.OPT_PASS_FORM: 1}):

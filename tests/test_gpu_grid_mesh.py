@@ -13,6 +13,7 @@ import torch
 
 import demo_geometry as DG
 import grid_mesh_ref as G
+from program_fill_check import interleave
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -56,7 +57,7 @@ class Loaded:
         torch.cuda.synchronize()
         self.h0, self.h1 = self.t0.cpu().numpy(), self.t1.cpu().numpy()
         assert (G.bits(self.dist.cpu().numpy()) == G.bits(self.h0[..., 0])).all()        # the volume mirrors tex0.r
-        self.ilv = torch.from_numpy(G.interleave(self.h0[..., 0])).cuda() if dims[1] % 2 == 0 else None
+        self.ilv = torch.from_numpy(interleave(self.h0[..., 0])).cuda() if dims[1] % 2 == 0 else None
 
 
 @functools.lru_cache(maxsize=None)

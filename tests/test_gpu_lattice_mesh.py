@@ -1,5 +1,5 @@
 """Meshing a sampled lattice on the device (include/sdfgrid.h, "Meshing a sampled lattice") against the numpy restatement of
-tests/lattice_mesh_ref.py, bit for bit in positions, normals and indices, under marching cubes and dual contouring: lattices from
+tests/lattice_mesh_ref.py (over tests/mesh_ref.py), bit for bit in positions, normals and indices, under marching cubes and dual contouring: lattices from
 programs, a gyroid that cuts the box, seeded noise that reaches all 256 cube cases, a box that is no cube, an empty mesh, zero
 gradients; the three helper entry points; the one scratch pool; the C++ host route and the command line."""
 import ctypes as C
@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import lattice_mesh_ref as L
+import mesh_ref as MR
 import program_mesh_ref as M
 import program_ref as R
 
@@ -177,7 +178,7 @@ def test_the_scratch_is_shared_with_program_extractions(pkg, PM):
 
 def test_lattice_points_over_a_range_that_spans_a_row_end_and_a_plane_end(pkg):
     n, bb = 12, SLAB_BOX                                               # rows of 13, planes of 169
-    want = L.lattice_points(n, bb)
+    want = MR.lattice_points(n, bb)
     for first, count in ((100, 300), (0, 13 ** 3), (13 ** 3 - 1, 1), (169, 0)):
         got = pkg.lattice_points(bb, n, first, count).cpu().numpy()
         assert got.shape == (count, 3) and (L.bits(got) == L.bits(want[first:first + count])).all(), (first, count)
@@ -209,7 +210,7 @@ def test_lattice_normals_inside_cells_and_outside_the_box(pkg, kind, n):
     v = np.full((m, 12), 9.0, F)
     v[:, :3] = p.astype(F)
     want = v.copy()
-    want[:, 3:6] = L.normals(d, bb, v[:, :3])
+    want[:, 3:6] = MR.lattice_normals(d, bb, v[:, :3])
     assert np.isfinite(want).all()
     dev = to_dev(d)
     for offset in (0, 1):
@@ -274,7 +275,7 @@ def test_cli_meshes_a_provider_library(pkg, gyroid_provider, tmp_path):
     verts, faces = parse_ply(open(out).read())
     n, bb = 12, (-1.0, -0.5, -0.75, 1.0, 0.5, 0.75)
     raw = C.CDLL(gyroid_provider)
-    pts = L.lattice_points(n, bb)
+    pts = MR.lattice_points(n, bb)
     d = np.zeros(len(pts), F)
     rec = np.zeros(7, F)
     for k, p in enumerate(pts):

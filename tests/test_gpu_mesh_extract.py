@@ -1,74 +1,18 @@
 """The device mesher (sdfv_mesh_extract): the extraction algorithm is the build's own (the reference delegates to the
-un-vendored `isosurface` crate), so the checks are (1) an independent numpy restatement of the same conventions
-(tools/gen_mc_table.py documents them) fed with the ORACLE's lattice distances -- vertices and indices must match
-exactly -- and (2) properties any correct extractor has: closed 2-manifold, outward orientation, Euler
+un-vendored `isosurface` crate), so the checks are (1) the numpy restatement of the same conventions (tests/mesh_ref.py
+through tests/demo_mesh_ref.py; tools/gen_mc_table.py documents them) fed with the ORACLE's lattice distances and normals --
+vertices and indices must match exactly -- and (2) properties any correct extractor has: closed 2-manifold, outward orientation, Euler
 characteristic, vertices on the surface."""
-import importlib.util
 import os
-from collections import Counter
 
 import numpy as np
 import pytest
 import torch
 
+import demo_mesh_ref as DM
+import mesh_ref as MR
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = np.float32
-
-
-@pytest.fixture(scope="module")
-def table():
-    spec = importlib.util.spec_from_file_location("gen_mc_table", os.path.join(ROOT, "tools", "gen_mc_table.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod.build()
-
-
-def lattice_distances(oracle, prm, n, box, sdf_id):
-    ax = (np.arange(n + 1, dtype=np.float32) / F(n)).astype(np.float32)
-    pts = np.stack(np.meshgrid(ax, ax, ax, indexing="ij"), axis=-1)  # [i, j, k, 3]
-    d = oracle.source_scalar_many(prm, pts.reshape(-1, 3), box[0], box[1], sdf_id).reshape(n + 1, n + 1, n + 1)
-    return ax, d  # d[i, j, k]
-
-
-def numpy_extract(table, oracle, prm, n, box, sdf_id):
-    """Restatement of the extractor: lattice order (k, j, i) then axis order for vertices, cell order for triangles."""
-    ax, d = lattice_distances(oracle, prm, n, box, sdf_id)
-    inside = d < 0
-    lo, size = np.float32(box[0]), np.float32(box[1]) - np.float32(box[0])
-    vid, verts = {}, []
-    for k in range(n + 1):
-        for j in range(n + 1):
-            for i in range(n + 1):
-                idx = (i, j, k)
-                for a in range(3):
-                    nb = list(idx)
-                    nb[a] += 1
-                    if nb[a] > n or inside[tuple(nb)] == inside[idx]:
-                        continue
-                    d0, d1 = d[idx], d[tuple(nb)]
-                    t = d0 / (d0 - d1)
-                    u = [ax[idx[0]], ax[idx[1]], ax[idx[2]]]
-                    u[a] = u[a] + t * (ax[idx[a] + 1] - u[a])
-                    vid[(idx, a)] = len(verts)
-                    verts.append([u[b] * size[b] + lo[b] for b in range(3)])
-    tris = []
-    for k in range(n):
-        for j in range(n):
-            for i in range(n):
-                case = 0
-                for c in range(8):
-                    if inside[i + (c & 1), j + ((c >> 1) & 1), k + ((c >> 2) & 1)]:
-                        case |= 1 << c
-                for tri in table[case]:
-                    for e in tri:
-                        a, s = divmod(e, 4)
-                        others = [b for b in range(3) if b != a]
-                        owner = [i, j, k]
-                        owner[others[0]] += s & 1
-                        owner[others[1]] += s >> 1
-                        tris.append(vid[(tuple(owner), a)])
-    return np.array(verts, np.float32).reshape(-1, 3), np.array(tris, np.int64), d
 
 
 @pytest.mark.parametrize("sdf_id,kw,box,n", [
@@ -77,30 +21,18 @@ def numpy_extract(table, oracle, prm, n, box, sdf_id):
     (1, dict(cube_half_side=0.6), ((-1.0, -0.75, -1.25), (1.0, 1.0, 0.5)), 9),
     (0, dict(cube_half_side=0.7, sphere_radius=0.8), ((-1, -1, -1), (1, 1, 1)), 11),
 ])
-def test_extraction_matches_numpy_restatement(pkg, oracle, table, sdf_id, kw, box, n):
+def test_extraction_matches_numpy_restatement(pkg, oracle, sdf_id, kw, box, n):
     prm = pkg.default_params(**kw)
     oprm = oracle.params_from(prm)
     v, idx = pkg.mesh_extract(prm, n, *box, sdf_id=sdf_id)
-    want_v, want_i, _ = numpy_extract(table, oracle, oprm, n, box, sdf_id)
+    want_v, want_i, _ = DM.extract_demo(oracle, oprm, n, box, sdf_id)
     assert v.shape[0] == want_v.shape[0] and idx.shape[0] == want_i.shape[0]
     got = v.cpu().numpy()
-    np.testing.assert_array_equal(got[:, :3].view(np.uint32), want_v.view(np.uint32))
+    np.testing.assert_array_equal(MR.bits(got[:, :3]), MR.bits(want_v[:, :3]))
     np.testing.assert_array_equal(idx.cpu().numpy().astype(np.int64), want_i)
-    # normals = HermiteSource at the vertex, material fields = Vertex::default()
-    want_n = oracle.normal_many(oprm, want_v, 0.0, sdf_id)
-    np.testing.assert_array_equal(got[:, 3:6].view(np.uint32), want_n.view(np.uint32))
+    # normals = HermiteSource at the vertex (the oracle's normal_many), material fields = Vertex::default()
+    np.testing.assert_array_equal(MR.bits(got[:, 3:6]), MR.bits(want_v[:, 3:6]))
     assert (got[:, 6:] == 0).all()
-
-
-def manifold_report(indices):
-    tri = indices.reshape(-1, 3)
-    directed = Counter()
-    for a, b, c in tri:
-        for e in ((a, b), (b, c), (c, a)):
-            directed[e] += 1
-    assert all(cnt == 1 for cnt in directed.values()), "an oriented edge is used twice"
-    assert all((b, a) in directed for (a, b) in directed), "an edge has no opposite partner: the mesh is open"
-    return len(directed) // 2
 
 
 @pytest.mark.parametrize("n", [16, 33, 64])
@@ -108,7 +40,7 @@ def test_sphere_is_a_closed_oriented_genus_0_surface(pkg, oracle, n):
     prm = pkg.default_params(sphere_radius=0.8)
     v, idx = pkg.mesh_extract(prm, n, sdf_id=2)
     v, idx = v.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
-    n_edges = manifold_report(idx)
+    n_edges = MR.manifold_edges(idx)
     assert v.shape[0] - n_edges + idx.shape[0] // 3 == 2  # Euler characteristic of a sphere
     assert idx.min() == 0 and idx.max() == v.shape[0] - 1 and len(np.unique(idx)) == v.shape[0]
     r = np.linalg.norm(v[:, :3].astype(np.float64), axis=1)
@@ -123,7 +55,7 @@ def test_sphere_is_a_closed_oriented_genus_0_surface(pkg, oracle, n):
 def test_demo_sdf_mesh_is_closed_and_postproc_fills_materials(pkg, oracle):
     prm = pkg.default_params()
     v, idx = pkg.mesh_extract(prm, 48)
-    manifold_report(idx.cpu().numpy().astype(np.int64))
+    MR.manifold_edges(idx.cpu().numpy().astype(np.int64))
     before = v.clone()
     pkg.mesh_postproc(prm, v)
     want = oracle.mesh_postproc(oracle.params_from(prm), before.cpu().numpy())
@@ -186,7 +118,7 @@ def test_marching_cubes_is_the_same_before_and_after_dual_contouring(pkg):
         assert a.shape == b.shape and (a.view(np.uint32) == b.view(np.uint32)).all()
 
 
-def test_randomised_extractions_match_numpy_restatement(pkg, oracle, table):
+def test_randomised_extractions_match_numpy_restatement(pkg, oracle):
     """Seeded sweep (tools/soak.sh varies the seed): random demo parameters, sub-trees, boxes and lattice sizes."""
     rng = np.random.default_rng(int(os.environ.get("SDFV_SOAK_SEED", 11)))
     for _ in range(int(os.environ.get("SDFV_SOAK_TRIALS", 4))):
@@ -198,8 +130,8 @@ def test_randomised_extractions_match_numpy_restatement(pkg, oracle, table):
         n, sdf_id = int(rng.integers(3, 14)), int(rng.integers(0, 3))
         prm = pkg.default_params(**kw)
         v, idx = pkg.mesh_extract(prm, n, *box, sdf_id=sdf_id)
-        want_v, want_i, _ = numpy_extract(table, oracle, oracle.params_from(prm), n, box, sdf_id)
+        want_v, want_i, _ = DM.extract_demo(oracle, oracle.params_from(prm), n, box, sdf_id)
         assert v.shape[0] == want_v.shape[0], (kw, box, n, sdf_id)
         if v.shape[0]:
-            np.testing.assert_array_equal(v.cpu().numpy()[:, :3].view(np.uint32), want_v.view(np.uint32))
+            np.testing.assert_array_equal(MR.bits(v.cpu().numpy()[:, :3]), MR.bits(want_v[:, :3]))
             np.testing.assert_array_equal(idx.cpu().numpy().astype(np.int64), want_i)

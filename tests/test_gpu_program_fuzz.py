@@ -11,13 +11,12 @@ import numpy as np
 import pytest
 import torch
 
-import dual_contour_ref as D
 import program_fuzz as Z
 import program_march_ref as M
 import program_mesh_ref as MR
 import program_pass_ref as P
 import program_ref as R
-from program_fill_check import fill_equals_packing, same_bits
+from program_fill_check import fill_equals_packing, interleave, same_bits
 from test_gpu_dual_contour import assert_mesh_equal as assert_dual_mesh_equal
 from test_gpu_program_march import RGBA_TOL
 from test_gpu_program_mesh import assert_mesh_equal
@@ -162,14 +161,14 @@ def test_a_pass_of_one_program_over_a_grid_loaded_with_another(pkg, PM, corpus):
                         want = P.expected(before, dense[1], mask, air, volume)
                         t0, t1 = torch.from_numpy(before[0].copy()).cuda(), torch.from_numpy(before[1].copy()).cuda()
                         plain = before[0][..., 0].copy()
-                        vol = None if volume is None else torch.from_numpy(P.interleave(plain) if volume == "ilv" else plain.reshape(-1)).cuda()
+                        vol = None if volume is None else torch.from_numpy(interleave(plain) if volume == "ilv" else plain.reshape(-1)).cuda()
                         B.grid_pass(grid, step, t0, t1, dist=vol, changed_box=box, flags=K.PASS_VOLUME_INTERLEAVED if volume == "ilv" else 0)
                         torch.cuda.synchronize()
                         what = f"step {step} box {box} volume {volume}"
                         same_bits(t0.cpu().numpy(), want[0], what + " tex0")
                         same_bits(t1.cpu().numpy(), want[1], what + " tex1")
                         if volume:
-                            same_bits(vol.cpu().numpy(), P.interleave(want[2]) if volume == "ilv" else want[2].reshape(-1), what + " volume")
+                            same_bits(vol.cpu().numpy(), interleave(want[2]) if volume == "ilv" else want[2].reshape(-1), what + " volume")
     print(f"{len(pairs)} pairs, {skipped} skipped for a stored AIR_DIST, {differing} whose fills differ inside the box and outside it")
     assert 4 * skipped <= len(pairs) and 4 * differing >= 3 * (len(pairs) - skipped)
 
@@ -203,7 +202,7 @@ def test_the_direct_march_equals_its_restatement_on_the_corpus(pkg, PM, corpus, 
 
 def restated_meshes(ops, bb, materials, sizes=(7, 9)):
     """{(n, algorithm): (vertices, indices)} from the two restatements, or None where they do not apply: a lattice with an exact
-    zero or a NaN (tests/program_mesh_ref.py extract refuses those), a marching-cubes normal that is not finite
+    zero or a NaN (tests/mesh_ref.py extract refuses those), a marching-cubes normal that is not finite
     (tests/test_gpu_program_mesh.py compares them bit for bit) or a dual-contouring position that is not
     (tests/test_gpu_dual_contour.py asserts it)."""
     out = {}
@@ -212,15 +211,15 @@ def restated_meshes(ops, bb, materials, sizes=(7, 9)):
         if np.isnan(d).any() or (d == 0).any():
             return None
         out[n, 0] = MR.extract(ops, n, bb, materials)[:2]
-        out[n, D.DUAL] = D.extract_program(ops, n, bb, materials)[:2]
-        if not np.isfinite(out[n, 0][0][:, 3:6]).all() or not np.isfinite(out[n, D.DUAL][0][:, :3]).all():
+        out[n, MR.DUAL] = MR.extract(ops, n, bb, materials, MR.DUAL)[:2]
+        if not np.isfinite(out[n, 0][0][:, 3:6]).all() or not np.isfinite(out[n, MR.DUAL][0][:, :3]).all():
             return None
     return out
 
 
 @pytest.mark.timeout(600)
 def test_marching_cubes_and_dual_contouring_equal_their_restatements_on_the_corpus(pkg, PM, corpus):
-    """mesh(n, algorithm=0) against tests/program_mesh_ref.py and mesh(n, algorithm=4) against tests/dual_contour_ref.py at 7 and 9
+    """mesh(n, algorithm=0) and mesh(n, algorithm=4) against tests/program_mesh_ref.py (over tests/mesh_ref.py) at 7 and 9
     cells over the program's box, the materials fused on every other program: the first 16 programs of the corpus, in the
     order of program_fuzz.share, that the restatements apply to."""
     meshed = nonempty = 0

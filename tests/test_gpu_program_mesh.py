@@ -1,5 +1,5 @@
 """Meshing over SDF programs on the device (include/sdfgrid.h, "SDF programs: meshing") against the numpy restatement of
-tests/program_mesh_ref.py, bit for bit: extraction, the fused materials, Mesh::postproc's rule, the batched normal, the
+tests/program_mesh_ref.py (over tests/mesh_ref.py), bit for bit: extraction, the fused materials, Mesh::postproc's rule, the batched normal, the
 properties any correct extractor has, the one scratch pool, and the C++ host route.  The programs are program_ref.catalogue's."""
 import functools
 import importlib
@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import mesh_ref as MR
 import program_mesh_ref as M
 import program_ref as R
 
@@ -180,7 +181,7 @@ def test_normal_points_against_the_restatement(built, cat, eps):
 @pytest.mark.parametrize("n", [16, 33])
 def test_the_sphere_is_a_closed_oriented_genus_0_surface_on_the_device(built, n):
     v, i = host(*built("single").mesh(n))
-    M.assert_sphere_properties(v, i, n)
+    MR.assert_sphere_properties(v, i, n)
 
 
 def test_one_scratch_pool_serves_the_demo_and_programs(pkg, built):

@@ -9,6 +9,7 @@ import torch
 
 import program_pass_ref as P
 import program_ref as R
+from program_fill_check import interleave
 
 pytestmark = pytest.mark.gpu
 VOLUMES = ("plain", "ilv", None)
@@ -72,7 +73,7 @@ class Scene:
         vol = None
         if volume:
             plain = state[0][..., 0].copy()
-            vol = torch.from_numpy(P.interleave(plain) if volume == "ilv" else plain.reshape(-1)).cuda()
+            vol = torch.from_numpy(interleave(plain) if volume == "ilv" else plain.reshape(-1)).cuda()
         return t0, t1, vol
 
     def check(self, dev, want, volume, what):
@@ -80,7 +81,7 @@ class Scene:
         same_bits(dev[0].cpu().numpy(), want[0], what + " tex0")
         same_bits(dev[1].cpu().numpy(), want[1], what + " tex1")
         if volume:
-            same_bits(dev[2].cpu().numpy(), P.interleave(want[2]) if volume == "ilv" else want[2].reshape(-1), what + " volume")
+            same_bits(dev[2].cpu().numpy(), interleave(want[2]) if volume == "ilv" else want[2].reshape(-1), what + " volume")
 
     def air_state(self):
         W, H, D = P.DIMS
@@ -168,7 +169,7 @@ def test_flags_are_knowledge_and_the_hint_is_a_hint(scene, volume):
             same_bits(got[1], state[1], f"{label} step {step} tex1")
             if volume:
                 plain = state[0][..., 0]
-                same_bits(got[2], P.interleave(plain) if volume == "ilv" else plain.reshape(-1), f"{label} step {step} volume")
+                same_bits(got[2], interleave(plain) if volume == "ilv" else plain.reshape(-1), f"{label} step {step} volume")
     same_bits(state[0], scene.dense["B", 0][0], "the load ends in the dense fill: tex0")
     same_bits(state[1], scene.dense["B", 0][1], "the load ends in the dense fill: tex1")
 

@@ -13,6 +13,7 @@ import torch
 import grid_mesh_ref as G
 import stream_gate as SG
 import test_gpu_containment_grid_mesh as CG
+from program_fill_check import interleave
 from stream_gate import capture, gate  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -56,7 +57,7 @@ def test_grid_mesh_extract_synchronises_its_stream(pkg, gate, source, algorithm)
     if source == "volume":
         inputs["dist"] = (vol, 4)
     elif source == "interleaved":
-        inputs["dist"] = (G.interleave(vol), 8)
+        inputs["dist"] = (interleave(vol), 8)
     meshes = []
 
     def call(t, h):

@@ -19,7 +19,6 @@ stream is idle when the call returns, and the host was held for as long as the s
 import ctypes as C
 import functools
 import importlib
-import importlib.util
 
 import numpy as np
 import pytest
@@ -241,24 +240,13 @@ def wanted_mesh(entry, algorithm):
     if entry == "lattice":
         v, i, _ = LM.extract(np.ascontiguousarray(LM.gyroid_lattice(CELLS, LATTICE_BB), F), LATTICE_BB, algorithm)
     elif entry == "program":
-        import dual_contour_ref as D
         import program_mesh_ref as PMR
         import program_ref as R
         b = R.catalogue(PM)["all_ops"]
-        v, i, _ = (D.extract_program if algorithm == DUAL else PMR.extract)(b.ops, CELLS, b.bb)
+        v, i, _ = PMR.extract(b.ops, CELLS, b.bb, algorithm=algorithm)
     else:
-        oprm = oracle.params_from(pkg.default_params())
-        if algorithm == DUAL:
-            import dual_contour_ref as D
-            v, i, _ = D.extract_demo(oracle, oprm, CELLS, UNIT_BOX, 0)
-        else:
-            import test_gpu_mesh_extract as ME
-            spec = importlib.util.spec_from_file_location("gen_mc_table", ME.os.path.join(ME.ROOT, "tools", "gen_mc_table.py"))
-            mod = importlib.util.module_from_spec(spec)
-            spec.loader.exec_module(mod)
-            pos, i, _ = ME.numpy_extract(mod.build(), oracle, oprm, CELLS, UNIT_BOX, 0)
-            v = np.zeros((len(pos), 12), F)
-            v[:, :3], v[:, 3:6] = pos, oracle.normal_many(oprm, pos, 0.0, 0)
+        import demo_mesh_ref as DM
+        v, i, _ = DM.extract_demo(oracle, oracle.params_from(pkg.default_params()), CELLS, UNIT_BOX, 0, algorithm)
     assert len(i) > 0
     return np.ascontiguousarray(v, F), np.asarray(i, np.int64)
 

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from program_fill_check import interleave
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
@@ -29,13 +31,6 @@ def coords(dims, bb_min, bb_max):
         size = np.float32(bb_max[a]) - np.float32(bb_min[a])
         out.append(((i / dm1) * size) + np.float32(bb_min[a]))
     return out
-
-
-def interleave(vol):
-    """texture-order volume [D, H, W] -> the y-interleaved layout (entry ((row >> 1) * W + x) * 2 + (row & 1))"""
-    D, H, W = vol.shape
-    rows = vol.reshape(D * H // 2, 2, W)
-    return np.ascontiguousarray(rows.transpose(0, 2, 1)).reshape(-1)
 
 
 def emit_reference(dims, bb_min, bb_max, step, cursor, n, box, vol, air):

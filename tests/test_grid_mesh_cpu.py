@@ -1,17 +1,17 @@
 """CPU tests of meshing a loaded grid (include/sdfgrid.h, "Meshing a loaded grid"): the numpy restatement the GPU tests compare
-against (tests/grid_mesh_ref.py) -- its per-axis extraction held to the cubic restatements that are already pinned, the table
-inversion, the round trip of the golden grid's colours through the oracle's 8-bit quantisation and the PLY byte rule --, what
+against (tests/grid_mesh_ref.py over tests/mesh_ref.py) -- the extraction on a lattice that is no cube (every route's bits are
+pinned by tests/test_mesh_ref_pins.py), the table inversion, the round trip of the golden grid's colours through the oracle's 8-bit quantisation and the PLY byte rule --, what
 the two entry points refuse without a device, and what the built kernels look like.  No device needed."""
 import ctypes as C
 import os
 import re
 
 import numpy as np
-import pytest
 
-import dual_contour_ref as D
 import grid_mesh_ref as G
 import lattice_mesh_ref as L
+import mesh_ref as MR
+from program_fill_check import interleave
 from kernel_objects import code_objects, disassembly, kernel_table  # noqa: F401 (code_objects is a fixture)
 
 INVALID, NO_DEVICE = -1, -4
@@ -23,39 +23,18 @@ SLAB_BOX = (-1.0, -0.5, -0.75, 1.0, 0.5, 0.75)
 
 
 # ---- the restatement ----
-@pytest.mark.parametrize("algorithm", [0, G.DUAL])
-@pytest.mark.parametrize("n,bb", [(9, BOX), (12, SLAB_BOX)])
-def test_the_per_axis_extraction_is_the_pinned_one_on_a_cube(n, bb, algorithm):
-    """tests/lattice_mesh_ref.py and tests/dual_contour_ref.py take n cells on every axis; grid_mesh_ref's functions are theirs
-    with cells per axis.  On a cubic lattice every piece gives the same bits."""
-    d = L.gyroid_lattice(n, bb)
-    want_v, want_i, want = L.extract(d, bb, algorithm)
-    got_v, got_i, got = G.extract_lattice(d, bb, algorithm)
-    assert want_v.shape[0] > 50 and got_v.shape == want_v.shape
-    assert (G.bits(got_v) == G.bits(want_v)).all() and (got_i == want_i).all()
-    if algorithm == G.DUAL:
-        assert (G.bits(got["hermite"]) == G.bits(want["hermite"])).all() and (got["cells"] == want["cells"]).all()
-        assert (G.bits(got["mass"]) == G.bits(want["mass"])).all() and (got["used"] == want["used"]).all()
-    else:
-        assert (got["cases"] == want["cases"]).all()
-    rng = np.random.default_rng(n)
-    p = rng.uniform(-1.5, 1.5, size=(500, 3)).astype(F)
-    assert (G.bits(G.normals(d, bb, p)) == G.bits(L.normals(d, bb, p))).all()
-    assert (G.bits(G.hermite_positions(d, bb)) == G.bits(D.hermite_positions(d, bb))).all()
-
-
 def test_a_lattice_that_is_no_cube_gives_a_closed_surface_inside_its_box():
     """A sphere on 8 x 6 x 4 cells of a box with three different sides: both algorithms give a closed, oriented surface whose
     vertices lie within a cell's diagonal of the sphere, and unit normals."""
     cells, bb = (8, 6, 4), (-1.0, -0.9, -0.8, 1.0, 0.9, 0.8)
-    _, _, _, axes = G.axes_of(cells, bb)
+    _, _, _, axes = MR.axes_of(cells, bb)
     zz, yy, xx = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
     d = (np.sqrt(xx.astype(np.float64) ** 2 + yy ** 2 + zz ** 2) - 0.6).astype(F)
-    assert d.shape == (5, 7, 9) and G.cells_of(d) == cells
+    assert d.shape == (5, 7, 9) and MR.cells_of(d) == cells
     for algorithm in (0, G.DUAL):
-        v, i, _ = G.extract_lattice(d, bb, algorithm)
+        v, i, _ = L.extract(d, bb, algorithm)
         assert v.shape[0] > 20 and i.shape[0] % 3 == 0 and i.max() == v.shape[0] - 1
-        D.assert_closed_and_oriented(i)
+        MR.assert_closed_and_oriented(i)
         r = np.linalg.norm(v[:, :3].astype(np.float64), axis=1)
         assert np.abs(r - 0.6).max() < 0.5 * np.linalg.norm([2.0 / 8, 1.8 / 6, 1.6 / 4])
         assert np.abs(np.linalg.norm(v[:, 3:6].astype(np.float64), axis=1) - 1.0).max() < 1e-6
@@ -79,7 +58,7 @@ def test_lattice_of_and_unpack_follow_the_published_voxels():
     c, _ = G.lattice_of((9, 7, 5), bb, 2)
     assert c == (4, 3, 2) and G.unpack(np.zeros((5, 7, 9), F), 2).shape == (3, 4, 5)
     vol = np.arange(4 * 6 * 5, dtype=F).reshape(4, 6, 5)
-    ilv = G.interleave(vol)
+    ilv = interleave(vol)
     for z, y, x in ((0, 0, 0), (1, 3, 2), (3, 5, 4), (2, 4, 1)):
         row = z * 6 + y
         assert ilv[((row >> 1) * 5 + x) * 2 + (row & 1)] == vol[z, y, x]

@@ -1,6 +1,6 @@
 """CPU tests of meshing a sampled lattice (include/sdfgrid.h, "Meshing a sampled lattice"): the sanity of the numpy restatement
-the GPU tests compare against (tests/lattice_mesh_ref.py) on geometry whose answer is known and against the restatements that
-are already pinned; what the four entry points refuse without a device, with code and text; and what the built kernels look
+the GPU tests compare against (tests/lattice_mesh_ref.py over tests/mesh_ref.py) on geometry whose answer is known (its bits are
+pinned by tests/test_mesh_ref_pins.py); what the four entry points refuse without a device, with code and text; and what the built kernels look
 like.  No device needed."""
 import ctypes as C
 import importlib
@@ -10,18 +10,14 @@ import re
 import numpy as np
 import pytest
 
-import dual_contour_ref as D
 import lattice_mesh_ref as L
-import program_mesh_ref as M
-import program_ref as R
+import mesh_ref as MR
 from kernel_objects import code_objects, disassembly, kernel_table  # noqa: F401 (code_objects is a fixture)
 
 INVALID, NO_DEVICE = -1, -4
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOX = (-1.0, -1.0, -1.0, 1.0, 1.0, 1.0)
 F = np.float32
-CUBE = ((R.CUBE, (0.6,)),)
-CUBE_MINUS_SPHERE = ((R.CUBE, (0.6,)), (R.SPHERE, (0.7,)), (R.SUBTRACT, ()))
 
 
 # ---- the restatement: it is the yardstick of tests/test_gpu_lattice_mesh.py ----
@@ -36,7 +32,7 @@ def test_the_restated_normal_reproduces_the_header_s_sphere_table(n, degrees):
     """A sphere of radius 0.6 in [-1, 1]^3, its exact distance at the lattice points, 4000 points on the surface: the worst angle
     between the restated normal and the true one is the figure the header quotes, within 5 % of it."""
     u = fibonacci_sphere(4000)
-    got = L.normals(L.sphere_lattice(n, BOX), BOX, (u * 0.6).astype(F)).astype(np.float64)
+    got = MR.lattice_normals(L.sphere_lattice(n, BOX), BOX, (u * 0.6).astype(F)).astype(np.float64)
     assert (np.abs(np.linalg.norm(got, axis=1) - 1.0) < 1e-6).all()
     worst = np.degrees(np.arccos(np.clip((got * u).sum(axis=1), -1.0, 1.0))).max()
     print(n, "cells: worst angle to the true normal", worst, "degrees; the header says", degrees)
@@ -48,40 +44,18 @@ def test_the_restated_normal_is_exact_on_a_linear_field_clamps_outside_and_is_ze
     the box included (the clamp takes the border cell).  A constant lattice has no gradient: the zero normal."""
     n, bb = 7, (-1.0, -0.5, 0.0, 1.0, 1.5, 3.0)
     a = np.array([0.3, -0.5, 0.8])
-    d = (L.lattice_points(n, bb).astype(np.float64) @ a + 0.05).astype(F).reshape(n + 1, n + 1, n + 1)
+    d = (MR.lattice_points(n, bb).astype(np.float64) @ a + 0.05).astype(F).reshape(n + 1, n + 1, n + 1)
     pts = np.array([(0.1, 0.2, 0.3), (-1.0, -0.5, 0.0), (1.0, 1.5, 3.0), (5.0, -7.0, 1.0), (0.999, 1.499, 2.999)], F)
-    got = L.normals(d, bb, pts)
+    got = MR.lattice_normals(d, bb, pts)
     assert np.abs(got - (a / np.linalg.norm(a))[None, :]).max() < 1e-5
     flat = np.full((n + 1, n + 1, n + 1), 0.25, F)
-    assert (L.bits(L.normals(flat, bb, pts)) == 0).all()
-
-
-@pytest.mark.parametrize("ops", [CUBE, CUBE_MINUS_SPHERE], ids=["cube", "cube-sphere"])
-def test_extraction_from_a_program_s_distances_is_the_program_s_extraction(ops):
-    """The lattice route is the program route with the distances given: positions and indices equal tests/program_mesh_ref.py's
-    and tests/dual_contour_ref.py's, bit for bit, at 12 cells.  (The normals differ: they are the lattice's own.)"""
-    n = 12
-    _, d = M.lattice(ops, n, BOX)
-    want_v, want_i, _ = M.extract(ops, n, BOX)
-    got_v, got_i, _ = L.extract(d, BOX)
-    assert want_v.shape[0] > 0 and got_v.shape == want_v.shape
-    assert (L.bits(got_v[:, :3]) == L.bits(want_v[:, :3])).all() and (got_i == want_i).all()
-    assert (got_v[:, 6:] == 0).all() and np.isfinite(got_v).all()
-    assert (np.abs(np.linalg.norm(got_v[:, 3:6].astype(np.float64), axis=1) - 1.0) < 1e-6).all()
-    dv, di, ds = D.extract_program(ops, n, BOX)
-    hermite = ds["hermite"]
-    solved = D.solve(d, BOX, hermite)                                  # the same Hermite normals: the same solve
-    assert (L.bits(solved["pos"]) == L.bits(dv[:, :3])).all() and (solved["idx"] == di).all()
-    gv, gi, gs = L.extract(d, BOX, L.DUAL)                             # the lattice's normals: the same cells and quads
-    assert (L.bits(gs["hermite"][:, :3]) == L.bits(hermite[:, :3])).all()
-    assert gv.shape == dv.shape and (gi == di).all() and (gs["cells"] == ds["cells"]).all()
-    L.assert_closed_and_oriented(gi)
+    assert (L.bits(MR.lattice_normals(flat, bb, pts)) == 0).all()
 
 
 @pytest.mark.parametrize("n", [9, 12])
 def test_the_restated_sphere_is_a_closed_oriented_genus_0_surface(n):
     v, i, _ = L.extract(L.sphere_lattice(n, BOX), BOX)
-    L.assert_sphere_properties(v, i, n)
+    MR.assert_sphere_properties(v, i, n)
 
 
 # ---- the ABI ----

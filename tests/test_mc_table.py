@@ -1,20 +1,9 @@
 """The triangle table of the device mesher (sdf-viewer_amd/csrc/mc_table.inc) is generated, not copied: the committed
 file must be what tools/gen_mc_table.py produces, and the table must triangulate ANY sign field into a closed,
 consistently oriented surface (checked on random fields, where every ambiguous face and case shows up)."""
-import importlib.util
-import os
-from collections import Counter
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def load_generator():
-    spec = importlib.util.spec_from_file_location("gen_mc_table", os.path.join(ROOT, "tools", "gen_mc_table.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+from mesh_ref import directed_edges, mc_generator as load_generator   # the one loader of tools/gen_mc_table.py
 
 
 def test_committed_table_is_the_generated_one():
@@ -41,7 +30,7 @@ def test_random_sign_fields_give_closed_oriented_surfaces():
         n = 5
         inside = np.zeros((n + 1, n + 1, n + 1), bool)
         inside[1:-1, 1:-1, 1:-1] = rng.random((n - 1, n - 1, n - 1)) < (0.5 if trial % 2 else 0.25)
-        directed = Counter()
+        vid, idx = {}, []                                 # vertex ids of the (lattice point, axis) keys, and the triangles
         for k in range(n):
             for j in range(n):
                 for i in range(n):
@@ -50,16 +39,14 @@ def test_random_sign_fields_give_closed_oriented_surfaces():
                         if inside[i + (c & 1), j + ((c >> 1) & 1), k + ((c >> 2) & 1)]:
                             case |= 1 << c
                     for tri in table[case]:
-                        keys = []
                         for e in tri:
                             a, s = divmod(e, 4)
                             others = [b for b in range(3) if b != a]
                             owner = [i, j, k]
                             owner[others[0]] += s & 1
                             owner[others[1]] += s >> 1
-                            keys.append((tuple(owner), a))
-                        for u, v in ((keys[0], keys[1]), (keys[1], keys[2]), (keys[2], keys[0])):
-                            directed[(u, v)] += 1
+                            idx.append(vid.setdefault((tuple(owner), a), len(vid)))
+        directed = directed_edges(idx)
         assert directed, "the random field has a surface"
         assert all(c == 1 for c in directed.values())
         assert all((v, u) in directed for (u, v) in directed), "open edge: the surface is not watertight"

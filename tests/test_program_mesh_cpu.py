@@ -1,6 +1,6 @@
 """CPU tests of meshing over SDF programs (include/sdfgrid.h, "SDF programs: meshing"): what the four entry points refuse, with
 their messages; what the built kernels look like; and the sanity of the numpy restatement the GPU tests compare against
-(tests/program_mesh_ref.py).  No device needed."""
+(tests/program_mesh_ref.py over tests/mesh_ref.py).  No device needed."""
 import ctypes as C
 import importlib
 import re
@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import mesh_ref as MR
 import program_mesh_ref as M
 import program_ref as R
 from kernel_objects import code_objects, disassembly, kernel_table  # noqa: F401 (code_objects is a fixture)
@@ -124,8 +125,8 @@ def test_mesh_kernels_keep_the_resource_ceilings(code_objects):
 @pytest.mark.parametrize("n", [16, 33])
 def test_the_restated_sphere_is_a_closed_oriented_genus_0_surface(PM, n):
     b = R.catalogue(PM)["single"]
-    v, idx, d = M.extract(b.ops, n, b.bb)
-    M.assert_sphere_properties(v, idx, n)
+    v, idx, _ = M.extract(b.ops, n, b.bb)
+    MR.assert_sphere_properties(v, idx, n)
     assert np.isfinite(v).all() and (v[:, 6:] == 0).all()
 
 
