@@ -35,7 +35,6 @@ sdfv::FillArgs make_fill_args(const sdfv_demo_params& p, uint32_t sdf_id, const 
     a.prm = p;
     a.sdf_id = sdf_id;
     a.D = g.dims[2];
-    a.z_step = 1;
     set_grid_fill_args(a, g, tex0, tex1);
     return a;
 }
@@ -125,19 +124,6 @@ int fill_grid_signalling_start(const sdfv_demo_params* params, uint32_t sdf_id, 
     a.signal_value = value;
     if (int rc = check_one_launch(a)) return rc;
     SDFV_HIP_RETURN(launch_fill_dense(a, fill_launch_config(dist != nullptr), (hipStream_t)stream));
-}
-
-int fill_boundary_slices(const sdfv_demo_params* params, uint32_t sdf_id, const sdfv_grid* slab, float* o0, float* o1,
-                         void* stream) {
-    if (int rc = check_params(params, sdf_id)) return rc;
-    if (int rc = check_grid(slab)) return rc;
-    if (slab->z_end - slab->z_begin < 2) return set_error(SDFV_ERR_INVALID_ARGUMENT, "a slab of one slice has one boundary");
-    if (int rc = check_texel_alignment(o0, o1)) return rc;
-    if (int rc = need_device()) return rc;
-    FillArgs a = make_fill_args(*params, sdf_id, *slab, o0, o1);
-    a.z_step = a.slab_d - 1;
-    a.slab_d = 2;
-    SDFV_HIP_RETURN(launch_fill_slices(a, (hipStream_t)stream));
 }
 }  // namespace sdfv
 

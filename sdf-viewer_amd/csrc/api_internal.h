@@ -146,8 +146,6 @@ struct DeviceFacts {
 const DeviceFacts& device_facts();
 // An SDF program's instructions on the current device (copied there on the first use), their count and, if asked for, its box.
 int program_on_device(const sdfv_program* p, const sdfv_prog_op** ops, uint32_t* n_ops, const float** bb = nullptr);
-// The first and the last slice of `slab` (the ones the z-neighbours need) in one launch; o0/o1 address the first
-// owned slice.  Same texels as sdfv_fill_grid over those two slices.  Requires at least two owned slices.
 // Dense fill of `slab` in boundary-first workgroup order (fill_kernels.h): the `lead` first slices and the last one come
 // first, optionally copied into the packed staging buffers.
 struct OrderedFill {
@@ -171,8 +169,6 @@ int fill_grid_signalling_start(const sdfv_demo_params* params, uint32_t sdf_id, 
                                float* tex1, float* dist, uint32_t* signal, uint32_t value, void* stream);
 // dist[i] = tex0[i].r over n texels (the ghost slices' share of the compact distance volume)
 int extract_distance(const float* tex0, float* dist, size_t n, void* stream);
-int fill_boundary_slices(const sdfv_demo_params* params, uint32_t sdf_id, const sdfv_grid* slab, float* o0, float* o1,
-                         void* stream);
 }  // namespace sdfv
 
 // sdfv_raymarch_slab_round with a counter of the rays the round hands on (`leftover`, DEVICE or NULL): sdfv_slab_march passes

@@ -20,8 +20,7 @@ struct FillArgs {
     float air_dist;
     uint32_t x_chunks;       // set by the launcher: ceil(W / TX)
     unsigned long long w_magic;  // set by the launcher (flat form): floor(2^64 / W) + 1
-    uint32_t z_step;         // strided flat form only: local slice k is global slice z_begin + k * z_step and
-                             // lives k * z_step slices into the textures (1 everywhere else)
+    uint32_t reserved;       // unused (0): keeps the fields behind it where the kernels' scalar loads were laid out for
     float4* tex0;
     float4* tex1;
     float* dist;             // optional compact copy of tex0.r written in the same pass (fused SDFViewer::commit)
@@ -121,8 +120,6 @@ struct CopySegments {
     float* r_out[4];  // optional: the texels' first component as a compact array (the distance volume's ghost slices)
 };
 hipError_t launch_copy_segments(const CopySegments& c, hipStream_t stream);
-// slab_d slices z_begin + k * z_step in ONE launch (the two boundary slices of a slab: slab_d = 2).
-hipError_t launch_fill_slices(const FillArgs& a, hipStream_t stream);
 // dense_cfg: store policy / index form of the dense kernel, which an all-required step-1 pass is
 hipError_t launch_fill_pass(const FillArgs& a, const PassArgs& p, const FillLaunch& dense_cfg, hipStream_t stream);
 hipError_t launch_commit_distance(const float* tex0, float* dist, uint64_t n_voxels, hipStream_t stream);

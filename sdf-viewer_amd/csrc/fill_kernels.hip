@@ -98,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void fill_dense_ilv_paired_kernel(FillArgs 
 // is 1 KiB whatever W is.  x and row come from an exact division by W done as a 64-bit multiply-high with
 // M = floor(2^64 / W) + 1 (exact for dividends below 2^32); the (y, z) coordinates of the few rows a workgroup
 // touches are staged in LDS by its first lanes.
-template <bool NT, typename Cfg, bool STRIDED = false, bool ORDERED = false>
+template <bool NT, typename Cfg, bool ORDERED = false>
 __global__ __launch_bounds__(kBlock) void fill_dense_flat_kernel(FillArgs a) {
     __shared__ float s_lut[256];
     __shared__ float2 s_yz[kBlock + 1];
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void fill_dense_flat_kernel(FillArgs a) {
     const uint32_t v_last = min(v0 + kBlock - 1, n_vox - 1);
     const uint32_t n_rows_here = div_w(v_last) - row_first + 1;  // <= kBlock + 1
     const LdsLut lut = stage_srgb_lut(s_lut);
-    for (uint32_t r = tid; r < n_rows_here; r += kBlock) s_yz[r] = stage_row_yz(a, row_first + r, STRIDED ? a.z_step : 1u);
+    for (uint32_t r = tid; r < n_rows_here; r += kBlock) s_yz[r] = stage_row_yz(a, row_first + r);
     __syncthreads();
     const uint32_t v = v0 + tid;
     if (!ORDERED && v >= n_vox) return;  // ordered launches cover whole workgroups only
@@ -127,8 +127,7 @@ __global__ __launch_bounds__(kBlock) void fill_dense_flat_kernel(FillArgs a) {
     const float2 yz = s_yz[row - row_first];
     float4 v0t, v1t;
     fill_voxel<Cfg>(a.prm, a.sdf_id, px, yz.x, yz.y, lut, a.air_dist, v0t, v1t);
-    size_t at = v;
-    if (STRIDED) at += (size_t)(row / a.H) * (a.z_step - 1) * a.H * a.W;  // the slices skipped in between
+    const size_t at = v;
     if (!ORDERED || !a.stage_only) {
         store_texel<NT>(a.tex0 + at, v0t);
         store_texel<NT>(a.tex1 + at, v1t);
@@ -597,7 +596,7 @@ hipError_t launch_fill_dense_ordered(const FillArgs& args, uint32_t block_begin,
     else if (p.tx == 256) launch_ordered_rows<256>(a, blocks, stream);
     else {
         a.w_magic = a.W > 1 ? (~0ull / a.W) + 1ull : 0ull;
-        SDFV_LAUNCH_CFG(a, (fill_dense_flat_kernel<false, Cfg, false, true>), dim3(blocks), dim3(kBlock), 0, stream, a);
+        SDFV_LAUNCH_CFG(a, (fill_dense_flat_kernel<false, Cfg, true>), dim3(blocks), dim3(kBlock), 0, stream, a);
     }
     return hipGetLastError();
 }
@@ -612,17 +611,6 @@ hipError_t launch_copy_segments(const CopySegments& c, hipStream_t stream) {
     if (segs == 0) return hipSuccess;
     const uint32_t bx = blocks_for(n_max);
     hipLaunchKernelGGL(copy_segments_kernel, dim3(bx < 4096 ? bx : 4096, segs), dim3(kBlock), 0, stream, c);
-    return hipGetLastError();
-}
-
-hipError_t launch_fill_slices(const FillArgs& args, hipStream_t stream) {
-    FillArgs a = args;
-    const uint64_t n_vox = (uint64_t)a.W * a.H * a.slab_d;
-    if (n_vox == 0) return hipSuccess;
-    const uint32_t blocks = blocks_for(n_vox, 0xffffffffull);
-    if (a.z_step == 0 || !blocks) return hipErrorInvalidValue;
-    a.w_magic = a.W > 1 ? (~0ull / a.W) + 1ull : 0ull;
-    SDFV_LAUNCH_CFG(a, (fill_dense_flat_kernel<false, Cfg, true>), dim3(blocks), dim3(kBlock), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -96,13 +96,13 @@ __device__ __forceinline__ void pass_store_texels(const Args& a, float* vol, uin
     store_texel<true>(a.tex1 + flat, v1);
 }
 
-// The (y, z) coordinates of slab row `row` (= z_local * H + y; local slice k is global slice z_begin + k * z_step): an IEEE
+// The (y, z) coordinates of slab row `row` (= z_local * H + y): an IEEE
 // divide per axis, so once per row (through LDS) instead of once per voxel.
 template <typename Args>
-__device__ __forceinline__ float2 stage_row_yz(const Args& a, uint32_t row, uint32_t z_step = 1) {
+__device__ __forceinline__ float2 stage_row_yz(const Args& a, uint32_t row) {
     const uint32_t zl = row / a.H, y = row - zl * a.H;
     return make_float2(voxel_coord(y, a.dm1[1], a.bb_size[1], a.bb_min[1]),
-                       voxel_coord(a.z_begin + zl * z_step, a.dm1[2], a.bb_size[2], a.bb_min[2]));
+                       voxel_coord(a.z_begin + zl, a.dm1[2], a.bb_size[2], a.bb_min[2]));
 }
 
 // "This launch has started" = everything enqueued before it on its stream has finished: the multi-GPU fill step lets the

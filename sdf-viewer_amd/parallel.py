@@ -81,6 +81,11 @@ class SlabTextures:
         return self.tex1[self.ghost_lo:self.ghost_lo + (self.z_end - self.z_begin)]
 
 
+def _ghost_counts(rank, world, periodic=False, halo_hi=1):
+    """-> (ghost slices below, above) of rank's slab: one below if a lower neighbour exists, halo_hi above if an upper one does."""
+    return (1 if periodic or rank > 0 else 0), (halo_hi if periodic or rank < world - 1 else 0)
+
+
 def alloc_slab(dims, rank, world, device, fill_value=None, periodic=False, pkg=None, halo_hi=1):
     """pkg given (and a GPU device): the two textures share one block, tex1 at the distance from tex0's end that MI355X fills
     fastest for textures of this size (pkg.alloc_textures_placed = what SDFViewer::new_voxels allocates; no probe).
@@ -88,8 +93,9 @@ def alloc_slab(dims, rank, world, device, fill_value=None, periodic=False, pkg=N
     communicator fills them when created with SDFV_COMM_HALO2 (SlabComm(halo_hi=2)), halo_exchange() below handles either
     depth over torch.distributed."""
     z0, z1 = slab_range(dims[2], rank, world)
-    glo = 1 if (periodic or rank > 0) else 0
-    ghi = halo_hi if periodic else min(halo_hi, dims[2] - z1)
+    glo, ghi = _ghost_counts(rank, world, periodic, halo_hi)
+    if not periodic:
+        ghi = min(ghi, dims[2] - z1)  # only the slices that exist
     shape = (glo + (z1 - z0) + ghi, dims[1], dims[0], 4)
     if pkg is not None and torch.device(device).type == "cuda":
         with torch.cuda.device(torch.device(device)):
@@ -109,50 +115,60 @@ def _needs_host_staging(t, group=None):
     return t.is_cuda and c10d.get_backend(group) == "gloo"
 
 
+class _P2PBatch:
+    """One batch_isend_irecv: send(block, peer) / recv(block, peer) in posting order, then run().  Blocks on a GPU are staged
+    through host memory where _needs_host_staging says so (received ones are copied back after the wait)."""
+
+    def __init__(self, group):
+        self.group, self.ops, self.copies, self.sent = group, [], [], 0  # copies: (block, host buffer); sent: bytes
+
+    def send(self, block, peer):
+        self.ops.append(c10d.P2POp(c10d.isend, block.cpu() if _needs_host_staging(block, self.group) else block.contiguous(), peer, self.group))
+        self.sent += block.numel() * block.element_size()
+
+    def recv(self, block, peer):
+        buf = block
+        if _needs_host_staging(block, self.group):
+            buf = torch.empty(block.shape, dtype=block.dtype)
+            self.copies.append((block, buf))
+        self.ops.append(c10d.P2POp(c10d.irecv, buf, peer, self.group))
+
+    def run(self, stage):
+        if self.ops:
+            enter_stage(stage)
+            for req in c10d.batch_isend_irecv(self.ops):
+                req.wait()
+        for block, buf in self.copies:
+            block.copy_(buf)
+
+
 def halo_exchange(slab, rank, world, group=None):
     """Halo of both textures with ranks rank-1 / rank+1; non-periodic ends.  Downwards a rank sends its first
     `slab.halo_hi` owned slices (the lower neighbour's upper ghosts: 1 = the one-voxel halo, 2 = what sdfNormal's taps
     need in the sharded march), upwards its last owned slice.  Returns the number of bytes this rank sent."""
     if world == 1:
         return 0
-    staged = _needs_host_staging(slab.tex0, group)
-    ops, copies = [], []  # copies: (ghost slices, host buffer) to copy back after the wait when staging
-    sent = 0
-    n_owned = slab.z_end - slab.z_begin
-    depth = slab.halo_hi
+    batch = _P2PBatch(group)
+    n_owned, depth, lo = slab.z_end - slab.z_begin, slab.halo_hi, slab.ghost_lo
     assert n_owned >= depth, "a halo deeper than a neighbour's slab would need a second hop"
-
-    def send(block, peer):
-        nonlocal sent
-        ops.append(c10d.P2POp(c10d.isend, block.cpu() if staged else block, peer, group))
-        sent += block.numel() * 4
-
-    def recv(block, peer):
-        if staged:
-            buf = torch.empty(block.shape, dtype=block.dtype)
-            ops.append(c10d.P2POp(c10d.irecv, buf, peer, group))
-            copies.append((block, buf))
-        else:
-            ops.append(c10d.P2POp(c10d.irecv, block, peer, group))
-
-    lo = slab.ghost_lo
     for t in (slab.tex0, slab.tex1):
         # sends down then up, receives from above then from below: messages between a pair match in posting order
         if rank > 0:
-            send(t[lo:lo + depth], rank - 1)
+            batch.send(t[lo:lo + depth], rank - 1)
         if rank < world - 1:
-            send(t[lo + n_owned - 1:lo + n_owned], rank + 1)
+            batch.send(t[lo + n_owned - 1:lo + n_owned], rank + 1)
         if rank < world - 1:
-            recv(t[lo + n_owned:lo + n_owned + slab.ghost_hi], rank + 1)
+            batch.recv(t[lo + n_owned:lo + n_owned + slab.ghost_hi], rank + 1)
         if rank > 0:
-            recv(t[0:lo], rank - 1)
-    enter_stage(f"halo_exchange: batch_isend_irecv of {len(ops)} ops with ranks {rank - 1}/{rank + 1}")
-    for req in c10d.batch_isend_irecv(ops):
-        req.wait()
+            batch.recv(t[0:lo], rank - 1)
+    batch.run(f"halo_exchange: batch_isend_irecv of {len(batch.ops)} ops with ranks {rank - 1}/{rank + 1}")
     enter_stage("halo_exchange: done")
-    for dst, buf in copies:
-        dst.copy_(buf)
-    return sent
+    return batch.sent
+
+
+def _ptr(t):
+    """A tensor's address as a void* argument of the library (None: NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class SlabComm:
@@ -171,14 +187,20 @@ class SlabComm:
         self.pkg, self.rank, self.world, self.periodic, self.halo_hi = pkg, rank, world, periodic, halo_hi
         self.handle = None
         assert halo_hi in (1, 2)
+
+        def create(ident, how):  # sdfv_slab_comm_create with these 128 bytes -> its status; the handle is kept on success
+            handle = C.c_void_p()
+            flags = (capi.COMM_PERIODIC if periodic else 0) | (capi.COMM_HALO2 if halo_hi == 2 else 0)
+            enter_stage(f"SlabComm.__init__: sdfv_slab_comm_create{how}")
+            rc = pkg.lib.sdfv_slab_comm_create(ident, rank, world, flags, C.byref(handle))
+            if rc == 0:
+                self.handle = handle
+            return rc
+
         if ident is not None:
             ident = bytes(ident)
             assert len(ident) == capi.COMM_ID_BYTES
-            handle = C.c_void_p()
-            flags = (capi.COMM_PERIODIC if periodic else 0) | (capi.COMM_HALO2 if halo_hi == 2 else 0)
-            enter_stage(f"SlabComm.__init__: sdfv_slab_comm_create(rank {rank} of {world}) with the host's own id")
-            pkg.check(pkg.lib.sdfv_slab_comm_create((C.c_ubyte * capi.COMM_ID_BYTES)(*ident), rank, world, flags, C.byref(handle)))
-            self.handle = handle
+            pkg.check(create((C.c_ubyte * capi.COMM_ID_BYTES)(*ident), f"(rank {rank} of {world}) with the host's own id"))
             return
         on_gpu = world > 1 and c10d.get_backend(group) == "nccl"
         dev = "cuda" if on_gpu else "cpu"
@@ -203,12 +225,7 @@ class SlabComm:
             t = torch.tensor(list(ident), dtype=torch.uint8, device=dev)
             c10d.broadcast(t, src=c10d.get_global_rank(group, 0) if group is not None else 0, group=group)
             ident = (C.c_ubyte * capi.COMM_ID_BYTES)(*t.cpu().tolist())
-        handle = C.c_void_p()
-        flags = (capi.COMM_PERIODIC if periodic else 0) | (capi.COMM_HALO2 if halo_hi == 2 else 0)
-        enter_stage(f"SlabComm.__init__: sdfv_slab_comm_create = ncclCommInitRank(rank {rank} of {world}) on the library's communicator")
-        rc = pkg.lib.sdfv_slab_comm_create(ident, rank, world, flags, C.byref(handle))
-        if rc == 0:
-            self.handle = handle
+        rc = create(ident, f" = ncclCommInitRank(rank {rank} of {world}) on the library's communicator")
         try:
             agree(rc == 0, "sdfv_slab_comm_create")
         except Exception:
@@ -223,13 +240,8 @@ class SlabComm:
         pkg.check(pkg.lib.sdfv_slab_comm_unique_id(ident))
         return bytes(ident)
 
-    @property
-    def ghost_lo(self):
-        return 1 if (self.periodic or self.rank > 0) else 0
-
-    @property
-    def ghost_hi(self):
-        return self.halo_hi if (self.periodic or self.rank < self.world - 1) else 0
+    ghost_lo = property(lambda self: _ghost_counts(self.rank, self.world, self.periodic, self.halo_hi)[0])
+    ghost_hi = property(lambda self: _ghost_counts(self.rank, self.world, self.periodic, self.halo_hi)[1])
 
     @property
     def rccl_ranks(self):
@@ -249,8 +261,7 @@ class SlabComm:
         assert slab.ghost_lo == self.ghost_lo and slab.ghost_hi == self.ghost_hi
         assert slab.tex0.shape[0] == self.ghost_lo + n_owned + self.ghost_hi
         stream = torch.cuda.current_stream() if stream is None else stream
-        return (C.byref(grid), C.c_void_p(slab.tex0.data_ptr()), C.c_void_p(slab.tex1.data_ptr()),
-                C.c_void_p(stream.cuda_stream))
+        return C.byref(grid), _ptr(slab.tex0), _ptr(slab.tex1), C.c_void_p(stream.cuda_stream)
 
     def halo_exchange(self, grid, slab, stream=None):
         self.pkg.check(self.pkg.lib.sdfv_slab_halo_exchange(self.handle, *self._args(grid, slab, stream)))
@@ -264,8 +275,7 @@ class SlabComm:
             return
         assert dist.is_cuda and dist.dtype == torch.float32 and dist.is_contiguous() and \
             tuple(dist.shape) == tuple(slab.tex0.shape[:3])
-        self.pkg.check(self.pkg.lib.sdfv_slab_fill_step_commit(self.handle, C.byref(params), sdf_id, g, t0, t1,
-                                                               C.c_void_p(dist.data_ptr()), st))
+        self.pkg.check(self.pkg.lib.sdfv_slab_fill_step_commit(self.handle, C.byref(params), sdf_id, g, t0, t1, _ptr(dist), st))
 
     def march(self, rp, grid, slab, camera, width, height, want_aux=False, capacity=None, merge=True, stream=None):
         """sdfv_slab_march: the whole sharded march of one frame enqueued in one call -- `world` rounds back to back, the ray
@@ -285,24 +295,27 @@ class SlabComm:
             rgba = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
             aux = torch.empty((height, width, pkg.AUX_FLOATS), dtype=torch.int32, device=dev) if want_aux else None
             status = torch.zeros(2, dtype=torch.int32, device=dev)
-            pkg.check(pkg.lib.sdfv_slab_march(self.handle, C.byref(rp), C.byref(grid), C.c_void_p(slab.tex0.data_ptr()),
-                                              C.c_void_p(slab.tex1.data_ptr()), C.byref(camera), width, height,
-                                              C.c_void_p(rgba.data_ptr()), None if aux is None else C.c_void_p(aux.data_ptr()),
-                                              C.c_void_p(scratch.data_ptr()), n, capacity, pkg._capi.MARCH_MERGE if merge else 0,
-                                              C.c_void_p(status.data_ptr()), C.c_void_p(stream.cuda_stream)))
+            pkg.check(pkg.lib.sdfv_slab_march(self.handle, C.byref(rp), C.byref(grid), _ptr(slab.tex0), _ptr(slab.tex1), C.byref(camera),
+                                              width, height, _ptr(rgba), _ptr(aux), _ptr(scratch), n, capacity,
+                                              pkg._capi.MARCH_MERGE if merge else 0, _ptr(status), C.c_void_p(stream.cuda_stream)))
             self._march_scratch = scratch  # alive until the stream has run the rounds
             merged_aux = merge_sharded_aux(aux) if (want_aux and merge) else aux
         return rgba, merged_aux, status
 
     # ---- config 5's collectives over this communicator; every rank calls, nothing synchronises ----
+    @staticmethod
+    def _gather_words(gather, part, *args, **kw):
+        """The 8-bit UNORM plane (sdfv_march_desc.rgba8) is 4 bytes = one word per pixel: gathered as float32, viewed back."""
+        out = gather(part.view(torch.float32), *args, **kw)
+        return None if out is None else out.view(torch.uint8)
+
     def gather_bands(self, part, height, dst=0, stream=None, band_height=16):
         """sdfv_comm_gather_bands: part = [n_cam, band rows of this rank, W, C] rendered with bands=(rank, world, band_height) -> on
         `dst` the images [n_cam, height, W, C] (None elsewhere)."""
         pkg = self.pkg
         stream = torch.cuda.current_stream() if stream is None else stream
-        if part.dtype == torch.uint8:  # the 8-bit UNORM plane (sdfv_march_desc.rgba8): 4 bytes per pixel = one word per pixel
-            out = self.gather_bands(part.view(torch.float32), height, dst=dst, stream=stream, band_height=band_height)
-            return None if out is None else out.view(torch.uint8)
+        if part.dtype == torch.uint8:
+            return self._gather_words(self.gather_bands, part, height, dst=dst, stream=stream, band_height=band_height)
         n_cam, _, width, ch = (int(v) for v in part.shape)
         with torch.cuda.stream(stream):
             out = scratch = None
@@ -311,10 +324,8 @@ class SlabComm:
                 out = torch.empty((n_cam, height, width, ch), dtype=torch.float32, device=part.device)
                 scratch = torch.empty(max(n // 4, 4), dtype=torch.float32, device=part.device)
             enter_stage("SlabComm.gather_bands: sdfv_comm_gather_bands over the library communicator")
-            pkg.check(pkg.lib.sdfv_comm_gather_bands(self.handle, C.c_void_p(part.data_ptr()) if part.numel() else None, band_height, n_cam,
-                                                     width, height, ch, dst, None if out is None else C.c_void_p(out.data_ptr()),
-                                                     None if scratch is None else C.c_void_p(scratch.data_ptr()), n,
-                                                     C.c_void_p(stream.cuda_stream)))
+            pkg.check(pkg.lib.sdfv_comm_gather_bands(self.handle, _ptr(part if part.numel() else None), band_height, n_cam, width, height,
+                                                     ch, dst, _ptr(out), _ptr(scratch), n, C.c_void_p(stream.cuda_stream)))
         self._gather_scratch = scratch  # alive until the stream has run the scatter
         return out
 
@@ -322,16 +333,14 @@ class SlabComm:
         """sdfv_comm_gather_cameras: part = [cameras of this rank, H, W, C] (split_cameras) -> on `dst` [n_cameras, H, W, C]."""
         pkg = self.pkg
         stream = torch.cuda.current_stream() if stream is None else stream
-        if part.dtype == torch.uint8:  # the 8-bit UNORM plane: one 4-byte word per pixel
-            out = self.gather_cameras(part.view(torch.float32), n_cameras, dst=dst, stream=stream)
-            return None if out is None else out.view(torch.uint8)
+        if part.dtype == torch.uint8:
+            return self._gather_words(self.gather_cameras, part, n_cameras, dst=dst, stream=stream)
         _, height, width, ch = (int(v) for v in part.shape)
         with torch.cuda.stream(stream):
             out = torch.empty((n_cameras, height, width, ch), dtype=torch.float32, device=part.device) if self.rank == dst else None
             enter_stage("SlabComm.gather_cameras: sdfv_comm_gather_cameras over the library communicator")
-            pkg.check(pkg.lib.sdfv_comm_gather_cameras(self.handle, C.c_void_p(part.data_ptr()) if part.numel() else None, n_cameras,
-                                                       width, height, ch, dst, None if out is None else C.c_void_p(out.data_ptr()),
-                                                       C.c_void_p(stream.cuda_stream)))
+            pkg.check(pkg.lib.sdfv_comm_gather_cameras(self.handle, _ptr(part if part.numel() else None), n_cameras, width, height, ch,
+                                                       dst, _ptr(out), C.c_void_p(stream.cuda_stream)))
         return out
 
     def allgather_slabs(self, slab, dims, dist=None, stream=None):
@@ -348,12 +357,8 @@ class SlabComm:
             own_d = None if dist is None else dist[slab.ghost_lo:]
             enter_stage("SlabComm.allgather_slabs: sdfv_comm_allgather_slabs over the library communicator")
             pkg.check(pkg.lib.sdfv_comm_allgather_slabs(self.handle, (C.c_uint32 * 3)(*[int(d) for d in dims]),
-                                                        (C.c_uint32 * len(bounds))(*bounds), C.c_void_p(slab.owned0.data_ptr()),
-                                                        C.c_void_p(slab.owned1.data_ptr()),
-                                                        None if own_d is None else C.c_void_p(own_d.data_ptr()),
-                                                        C.c_void_p(out0.data_ptr()), C.c_void_p(out1.data_ptr()),
-                                                        None if outd is None else C.c_void_p(outd.data_ptr()),
-                                                        C.c_void_p(stream.cuda_stream)))
+                                                        (C.c_uint32 * len(bounds))(*bounds), _ptr(slab.owned0), _ptr(slab.owned1),
+                                                        _ptr(own_d), _ptr(out0), _ptr(out1), _ptr(outd), C.c_void_p(stream.cuda_stream)))
         return (out0, out1) if dist is None else (out0, out1, outd)
 
     def join(self, stream=None):
@@ -483,35 +488,27 @@ def _exchange_rays(down, up, rank, world, group):
     """Rays leaving downwards go to rank-1, upwards to rank+1; returns what the two neighbours sent here, concatenated.
     Counts travel first (the lists are data dependent), then the payloads."""
     dev = down.device
-    staged = _needs_host_staging(down, group)
-    cdev = torch.device("cpu") if staged else dev
+    cdev = torch.device("cpu") if _needs_host_staging(down, group) else dev
     peers = [(rank - 1, down), (rank + 1, up)]
     peers = [(p, t) for p, t in peers if 0 <= p < world]
-    send_n = [torch.tensor([t.shape[0]], dtype=torch.int64, device=cdev) for _, t in peers]
     recv_n = [torch.zeros(1, dtype=torch.int64, device=cdev) for _ in peers]
-    ops = []
-    for (p, _), sn, rn in zip(peers, send_n, recv_n):
-        ops += [c10d.P2POp(c10d.isend, sn, p, group), c10d.P2POp(c10d.irecv, rn, p, group)]
-    enter_stage(f"_exchange_rays: ray counts with {[p for p, _ in peers]}")
-    for req in c10d.batch_isend_irecv(ops):
-        req.wait()
-    ops, bufs = [], []
+    counts = _P2PBatch(group)
     for (p, t), rn in zip(peers, recv_n):
-        n = int(rn.item())
+        counts.send(torch.tensor([t.shape[0]], dtype=torch.int64, device=cdev), p)
+        counts.recv(rn, p)
+    counts.run(f"_exchange_rays: ray counts with {[p for p, _ in peers]}")
+    payloads, bufs = _P2PBatch(group), []
+    for (p, t), rn in zip(peers, recv_n):
         if t.shape[0]:
-            ops.append(c10d.P2POp(c10d.isend, t.cpu() if staged else t.contiguous(), p, group))
-        if n:
-            buf = torch.empty((n, t.shape[1]), dtype=t.dtype, device=cdev)
-            ops.append(c10d.P2POp(c10d.irecv, buf, p, group))
-            bufs.append(buf)
-    if ops:
-        enter_stage(f"_exchange_rays: ray payloads ({len(ops)} ops)")
-        for req in c10d.batch_isend_irecv(ops):
-            req.wait()
+            payloads.send(t, p)
+        if int(rn.item()):
+            bufs.append(torch.empty((int(rn.item()), t.shape[1]), dtype=t.dtype, device=dev))
+            payloads.recv(bufs[-1], p)
+    payloads.run(f"_exchange_rays: ray payloads ({len(payloads.ops)} ops)")
     enter_stage("_exchange_rays: done")
     if not bufs:
         return torch.empty((0, down.shape[1]), dtype=down.dtype, device=dev)
-    return torch.cat([b.to(dev) for b in bufs], dim=0)
+    return torch.cat(bufs, dim=0)
 
 
 def merge_sharded_aux(aux_sum):
@@ -590,25 +587,33 @@ def raymarch_sharded(pkg, rp, grid, slab, camera, width, height, rank, world, gr
     return rgba, merge_sharded_aux(merge(m.aux))
 
 
+def _gather_ragged(part, counts, axis, rank, world, dst, group, stage):
+    """The ranks' ragged shares (rank r holds counts[r] entries along `axis`) over torch.distributed: each is padded along `axis`
+    to the largest for the collective (gather to `dst`, all_gather when dst is None; staged through host memory under gloo) and
+    trimmed afterwards.  -> the `world` pieces in rank order on part's device; None where nothing is received.  stage: for enter_stage."""
+    shape = list(part.shape)
+    shape[axis] = max(counts)
+    padded = torch.zeros(shape, dtype=part.dtype, device="cpu" if _needs_host_staging(part, group) else part.device)
+    padded.narrow(axis, 0, part.shape[axis]).copy_(part)
+    receives = dst is None or rank == dst
+    got = [torch.empty_like(padded) for _ in range(world)] if receives else None
+    enter_stage(stage)
+    if dst is None:
+        c10d.all_gather(got, padded, group=group)
+    else:
+        c10d.gather(padded, got, dst=dst, group=group)
+    return [g.narrow(axis, 0, n).to(part.device) for g, n in zip(got, counts)] if receives else None
+
+
 def gather_replica(slab, dims, world, group=None, comm=None):
     """Full grid on every rank from the slabs (all-gather; slabs may differ by one slice, so each is
     padded to the deepest slab for the collective and trimmed afterwards).  comm: a (non-periodic) SlabComm -- the library's
     own collective then (sdfv_comm_allgather_slabs); torch.distributed is the gloo / CPU-test transport."""
     if comm is not None and comm.handle and not comm.periodic:
         return comm.allgather_slabs(slab, dims)
-    ranges = [slab_range(dims[2], r, world) for r in range(world)]
-    deepest = max(z1 - z0 for z0, z1 in ranges)
-    outs = []
-    staged = _needs_host_staging(slab.tex0, group)
-    for owned in (slab.owned0, slab.owned1):
-        dev = torch.device("cpu") if staged else owned.device
-        padded = torch.zeros((deepest, dims[1], dims[0], 4), dtype=owned.dtype, device=dev)
-        padded[:owned.shape[0]] = owned
-        parts = [torch.empty_like(padded) for _ in range(world)]
-        enter_stage("gather_replica: all_gather of the slabs")
-        c10d.all_gather(parts, padded, group=group)
-        outs.append(torch.cat([p[:z1 - z0] for p, (z0, z1) in zip(parts, ranges)], dim=0).to(owned.device))
-    return outs[0], outs[1]
+    depths = [z1 - z0 for z0, z1 in (slab_range(dims[2], r, world) for r in range(world))]
+    stage = "gather_replica: all_gather of the slabs"
+    return tuple(torch.cat(_gather_ragged(owned, depths, 0, None, world, None, group, stage), dim=0) for owned in (slab.owned0, slab.owned1))
 
 
 def split_cameras(n_cameras, rank, world):
@@ -663,35 +668,18 @@ def gather_bands(part, height, rank, world, dst=0, group=None, comm=None, band_h
         return part
     if comm is not None and comm.handle:
         return comm.gather_bands(part, height, dst=dst, band_height=band_height)
-    deepest = max(len(band_rows(height, r, world, band_height)) for r in range(world))
-    staged = _needs_host_staging(part, group)
-    dev = torch.device("cpu") if staged else part.device
-    padded = torch.zeros((part.shape[0], deepest) + tuple(part.shape[2:]), dtype=part.dtype, device=dev)
-    padded[:, :part.shape[1]] = part
-    got = [torch.empty_like(padded) for _ in range(world)] if rank == dst else None
-    enter_stage("gather_bands: gather of the tile bands")
-    c10d.gather(padded, got, dst=dst, group=group)
-    if rank != dst:
-        return None
-    return assemble_bands([g[:, :len(band_rows(height, r, world, band_height))] for r, g in enumerate(got)], height, band_height).to(part.device)
+    rows = [len(band_rows(height, r, world, band_height)) for r in range(world)]
+    got = _gather_ragged(part, rows, 1, rank, world, dst, group, "gather_bands: gather of the tile bands")
+    return None if got is None else assemble_bands(got, height, band_height)
 
 
 def gather_rows(band, height, rank, world, dst=0, group=None, tile=16):
     """Collect the row bands of split_rows ([n_cam, rows, W, 4] each) on rank `dst` -> [n_cam, height, W, 4]."""
     if world == 1:
         return band
-    ranges = [split_rows(height, r, world, tile) for r in range(world)]
-    deepest = max(y1 - y0 for y0, y1 in ranges)
-    staged = _needs_host_staging(band, group)
-    dev = torch.device("cpu") if staged else band.device
-    padded = torch.zeros((band.shape[0], deepest) + tuple(band.shape[2:]), dtype=band.dtype, device=dev)
-    padded[:, :band.shape[1]] = band
-    parts = [torch.empty_like(padded) for _ in range(world)] if rank == dst else None
-    enter_stage("gather_rows: gather of the row bands")
-    c10d.gather(padded, parts, dst=dst, group=group)
-    if rank != dst:
-        return None
-    return torch.cat([p[:, :y1 - y0] for p, (y0, y1) in zip(parts, ranges)], dim=1).to(band.device)
+    rows = [y1 - y0 for y0, y1 in (split_rows(height, r, world, tile) for r in range(world))]
+    got = _gather_ragged(band, rows, 1, rank, world, dst, group, "gather_rows: gather of the row bands")
+    return None if got is None else torch.cat(got, dim=1)
 
 
 def gather_images(rgba, n_cameras, rank, world, dst=0, group=None, comm=None):
@@ -703,13 +691,5 @@ def gather_images(rgba, n_cameras, rank, world, dst=0, group=None, comm=None):
     if comm is not None and comm.handle:
         return comm.gather_cameras(rgba, n_cameras, dst=dst)
     counts = [len(split_cameras(n_cameras, r, world)) for r in range(world)]
-    staged = _needs_host_staging(rgba, group)
-    dev = torch.device("cpu") if staged else rgba.device
-    padded = torch.zeros((max(counts),) + tuple(rgba.shape[1:]), dtype=rgba.dtype, device=dev)
-    padded[:rgba.shape[0]] = rgba
-    parts = [torch.empty_like(padded) for _ in range(world)] if rank == dst else None
-    enter_stage("gather_images: gather of the cameras' images")
-    c10d.gather(padded, parts, dst=dst, group=group)
-    if rank != dst:
-        return None
-    return torch.cat([p[:c] for p, c in zip(parts, counts)], dim=0).to(rgba.device)
+    got = _gather_ragged(rgba, counts, 0, rank, world, dst, group, "gather_images: gather of the cameras' images")
+    return None if got is None else torch.cat(got, dim=0)

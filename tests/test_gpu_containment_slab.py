@@ -1,7 +1,7 @@
 """Containment of sdfv_slab_fill_step[_commit] (tests/arena.py): the slab's textures -- lower ghost, owned slices, upper ghost(s)
 -- and its distance volume are carved from one arena, and a loopback communicator (world 1, periodic: the rank exchanges with
 itself) runs every form of the step.  The owned slices must be the oracle's, the ghosts the wrap, and nothing beside the
-allocation may change: the strided launch over the boundary slices (launch_fill_slices), the boundary-first ordered launch
+allocation may change: the plain dense launch, the boundary-first ordered launch (whole, and split between the two streams)
 and the copies into the ghosts all address the slab through slice offsets.  (The RCCL transfer itself is not under test.)"""
 import functools
 import importlib
