@@ -66,7 +66,9 @@ typedef enum sdfv_status {
     SDFV_ERR_UNKNOWN_SDF = -2, /* ffi.rs:46-49 "Failed to find SDF with ID" */
     SDFV_ERR_HIP = -3,
     SDFV_ERR_NO_DEVICE = -4,
-    SDFV_ERR_COMM = -5 /* RCCL could not be loaded, or one of its calls failed */
+    SDFV_ERR_COMM = -5, /* RCCL could not be loaded, or one of its calls failed */
+    SDFV_ERR_COMPILE = -6 /* sdfv_program_compile: the run-time compiler library could not be loaded, or the compilation failed
+                           * (sdfv_last_error() carries the start of the compiler's log) */
 } sdfv_status;
 
 /* src/sdf/mod.rs:104-118: #[repr(C)] struct SDFSample, 28 bytes */
@@ -252,6 +254,10 @@ typedef enum sdfv_option {
                                         * (which uses the lod for the tap distance only) nor by the sharded march (which refuses L != 1).
                                         * Per thread like every option: sdfv_raymarch_host, SDFViewer::render, sdfv_viewer_render and
                                         * sdfv_scene_render march on the caller's thread and follow it */
+    SDFV_OPT_HIPRTC_LIBRARY = 17,      /* PROCESS-wide, before the first sdfv_program_compile: value = address of a NUL-terminated path of
+                                        * the run-time compiler library that call loads (copied; 0 = "libhiprtc.so" by name, the default).
+                                        * The rules of SDFV_OPT_RCCL_LIBRARY: refused once the library is loaded (a path that fails to load
+                                        * is final too), sdfv_get_option hands back a copy that belongs to the calling thread */
     SDFV_OPT_TUNING_WAVE_TIMING = 100, /* tuning build only (-DSDFV_TUNING): DEVICE address of 32 B per raymarch wave */
     SDFV_OPT_TUNING_TILE_ORDER = 102,  /* tuning build only: DEVICE address of tiles_x * tiles_y uint32 tile numbers (row-major
                                         * tile index by * tiles_x + bx): workgroup L of a single-camera launch renders tile
@@ -852,6 +858,44 @@ int sdfv_program_raymarch(const sdfv_program_march_desc *desc, void *stream);
  * library reads it (absent fields 0 / NULL) and *normal_h the taps' distance it will use.  What the host mirror calls, so
  * that both routes refuse the same descriptors with the same messages.  Output pointers are checked for alignment only. */
 int sdfv_program_raymarch_check(const sdfv_program_march_desc *desc, sdfv_program_march_desc *checked, float *normal_h);
+
+/* ---- SDF programs compiled to kernels of their own, at run time ----
+ * An interpreted program pays for the interpreter per evaluation (instruction fetch, dispatch, the stack's shifts).
+ * sdfv_program_compile turns ONE program into gfx kernels in which every instruction is a compile-time constant: it generates a
+ * small translation unit (the instructions as constants, operands as their 32-bit patterns) around the same headers the
+ * library's own kernels are built from, and compiles it with the run-time compiler (libhiprtc, bound with dlopen on the first
+ * compile: a process that never compiles never loads it) under the library's own code-affecting flags.  Same text, same
+ * compiler, same flags: what a compiled route writes equals what the interpreter writes, word for word.
+ *
+ * *out is a NEW handle (handles stay immutable) with the same instructions and box, freed with sdfv_program_free and accepted by
+ * every entry point that takes an sdfv_program.  The routes named in `routes` launch the specialised kernels -- same argument
+ * checks, same options, same launch geometry, same stream as the interpreted call --; every other route (mesh, normals, the
+ * box launch and the scan of sdfv_program_grid_pass, the host mirror) interprets as before.
+ * arch: NULL = the current device's architecture (SDFV_ERR_NO_DEVICE without one), or a name such as "gfx950", with which the
+ * call needs no device.  When a device is current and matches, the call also loads the code object and makes the device copy of
+ * the instructions before it returns, so the first covered call can be captured into a graph; on another device the first
+ * use loads it (synchronously).  A compiled route on a device of another architecture is SDFV_ERR_INVALID_ARGUMENT (the message
+ * names both), before anything is loaded, launched or written; that handle's other routes still work.
+ * A compile takes of the order of a second per route: worth it for a model that is filled or rendered many times, not for an
+ * editor's snapshots.  Compilations are serialised; launches through a finished handle are as thread-safe as a plain one's.
+ * SDFV_ERR_INVALID_ARGUMENT: p or out NULL, routes 0 or with unknown bits.  SDFV_ERR_COMPILE: see there.  *out is NULL on failure. */
+#define SDFV_COMPILE_FILL   1u /* sdfv_program_fill_grid_commit, and sdfv_program_grid_pass where it IS the dense fill */
+#define SDFV_COMPILE_POINTS 2u /* sdfv_program_sample_points (+ _host, which runs on the device) */
+#define SDFV_COMPILE_MARCH  4u /* sdfv_program_raymarch */
+int sdfv_program_compile(const sdfv_program *p, uint32_t routes, const char *arch, sdfv_program **out);
+typedef struct sdfv_compiled_info {
+    uint32_t size;   /* in: sizeof(sdfv_compiled_info), size-prefixed like sdfv_march_desc */
+    uint32_t routes; /* 0 for a plain handle (and every field below 0 / "") */
+    char arch[32];
+    double compile_seconds;
+    uint64_t code_bytes;
+    uint64_t launches; /* specialised kernels launched through this handle: 1 per fill, the staged and the tail launch of a sampler
+                        * call, 1 per chunk of 16 cameras of a march */
+} sdfv_compiled_info;
+int sdfv_program_compiled_info(const sdfv_program *p, sdfv_compiled_info *info); /* info->size too small: SDFV_ERR_INVALID_ARGUMENT */
+/* The code object (an ELF for `arch`) and the generated translation unit (NUL-terminated); both stay valid until the handle is
+ * freed, either output may be NULL.  A plain handle is SDFV_ERR_INVALID_ARGUMENT. */
+int sdfv_program_compiled_code(const sdfv_program *p, const void **code, size_t *bytes, const char **source);
 
 /* rows a band set holds: bands of band_height (16 or 8; 0 = 16) rows, the last one of the image possibly short */
 uint32_t sdfv_band_rows_ex(uint32_t height, uint32_t band_first, uint32_t band_step, uint32_t band_height);

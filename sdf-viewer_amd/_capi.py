@@ -99,6 +99,15 @@ class ProgramMarchDesc(C.Structure):
 
 assert C.sizeof(ProgramMarchDesc) == 88
 
+
+class CompiledInfo(C.Structure):
+    """sdfv_compiled_info (size-prefixed): what sdfv_program_compiled_info reports about a handle."""
+    _fields_ = [("size", C.c_uint32), ("routes", C.c_uint32), ("arch", C.c_char * 32), ("compile_seconds", C.c_double),
+                ("code_bytes", C.c_uint64), ("launches", C.c_uint64)]
+
+
+assert C.sizeof(CompiledInfo) == 64
+
 PROTOTYPES = {
     "sdfv_raymarch_ex": (C.c_int, [C.POINTER(MarchDesc), C.c_void_p]),
     "sdfv_abi_version": (C.c_uint32, []),
@@ -198,6 +207,10 @@ PROTOTYPES = {
                                          C.c_void_p, C.c_uint32, C.c_void_p]),
     "sdfv_program_raymarch": (C.c_int, [C.POINTER(ProgramMarchDesc), C.c_void_p]),
     "sdfv_program_raymarch_check": (C.c_int, [C.POINTER(ProgramMarchDesc), C.POINTER(ProgramMarchDesc), C.POINTER(C.c_float)]),
+    # ... compiled to kernels of their own
+    "sdfv_program_compile": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "sdfv_program_compiled_info": (C.c_int, [C.c_void_p, C.POINTER(CompiledInfo)]),
+    "sdfv_program_compiled_code": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_char_p)]),
     # ... meshing
     "sdfv_program_normal_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
     "sdfv_program_mesh_extract": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
@@ -249,6 +262,7 @@ OPT_RAYMARCH_CAMERA_STAGING = 12
 OPT_PASS_FORM = 13  # 0 auto | 1 per-voxel kernels for unflagged passes (A/B)
 OPT_RCCL_LIBRARY = 14  # process-wide: address of the path of the RCCL-ABI library to load (before the first communicator)
 OPT_PASS_LOADS = 15  # 0 auto (SDFV_PASS_EXPECT_NOOP decides) | 1 cached | 2 nontemporal loads for update_required
+OPT_HIPRTC_LIBRARY = 17  # process-wide: address of the path of the run-time compiler library (before the first sdfv_program_compile)
 OPT_RAYMARCH_LOD_FILTER = 16  # a loading grid (lod != 1): 0 sdfSampleRawNearest (default) | 1 trilinear over the loaded lattice
 OPT_EXT_SRGB_QUANT = 10  # Srgba::from(Vec3): 0 truncate (default) | 1 round
 OPT_TUNING_WAVE_TIMING = 100
@@ -261,6 +275,8 @@ PASS_FRESH_GRID, PASS_SAME_LOAD, PASS_VIRGIN_GRID, PASS_VOLUME_INTERLEAVED, PASS
 (OP_SPHERE, OP_CUBE, OP_BOX, OP_CYLINDER, OP_TORUS, OP_PLANE, OP_PUSH_AFFINE, OP_PUSH_SCALE, OP_POP, OP_POP_SCALE, OP_UNION,
  OP_INTERSECT, OP_SUBTRACT, OP_SMOOTH_UNION, OP_SMOOTH_SUBTRACT, OP_ROUND, OP_SHELL, OP_MATERIAL) = range(1, 19)
 PROGRAM_MAX_OPS, PROGRAM_MAX_VALUES, PROGRAM_MAX_FRAMES = 256, 8, 4
+COMPILE_FILL, COMPILE_POINTS, COMPILE_MARCH = 1, 2, 4  # SDFV_COMPILE_*: the routes sdfv_program_compile specialises
+ERR_COMPILE = -6
 FILL_FORM = {"auto": 0, "rows": 1, "flat": 2}
 COMM_ID_BYTES = 128
 RAY_BUFFER_HEADER_BYTES = 16

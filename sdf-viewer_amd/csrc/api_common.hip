@@ -100,6 +100,26 @@ static bool set_rccl_library_path(const char* path) {
     g_rccl_path = path ? path : "";
     return true;
 }
+namespace {
+std::mutex g_hiprtc_path_mutex;
+std::string g_hiprtc_path;  // SDFV_OPT_HIPRTC_LIBRARY (process-wide: the run-time compiler is loaded once per process)
+bool g_hiprtc_loaded = false;
+}  // namespace
+std::string hiprtc_library_path_copy() {
+    std::lock_guard<std::mutex> lock(g_hiprtc_path_mutex);
+    return g_hiprtc_path;
+}
+const char* claim_hiprtc_library_path() {
+    std::lock_guard<std::mutex> lock(g_hiprtc_path_mutex);
+    g_hiprtc_loaded = true;
+    return g_hiprtc_path.c_str();
+}
+static bool set_hiprtc_library_path(const char* path) {
+    std::lock_guard<std::mutex> lock(g_hiprtc_path_mutex);
+    if (g_hiprtc_loaded) return false;
+    g_hiprtc_path = path ? path : "";
+    return true;
+}
 }  // namespace sdfv
 
 using namespace sdfv;
@@ -169,6 +189,13 @@ int sdfv_set_option(uint32_t option, uint64_t value) {
                 return set_error(SDFV_ERR_INVALID_ARGUMENT, "SDFV_OPT_RCCL_LIBRARY: RCCL has already been loaded in this process");
             return SDFV_OK;
         }
+        case SDFV_OPT_HIPRTC_LIBRARY: {  // the same rules for the run-time compiler library of sdfv_program_compile
+            const char* path = reinterpret_cast<const char*>((uintptr_t)value);
+            if (path && strnlen(path, 4096) >= 4096) break;
+            if (!sdfv::set_hiprtc_library_path(path))
+                return set_error(SDFV_ERR_INVALID_ARGUMENT, "SDFV_OPT_HIPRTC_LIBRARY: the run-time compiler has already been loaded in this process");
+            return SDFV_OK;
+        }
         case SDFV_OPT_RAYMARCH_WAVES_PER_SIMD:
             if (value == 1 || value > 7) break;  // 0 auto (the launcher's rule) | 2..6 cap | 7 never cap
             g_options.raymarch_waves_per_simd = (uint32_t)value;
@@ -206,6 +233,12 @@ int sdfv_get_option(uint32_t option, uint64_t* value) {
         case SDFV_OPT_RCCL_LIBRARY: {  // address of a copy that belongs to the CALLING THREAD ("" = by name): valid until this
             thread_local std::string copy;  // thread asks again, whatever another thread sets meanwhile
             copy = sdfv::rccl_library_path_copy();
+            *value = (uint64_t)(uintptr_t)copy.c_str();
+            return SDFV_OK;
+        }
+        case SDFV_OPT_HIPRTC_LIBRARY: {  // likewise
+            thread_local std::string copy;
+            copy = sdfv::hiprtc_library_path_copy();
             *value = (uint64_t)(uintptr_t)copy.c_str();
             return SDFV_OK;
         }

@@ -304,11 +304,13 @@ int sdfv_program_fill_grid_commit(const sdfv_program* p, const sdfv_grid* grid, 
     if (int rc = need_device()) return rc;
     sdfv::ProgramFillArgs a;
     memset(&a, 0, sizeof(a));
+    sdfv::ProgramKernels compiled;
+    if (int rc = program_compiled_kernels(p, SDFV_COMPILE_FILL, &compiled)) return rc;
     if (int rc = program_on_device(p, &a.ops, &a.n_ops)) return rc;
     set_grid_fill_args(a, *grid, tex0, tex1, dist, (flags & SDFV_PASS_VOLUME_INTERLEAVED) ? 1u : 0u);
     a.nontemporal = fill_launch_config(dist != nullptr).nontemporal ? 1u : 0u;
     if (int rc = check_one_launch(a)) return rc;
-    SDFV_HIP_RETURN(sdfv::launch_program_fill(a, (hipStream_t)stream));
+    SDFV_HIP_RETURN(sdfv::launch_program_fill(a, compiled, (hipStream_t)stream));
 }
 
 int sdfv_program_grid_pass(const sdfv_program* p, const sdfv_grid* grid, uint32_t step, const float* changed_box, float* tex0,
@@ -387,7 +389,9 @@ int sdfv_program_grid_pass(const sdfv_program* p, const sdfv_grid* grid, uint32_
     // (AIR_DIST by contract) or over a fresh grid (AIR_DIST is what it holds)
     if (whole && step == 1 && (dist || (flags & SDFV_PASS_FRESH_GRID)) && (uint64_t)f.H * f.slab_d <= 0x7fffffffull && f.W <= 0x7fffffffu) {
         f.nontemporal = fill_launch_config(dist != nullptr).nontemporal ? 1u : 0u;
-        SDFV_HIP_RETURN(sdfv::launch_program_fill(f, (hipStream_t)stream));
+        sdfv::ProgramKernels compiled;  // the one place where a pass IS the dense fill: a compiled handle's FILL route
+        if (int rc = program_compiled_kernels(p, SDFV_COMPILE_FILL, &compiled)) return rc;
+        SDFV_HIP_RETURN(sdfv::launch_program_fill(f, compiled, (hipStream_t)stream));
     }
     SDFV_HIP(sdfv::launch_program_pass_box(a, (hipStream_t)stream));
     if (whole) return SDFV_OK;

@@ -39,6 +39,9 @@ inline const Options& options() { return g_options; }
 // (claim_rccl_library_path: the path, and from that moment on SDFV_OPT_RCCL_LIBRARY is refused -- one RCCL per process)
 std::string rccl_library_path_copy();
 const char* claim_rccl_library_path();
+// SDFV_OPT_HIPRTC_LIBRARY, by the same rules: the run-time compiler library sdfv_program_compile loads (empty = libhiprtc.so by name)
+std::string hiprtc_library_path_copy();
+const char* claim_hiprtc_library_path();
 // Formats the thread-local message sdfv_last_error() returns and hands `code` back.
 int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int hip_fail(hipError_t e, const char* what);  // SDFV_ERR_NO_DEVICE or SDFV_ERR_HIP, with HIP's text
@@ -146,6 +149,13 @@ struct DeviceFacts {
 const DeviceFacts& device_facts();
 // An SDF program's instructions on the current device (copied there on the first use), their count and, if asked for, its box.
 int program_on_device(const sdfv_program* p, const sdfv_prog_op** ops, uint32_t* n_ops, const float** bb = nullptr);
+// The specialised kernels a handle has for `route` (one SDFV_COMPILE_* bit) on the current device, for the launchers of
+// program_kernels.h / program_march_kernels.h: *k stays empty for a plain handle and for a route that was not compiled (the
+// launcher then interprets).  A compiled route on a device of another architecture is SDFV_ERR_INVALID_ARGUMENT, decided
+// before anything is loaded; the first use on a device loads the code object (synchronously).  Needs a current device.
+struct ProgramKernels;
+int program_compiled_kernels(const sdfv_program* p, uint32_t route, ProgramKernels* k);
+void program_release_compiled(sdfv_program* p);  // sdfv_program_free's share: the modules and the code
 // Dense fill of `slab` in boundary-first workgroup order (fill_kernels.h): the `lead` first slices and the last one come
 // first, optionally copied into the packed staging buffers.
 struct OrderedFill {

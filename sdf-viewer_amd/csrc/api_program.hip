@@ -9,19 +9,12 @@
 #include <vector>
 
 #include "api_internal.h"
+#include "program_handle.h"
 #include "program_kernels.h"
 #include "program_march_kernels.h"
 #include "program_mesh_kernels.h"
 
 using namespace sdfv;
-
-// The handle: the validated instructions (host) and one device copy per device that has used it.
-struct sdfv_program {
-    std::vector<sdfv_prog_op> ops;
-    float bb[6];
-    std::mutex mu;
-    std::vector<std::pair<int, void*>> device_copies;  // (HIP device, n * 64 bytes)
-};
 
 namespace {
 
@@ -156,6 +149,7 @@ int sdfv_program_create(const sdfv_prog_op* ops, size_t n, const float bb[6], sd
 void sdfv_program_free(sdfv_program* p) {
     if (!p) return;
     for (const auto& c : p->device_copies) (void)hipFree(c.second);
+    program_release_compiled(p);
     delete p;
 }
 
@@ -171,9 +165,15 @@ int sdfv_program_sample_points(const sdfv_program* p, const float* points, size_
                                void* stream) {
     const sdfv_prog_op* dev_ops = nullptr;
     uint32_t n_ops = 0;
-    if (int rc = program_elements_ready(p, points, out, n, "points and out", &dev_ops, &n_ops)) return rc;
-    if (!dev_ops) return SDFV_OK;
-    SDFV_HIP_RETURN(sdfv::launch_program_sample_points(dev_ops, n_ops, points, n, distance_only != 0, out,
+    if (!p) return set_error(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if (int rc = check_point_buffers(points, out, n)) return rc;
+    if (int rc = check_word_aligned("points and out", points, out)) return rc;
+    if (int rc = need_device()) return rc;
+    if (n == 0) return SDFV_OK;
+    sdfv::ProgramKernels compiled;  // (a compiled handle on the wrong device is refused before its device copy is made)
+    if (int rc = program_compiled_kernels(p, SDFV_COMPILE_POINTS, &compiled)) return rc;
+    if (int rc = program_on_device(p, &dev_ops, &n_ops)) return rc;
+    SDFV_HIP_RETURN(sdfv::launch_program_sample_points(dev_ops, n_ops, points, n, distance_only != 0, out, compiled,
                                                 (hipStream_t)stream));
 }
 
@@ -227,6 +227,8 @@ int sdfv_program_raymarch(const sdfv_program_march_desc* desc, void* stream) {
     if (d.n_cameras == 0 || d.width == 0 || d.y0 == d.y1) return SDFV_OK;
     sdfv::ProgramMarchArgs a;
     memset(&a, 0, sizeof(a));
+    sdfv::ProgramKernels compiled;
+    if (int rc = program_compiled_kernels(d.program, SDFV_COMPILE_MARCH, &compiled)) return rc;
     if (int rc = program_on_device(d.program, &a.f.ops, &a.f.n_ops)) return rc;
     a.f.width = d.width;
     a.f.height = d.height;
@@ -242,7 +244,7 @@ int sdfv_program_raymarch(const sdfv_program_march_desc* desc, void* stream) {
         a.n_cameras = nc;
         memcpy(a.cameras, d.cameras + c0, nc * sizeof(sdfv_camera));
         point_outputs_at(a, pixels_per_cam, c0, d.rgba, d.rgba8, d.aux, d.depth);
-        SDFV_HIP(sdfv::launch_program_march(a, (hipStream_t)stream));
+        SDFV_HIP(sdfv::launch_program_march(a, compiled, (hipStream_t)stream));
     }
     return SDFV_OK;
 }

@@ -18,7 +18,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#if defined(__HIPCC_RTC__)  // the run-time compiler is handed the headers by name (program_compile.hip)
+#include "sdfgrid.h"
+#else
 #include "../../include/sdfgrid.h"
+#endif
 
 namespace sdfv {
 

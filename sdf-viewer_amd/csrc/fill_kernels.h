@@ -4,7 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#if defined(__HIPCC_RTC__)  // the run-time compiler is handed the headers by name (program_compile.hip)
+#include "sdfgrid.h"
+#else
 #include "../../include/sdfgrid.h"
+#endif
 
 namespace sdfv {
 
@@ -103,6 +107,7 @@ struct FillLaunch {
     bool xcd_pairing = false;                     // the device places workgroup b on XCD b % 8 (eight XCDs)
 };
 
+#if !defined(__HIPCC_RTC__)  // (host only: the run-time compiler reads this header for FillArgs)
 hipError_t launch_fill_dense(const FillArgs& a, const FillLaunch& cfg, hipStream_t stream);
 // Boundary-first order.  ordered_blocks() = {workgroups per slice, total} or {0, 0} when the slab's shape does not
 // allow it (rows that do not fill whole workgroups); launch_fill_dense_ordered runs logical workgroups
@@ -131,5 +136,6 @@ hipError_t launch_grid_init(float* tex0, float* tex1, uint64_t n_voxels, float a
 // [air; 4] (+ dist = air) into every row of the slab whose y or global z is not a multiple of step (step 0: every row)
 hipError_t launch_grid_init_unvisited(float* tex0, float* tex1, float* dist, uint32_t W, uint32_t H, uint32_t z_begin,
                                       uint32_t slab_d, uint32_t step, float air, uint32_t dist_ilv, hipStream_t stream);
+#endif
 
 }  // namespace sdfv

@@ -328,6 +328,7 @@ inline uint32_t blocks_for(uint64_t n, uint64_t max_n = ~0ull) { return n > max_
 // n elements through a kernel with a staged form: whole workgroups of kBlock through `staged(whole)` if `aligned` (the
 // pointers allow 16-byte accesses), the rest -- [done, n) -- through `scalar(blocks, done)`, which takes any alignment.
 // An n that needs more workgroups than one launch takes is refused before anything is launched, whatever the alignment.
+#if !defined(__HIPCC_RTC__)  // (host only: the run-time compiler reads this header for the device code)
 template <typename Staged, typename Scalar>
 hipError_t launch_staged_then_tail(size_t n, bool aligned, Staged&& staged, Scalar&& scalar) {
     if (n == 0) return hipSuccess;
@@ -339,5 +340,6 @@ hipError_t launch_staged_then_tail(size_t n, bool aligned, Staged&& staged, Scal
     if (done < n) scalar(all - whole, done);
     return hipGetLastError();
 }
+#endif
 
 }  // namespace sdfv

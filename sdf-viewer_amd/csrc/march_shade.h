@@ -11,7 +11,11 @@
 #include <math.h>
 #include <stdint.h>
 
+#if defined(__HIPCC_RTC__)  // the run-time compiler is handed the headers by name (program_compile.hip)
+#include "sdfgrid.h"
+#else
 #include "../../include/sdfgrid.h"
+#endif
 
 #if defined(__HIPCC__)
 #define SDFV_SHADE_FN __device__ __forceinline__

@@ -21,7 +21,11 @@
 #include <math.h>
 #include <stdint.h>
 
+#if defined(__HIPCC_RTC__)  // the run-time compiler is handed the headers by name (program_compile.hip)
+#include "sdfgrid.h"
+#else
 #include "../../include/sdfgrid.h"
+#endif
 
 #if defined(__HIPCC__)
 #define SDFV_PROG_FN __host__ __device__ __forceinline__
@@ -171,13 +175,18 @@ SDFV_PROG_FN void step(Machine& s, const sdfv_prog_op& o, uint32_t pc) {
 }
 
 // The whole program at one point: the result's distance and material index.
-SDFV_PROG_FN Value run(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, float px, float py, float pz) {
-    Machine s;
+// The machine before the first instruction, at the point (px, py, pz).
+SDFV_PROG_FN void start(Machine& s, float px, float py, float pz) {
     s.x = px; s.y = py; s.z = pz;
     s.f0x = s.f0y = s.f0z = s.f1x = s.f1y = s.f1z = s.f2x = s.f2y = s.f2z = s.f3x = s.f3y = s.f3z = 0.0f;
     s.v0.d = s.v1.d = s.v2.d = s.v3.d = s.v4.d = s.v5.d = s.v6.d = s.v7.d = 0.0f;
     s.v0.m = s.v1.m = s.v2.m = s.v3.m = s.v4.m = s.v5.m = s.v6.m = s.v7.m = kNoMaterial;
     s.cur = kNoMaterial;
+}
+
+SDFV_PROG_FN Value run(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, float px, float py, float pz) {
+    Machine s;
+    start(s, px, py, pz);
     // One instruction ahead: the scalar load of instruction pc + 1 is issued before instruction pc runs, so its latency hides
     // behind that instruction's vector work instead of standing between every two instructions.
     sdfv_prog_op cur = ops[0];
@@ -188,6 +197,16 @@ SDFV_PROG_FN Value run(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, flo
     }
     return s.v0;
 }
+
+// An EVALUATOR is what the shared kernel text (the fill's and the sampler's evaluators of program_device.h, march_pixel_program
+// of program_march.h) asks for a program's value at a point: `Value operator()(float, float, float) const`.  This one is the
+// interpreter -- the evaluator of every kernel built into the library.  A program compiled at run time (program_compile.hip)
+// brings one of its own: the same step() per instruction, with the instruction a compile-time constant.
+struct Interpreter {
+    const sdfv_prog_op* ops;
+    uint32_t n_ops;
+    SDFV_PROG_FN Value operator()(float px, float py, float pz) const { return run(ops, n_ops, px, py, pz); }
+};
 
 }  // namespace prog
 }  // namespace sdfv

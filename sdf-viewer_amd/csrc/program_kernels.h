@@ -3,8 +3,15 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#if !defined(__HIPCC_RTC__)
+#include <atomic>
+#endif
 
+#if defined(__HIPCC_RTC__)  // the run-time compiler is handed the headers by name (program_compile.hip)
+#include "sdfgrid.h"
+#else
 #include "../../include/sdfgrid.h"
+#endif
 
 namespace sdfv {
 
@@ -27,8 +34,33 @@ struct ProgramFillArgs {
     uint32_t nontemporal;     // texture stores pass L2 by (picks the _nt kernels)
 };
 
-hipError_t launch_program_fill(const ProgramFillArgs& a, hipStream_t stream);
+// The kernels a program is evaluated by on the routes sdfv_program_compile covers, in the order a compiled handle keeps its
+// specialised ones (program_compile.hip holds their names in this order).
+enum ProgramKernel {
+    kKernelFillTx64, kKernelFillTx64Nt, kKernelFillTx128, kKernelFillTx128Nt, kKernelFillTx256, kKernelFillTx256Nt,
+    kKernelPoints, kKernelPointsStaged, kKernelMarch, kKernelMarchAux, kProgramKernels
+};
+
+#if !defined(__HIPCC_RTC__)
+// What a compiled handle gives a launcher for the current device: its specialised kernels (nullptr where the route was not
+// compiled) and the counter of their launches.  A launcher given none launches the interpreter's kernel; the checks and the
+// launch geometry are computed before that choice, so the two cannot accept different calls.
+struct ProgramKernels {
+    const hipFunction_t* fn = nullptr;  // kProgramKernels entries, or nullptr: a plain handle, or a route that interprets
+    std::atomic<uint64_t>* launches = nullptr;  // sdfv_compiled_info::launches of that handle
+    // kernel `which` over `args` (one address per kernel argument) if it is there; *mine says whether it was
+    hipError_t launch(ProgramKernel which, dim3 grid, dim3 block, void** args, hipStream_t stream, bool* mine) const {
+        *mine = fn && fn[which];
+        if (!*mine) return hipSuccess;
+        const hipError_t e = hipModuleLaunchKernel(fn[which], grid.x, grid.y, grid.z, block.x, block.y, block.z, 0, stream, args, nullptr);
+        if (e == hipSuccess) launches->fetch_add(1, std::memory_order_relaxed);
+        return e;
+    }
+};
+
+hipError_t launch_program_fill(const ProgramFillArgs& a, const ProgramKernels& k, hipStream_t stream);
 hipError_t launch_program_sample_points(const sdfv_prog_op* ops, uint32_t n_ops, const float* points, size_t n,
-                                        bool distance_only, sdfv_sample* out, hipStream_t stream);
+                                        bool distance_only, sdfv_sample* out, const ProgramKernels& k, hipStream_t stream);
+#endif
 
 }  // namespace sdfv

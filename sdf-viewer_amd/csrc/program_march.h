@@ -46,8 +46,9 @@ SDFV_MARCH_FN bool wave_any(bool b) { return b; }
 // (it takes part in nothing and its outputs are not stored).  lut: the sRGB table (LDS on the device).  rgba: outColor; aux:
 // everything main() knows before shading, aux.depth = gl_FragDepth (1.0 without a hit).
 // status: 1 hit | 0 the pixel is off the box | -1 out of steps | -2 out of bounds | -3 a hit behind the origin (dropped).
-template <typename Lut>
-SDFV_MARCH_FN void march_pixel_program(const Frame& f, const sdfv_camera& cam, uint32_t px, uint32_t py, bool in_image,
+// eval: the program's evaluator (program_eval.h) -- it gives the march step, the hit sample and the four taps.
+template <typename Eval, typename Lut>
+SDFV_MARCH_FN void march_pixel_program(const Frame& f, const Eval& eval, const sdfv_camera& cam, uint32_t px, uint32_t py, bool in_image,
                                        const Lut& lut, float4& rgba, sdfv_march_aux& aux) {
     const sdfv_render_params& rp = f.rp;
     rgba = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -77,7 +78,7 @@ SDFV_MARCH_FN void march_pixel_program(const Frame& f, const sdfv_camera& cam, u
                 status = -2;
                 marching = false;
             } else {
-                v = prog::run(f.ops, f.n_ops, ray_pos.x, ray_pos.y, ray_pos.z);
+                v = eval(ray_pos.x, ray_pos.y, ray_pos.z);
                 ++steps;
                 if (v.d < 1e-5f) {
                     status = 1;
@@ -107,13 +108,20 @@ SDFV_MARCH_FN void march_pixel_program(const Frame& f, const sdfv_camera& cam, u
 #endif
         for (int t = 0; t < 4; ++t) {  // (one copy of the interpreter for the four)
             const V3 k = tap_sign(t);
-            const float d = prog::run(f.ops, f.n_ops, ray_pos.x + k.x * h, ray_pos.y + k.y * h, ray_pos.z + k.z * h).d;
+            const float d = eval(ray_pos.x + k.x * h, ray_pos.y + k.y * h, ray_pos.z + k.z * h).d;
             acc = t == 0 ? mk(k.x * d, k.y * d, k.z * d) : mk(acc.x + k.x * d, acc.y + k.y * d, acc.z + k.z * d);
         }
         const V3 n = normalize(acc);
         rgba = shade(rp, raw0, raw1);
         aux_set_hit(aux, raw0, raw1, n, frag_depth_of(cam.bvp, ray_pos.x, ray_pos.y, ray_pos.z));
     }
+}
+
+// ... with the interpreter over f.ops as the evaluator (the kernels of the library, the host mirror)
+template <typename Lut>
+SDFV_MARCH_FN void march_pixel_program(const Frame& f, const sdfv_camera& cam, uint32_t px, uint32_t py, bool in_image,
+                                       const Lut& lut, float4& rgba, sdfv_march_aux& aux) {
+    march_pixel_program(f, prog::Interpreter{f.ops, f.n_ops}, cam, px, py, in_image, lut, rgba, aux);
 }
 
 }  // namespace pmarch

@@ -21,6 +21,9 @@ struct ProgramMarchArgs {
     sdfv_camera cameras[kProgramMarchCameras];
 };
 
-hipError_t launch_program_march(const ProgramMarchArgs& a, hipStream_t stream);
+#if !defined(__HIPCC_RTC__)
+struct ProgramKernels;  // program_kernels.h
+hipError_t launch_program_march(const ProgramMarchArgs& a, const ProgramKernels& k, hipStream_t stream);
+#endif
 
 }  // namespace sdfv

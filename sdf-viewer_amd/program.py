@@ -32,6 +32,8 @@ from ._capi import ProgOp, SdfvError, check, lib
 
 
 PARAM_VALUE, PARAM_NEGATED, PARAM_RECIPROCAL = 0, 1, 2
+# the routes CompiledProgram.compile() specialises (SDFV_COMPILE_*)
+FILL, POINTS, MARCH = _capi.COMPILE_FILL, _capi.COMPILE_POINTS, _capi.COMPILE_MARCH
 PARAM_MAX_TARGETS = 4
 
 
@@ -340,6 +342,37 @@ class CompiledProgram:
         s._bb = tuple(bb)
         s._keep.append(self)
         return s
+
+    def compile(self, routes=FILL | POINTS | MARCH, arch=None):
+        """sdfv_program_compile: a NEW handle whose `routes` (FILL | POINTS | MARCH) launch kernels compiled for this very
+        program at run time; everything else about it is this handle's.  arch: None = the current device's, or a name such as
+        "gfx950" (needs no device).  Takes of the order of a second per route: for a model that is filled or rendered many
+        times, not for an editor's snapshots."""
+        h = C.c_void_p()
+        check(lib.sdfv_program_compile(self.h, int(routes), None if arch is None else str(arch).encode(), C.byref(h)))
+        new = CompiledProgram.__new__(CompiledProgram)
+        new.h, new._surface, new._owner = h, None, None
+        return new
+
+    def compiled_info(self):
+        """sdfv_program_compiled_info as a dict: routes (0 for a plain handle), arch, compile_seconds, code_bytes, launches."""
+        info = _capi.CompiledInfo()
+        info.size = C.sizeof(info)
+        check(lib.sdfv_program_compiled_info(self.h, C.byref(info)))
+        return dict(routes=int(info.routes), arch=info.arch.decode(), compile_seconds=float(info.compile_seconds),
+                    code_bytes=int(info.code_bytes), launches=int(info.launches))
+
+    def compiled_code(self):
+        """The code object of a compiled handle (bytes: an ELF for its architecture)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        check(lib.sdfv_program_compiled_code(self.h, C.byref(p), C.byref(n), None))
+        return C.string_at(p.value, n.value)
+
+    def compiled_source(self):
+        """The translation unit sdfv_program_compile generated for this handle (str)."""
+        src = C.c_char_p()
+        check(lib.sdfv_program_compiled_code(self.h, None, None, C.byref(src)))
+        return src.value.decode()
 
     def close(self):
         if self.h and self._owner is None:
