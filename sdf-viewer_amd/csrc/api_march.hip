@@ -4,7 +4,7 @@
 #include <cstring>
 
 #include "api_internal.h"
-#include "march_common.h"
+#include "march_plan.h"
 #include "raymarch_kernels.h"
 
 using namespace sdfv;
@@ -103,46 +103,6 @@ int check_lights(const sdfv_render_params* rp) {
 
 namespace {
 
-// Everything RaymarchArgs derives from the render parameters alone (exactness flags, tap sizes, cull sphere).
-void derive_raymarch_args(const sdfv_render_params* rp, sdfv::RaymarchArgs& a) {
-    memset(&a, 0, sizeof(a));
-    a.rp = *rp;
-    const uint32_t off = g_options.raymarch_disable;
-    a.pow2_extent = (off & SDFV_RM_NO_POW2_EXTENT) ? 0u : 1u;
-    a.fast_index = (off & SDFV_RM_NO_FAST_INDEX) ? 0u : 1u;
-    a.pow2_size = 1;
-    a.symmetric_box = 1;
-    a.fast_normal = 1;
-    float radius2 = 0.0f;
-    // sdfNormal's tap offset as the kernels take it (march_common.h): ((sx^2 + sy^2) + sz^2), the order of the loop that stood
-    // here -- whose leading 0 + sx^2 was exact -- and unchecked, so that fast_normal is what it was for every input
-    const float h_world = sdfv::march::tap_distance((float)rp->tex_size[0], (float)rp->tex_size[1], (float)rp->tex_size[2],
-                                                    rp->lod_dist_between_samples);
-    for (int i = 0; i < 3; ++i) {
-        a.bsize[i] = rp->bounds_max[i] - rp->bounds_min[i];
-        a.inv_bsize[i] = 1.0f / a.bsize[i];
-        const float n = (float)rp->tex_size[i];
-        // a marching ray stays within 1e-4 of the box (material.frag:106): floor(u) in [-1, N-1] needs
-        // 1e-4 * N / size well below 0.5; the normal's taps sit h_world further out
-        if (!(a.bsize[i] > 0.0f) || !(1e-4f * n / a.bsize[i] <= 0.25f)) a.fast_index = 0;
-        if (!(a.bsize[i] > 0.0f) || !((1e-4f + h_world) * n / a.bsize[i] <= 0.45f)) a.fast_normal = 0;
-        int e = 0;
-        // x / 2^k == x * 2^-k exactly (both correctly rounded), provided 2^-k is itself normal
-        if (!(a.bsize[i] > 0.0f) || frexpf(a.bsize[i], &e) != 0.5f || e < -100 || e > 100) a.pow2_extent = 0;
-        if (rp->tex_size[i] >= (1u << 24)) a.pow2_size = 0;  // (N as a float is exact below 2^24)
-        if (rp->bounds_min[i] != -rp->bounds_max[i]) a.symmetric_box = 0;
-        a.cull_center[i] = 0.5f * (rp->bounds_min[i] + rp->bounds_max[i]);
-        radius2 += 0.25f * a.bsize[i] * a.bsize[i];
-    }
-    a.cull_radius2 = radius2 * 1.0201f + 1e-12f;  // (1.01 r)^2
-    if (!(a.cull_radius2 > 0.0f) || !std::isfinite(a.cull_radius2)) a.cull_radius2 = INFINITY;  // never cull
-    a.asm_loop = (off & SDFV_RM_NO_ASM_LOOP) ? 0u : 1u;
-    a.no_interior_fetch = (off & SDFV_RM_NO_INTERIOR_FETCH) ? 1u : 0u;
-    a.cube_box = (a.symmetric_box && rp->bounds_max[0] == rp->bounds_max[1] && rp->bounds_max[1] == rp->bounds_max[2]) ? 1u : 0u;
-    if (off & SDFV_RM_NO_SYMMETRIC) a.symmetric_box = 0;
-    if (off & SDFV_RM_NO_POW2_SIZE) a.pow2_size = 0;
-}
-
 // What every march launch is told besides the render parameters: the two textures and the rows of the image.
 void set_march_frame(sdfv::RaymarchArgs& a, const float* tex0, const float* tex1, uint32_t width, uint32_t height, uint32_t y0, uint32_t y1) {
     a.tex0 = reinterpret_cast<const float4*>(tex0);
@@ -153,23 +113,20 @@ void set_march_frame(sdfv::RaymarchArgs& a, const float* tex0, const float* tex1
     a.y1 = y1;
 }
 
-// Rows [y0, y1) of the image (band_step 1), or the 16-row bands y0 / 16, y0 / 16 + band_step, ... below y1 == height.
-int raymarch_rows(const sdfv_march_desc& d, uint32_t y0, uint32_t y1, uint32_t band_step, uint32_t band_height, void* stream) {
+// The argument checks of a march call, then the device.
+int check_march_call(const sdfv_march_desc& d, uint32_t y0, uint32_t y1, uint32_t lod_filter) {
     const sdfv_render_params* rp = d.rp;
-    const uint32_t n_cameras = d.n_cameras, width = d.width, height = d.height;
-    const sdfv_camera* cameras = d.cameras;
     if (!rp || !d.tex0 || !d.tex1) return set_error(SDFV_ERR_INVALID_ARGUMENT, "NULL argument");
     if (!d.rgba && !d.rgba8) return set_error(SDFV_ERR_INVALID_ARGUMENT, "no colour output: rgba and rgba8 are both NULL");
     if (int rc = check_lights(rp)) return rc;
     if (int rc = check_texel_alignment(d.tex0, d.tex1, d.rgba)) return rc;
     if (int rc = check_word_aligned("dist, depth, aux and rgba8", d.dist, d.depth, d.aux, d.rgba8)) return rc;
     if (((uintptr_t)d.pairs | (uintptr_t)d.ilv) & 7) return set_error(SDFV_ERR_INVALID_ARGUMENT, "pairs and ilv must be 8-byte aligned");
-    if (n_cameras && !cameras) return set_error(SDFV_ERR_INVALID_ARGUMENT, "cameras is NULL");
-    if (y0 > y1 || y1 > height) return set_error(SDFV_ERR_INVALID_ARGUMENT, "rows [%u,%u) outside height %u", y0, y1, height);
+    if (d.n_cameras && !d.cameras) return set_error(SDFV_ERR_INVALID_ARGUMENT, "cameras is NULL");
+    if (y0 > y1 || y1 > d.height) return set_error(SDFV_ERR_INVALID_ARGUMENT, "rows [%u,%u) outside height %u", y0, y1, d.height);
     if (rp->tex_size[0] == 0 || rp->tex_size[1] == 0 || rp->tex_size[2] == 0)
         return set_error(SDFV_ERR_INVALID_ARGUMENT, "empty texture");
     if (!(rp->lod_dist_between_samples >= 1.0f)) return set_error(SDFV_ERR_INVALID_ARGUMENT, "lod_dist_between_samples < 1");
-    const uint32_t lod_filter = g_options.raymarch_lod_filter;
     if (lod_filter == 1 && rp->lod_dist_between_samples != 1.0f) {  // the lattice filter: L a power of two (what LoadingManager publishes)
         int e = 0;
         const float lod = rp->lod_dist_between_samples;
@@ -179,74 +136,67 @@ int raymarch_rows(const sdfv_march_desc& d, uint32_t y0, uint32_t y1, uint32_t b
     }
     if ((uint64_t)rp->tex_size[0] * rp->tex_size[1] * rp->tex_size[2] >= (1ull << 32))
         return set_error(SDFV_ERR_INVALID_ARGUMENT, "texture too large for 32-bit texel indexing");
-    if (int rc = need_device()) return rc;
-    sdfv::RaymarchArgs a;
-    derive_raymarch_args(rp, a);
+    return need_device();
+}
+
+// What the device and the calling thread's options contribute to a launch (march_plan.h: apply_march_policy).
+sdfv::MarchPolicy march_policy() {
+    const DeviceFacts& dev = device_facts();
+    return {dev.gfx950, dev.cus, dev.xcds, dev.last_level_cache_bytes, g_options.raymarch_tile_group, g_options.raymarch_waves_per_simd,
+            g_options.raymarch_box_first};
+}
+
+// Everything the launches of a call are told, cameras and output planes apart: rows [y0, y1) of the image (band_step 1), or the
+// bands of band_height rows y0 / band_height, y0 / band_height + band_step, ... below y1 == height.
+void fill_march_args(const sdfv_march_desc& d, uint32_t y0, uint32_t y1, uint32_t band_step, uint32_t band_height, sdfv::RaymarchArgs& a) {
+    derive_raymarch_args(d.rp, g_options.raymarch_disable, a);
     a.dist = d.dist;
     a.pairs = d.pairs;
     a.ilv = d.ilv;
-    set_march_frame(a, d.tex0, d.tex1, width, height, y0, y1);
+    set_march_frame(a, d.tex0, d.tex1, d.width, d.height, y0, y1);
     a.band_skip = band_height * (band_step - 1u);
     a.band_shift = band_height == 8u ? 3u : 4u;
-    a.rows_out = band_step > 1 ? sdfv_band_rows_ex(height, y0 / band_height, band_step, band_height) : y1 - y0;
+    a.rows_out = band_step > 1 ? sdfv_band_rows_ex(d.height, y0 / band_height, band_step, band_height) : y1 - y0;
     // sdfNormal's result only feeds calculate_lighting (material.frag:155,163), and the one AmbientLight the scene
     // configures (scene/mod.rs:106-112) does not read it: dead code a GLSL compiler removes.  It is evaluated when the
     // aux record asks for it; SDFV_OPT_RAYMARCH_KEEP_NORMAL evaluates it per hit regardless (what it would cost once a
     // directional light uses it).
     a.compute_normal = g_options.raymarch_keep_normal ? 1u : 0u;
-    // tile order: auto = for a single frame the launcher's XCD-aware choice (groups of 2 x 2 tiles, those under the projected
-    // bounding box first; profiles/r02/box_first_*.json, EXPERIMENTS R2-R3), launch order for batches of cameras, which
-    // lose 3-8 % with any grouping
-    // w waves per SIMD = w workgroups per CU: each asks for a w-th of the CU's 160 KB of LDS (less a little for rounding)
-    const uint32_t w = g_options.raymarch_waves_per_simd;
-    a.waves_per_simd = w;  // 0 = the launcher's occupancy rule (launch_raymarch), 7 = never cap, 2..6 = that cap
-    a.box_first = g_options.raymarch_box_first;
-    // The device's facts gate what is machine- or topology-specific: the hand-written loop is gfx950 code (anything else
-    // takes the compiler's loop, bit-identical), and the XCD-aware tile orders assume the observed workgroup -> XCD
-    // placement L % 8 of an eight-XCD part (speed only; launch order elsewhere).
-    const DeviceFacts& dev = device_facts();
-    if (!dev.gfx950) a.asm_loop = 0;
-    a.wave_slots_per_simd_unit = dev.cus * 4u;  // SIMDs: resident waves at w per SIMD = w * this
-    a.last_level_cache_bytes = dev.last_level_cache_bytes;
-    const bool xcd_order_ok = dev.xcds == 8;
-    a.group_shift = g_options.raymarch_tile_group == 0 ? (n_cameras == 1 && xcd_order_ok ? sdfv::kGroupAuto : 0u)
-                                                       : (g_options.raymarch_tile_group == 1 ? 0u : g_options.raymarch_tile_group - 1u);
-    // launches that keep launch order (batches, tile bands): tile columns rotated by row and camera, so that the XCDs' static
-    // shares balance (auto only: SDFV_OPT_RAYMARCH_TILE_GROUP 1 is the plain launch order, for A/B runs)
-    a.rotate_columns = g_options.raymarch_tile_group == 0 && xcd_order_ok ? 1u : 0u;
+    apply_march_policy(a, march_policy(), d.n_cameras);
 #ifdef SDFV_TUNING
     a.wave_timing = reinterpret_cast<unsigned long long*>(g_options.wave_timing);  // 32 B per wave, or 0
     a.priority_map = reinterpret_cast<const unsigned char*>(g_options.priority_map);
-    a.tile_order = n_cameras == 1 ? reinterpret_cast<const uint32_t*>(g_options.tile_order) : nullptr;
+    a.tile_order = d.n_cameras == 1 ? reinterpret_cast<const uint32_t*>(g_options.tile_order) : nullptr;
 #endif
-    const uint64_t pixels_per_cam = (uint64_t)a.rows_out * width;
-    hipStream_t main = (hipStream_t)stream;
-    // Cameras.  Up to kInlineCameras ride in the kernel-argument block.  A larger batch is read from device memory, so that
-    // kMaxCamerasPerLaunch of them still make ONE launch: the caller's own array if that is where it lies, else a slot of the
-    // camera ring per launch (CameraRing).  While the stream is being captured (the ring's events do not belong in somebody's
-    // graph), with the option off, or if the ring cannot be had, the batch goes out as launches of kInlineCameras instead
-    // (same pixels).
-    const sdfv_camera* device_cameras = nullptr;
-    bool ring = false;
+}
+
+// Where the launches of a call read their cameras (march_plan.h: camera_source).  kStaged means a slot of the camera ring per
+// launch (CameraRing); if the ring cannot be had the batch goes out as launches of kInlineCameras instead (same pixels).
+sdfv::CameraSource cameras_of_call(const sdfv_camera* cameras, uint32_t n_cameras, hipStream_t main) {
     // (asked for ANY count -- ADVICE r04: a device array of <= kInlineCameras cameras, e.g. a rank's share of a resident batch,
     // used to be memcpy'd from on the host; the kernel reads camera_list for any count)
     hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, cameras) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged)) {
-        device_cameras = cameras;
-    } else {
+    const bool on_device = hipPointerGetAttributes(&attr, cameras) == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (!on_device) {
         (void)hipGetLastError();
-        if (n_cameras > sdfv::kInlineCameras) {
-            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(main, &capturing) != hipSuccess) (void)hipGetLastError();
-            ring = capturing == hipStreamCaptureStatusNone && g_options.raymarch_camera_staging &&
-                   g_camera_ring.ensure(current_device()) == hipSuccess;
-        }
+        if (n_cameras > sdfv::kInlineCameras && hipStreamIsCapturing(main, &capturing) != hipSuccess) (void)hipGetLastError();
     }
-    const uint32_t per_launch = device_cameras || ring ? sdfv::kMaxCamerasPerLaunch : sdfv::kInlineCameras;
-    // several launches, each small (tools/split_balance.py: a launch of 17 000 workgroups gains 34 % from overlapping with its
-    // siblings, one of 35 000 11 %, one of 65 000 nothing, one of 130 000 loses 4 %): side streams, see BatchStreams
-    const uint64_t groups_per_launch = (uint64_t)((width + 15) / 16) * ((a.rows_out + 15) / 16) * per_launch;
-    const bool overlap = n_cameras > per_launch && groups_per_launch <= 40000 && g_options.raymarch_batch_streams;
+    sdfv::CameraSource src = sdfv::camera_source(n_cameras, on_device, capturing != hipStreamCaptureStatusNone, g_options.raymarch_camera_staging != 0);
+    if (src == sdfv::CameraSource::kStaged && g_camera_ring.ensure(current_device()) != hipSuccess) src = sdfv::CameraSource::kInline;
+    return src;
+}
+
+// The launches of one call: kMaxCamerasPerLaunch or kInlineCameras cameras each, small ones overlapping on side streams.
+int launch_march_batch(const sdfv_march_desc& d, sdfv::RaymarchArgs& a, uint32_t lod_filter, hipStream_t main) {
+    const uint32_t n_cameras = d.n_cameras;
+    const sdfv_camera* cameras = d.cameras;
+    const uint64_t pixels_per_cam = (uint64_t)a.rows_out * d.width;
+    const sdfv::CameraSource source = cameras_of_call(cameras, n_cameras, main);
+    const bool ring = source == sdfv::CameraSource::kStaged;
+    const uint32_t per_launch = sdfv::cameras_per_launch(source);
+    const uint64_t groups_per_launch = (uint64_t)((d.width + 15) / 16) * ((a.rows_out + 15) / 16) * per_launch;
+    const bool overlap = sdfv::launches_overlap(n_cameras, per_launch, groups_per_launch) && g_options.raymarch_batch_streams;  // see BatchStreams
     uint32_t used = 0;  // side streams that carry a launch of this call
     int rc = SDFV_OK;
     auto hip_ok = [&](hipError_t e, const char* what) {
@@ -258,7 +208,7 @@ int raymarch_rows(const sdfv_march_desc& d, uint32_t y0, uint32_t y1, uint32_t b
     for (uint32_t c0 = 0; c0 < n_cameras && rc == SDFV_OK; c0 += per_launch, ++launch) {
         const uint32_t nc = n_cameras - c0 < per_launch ? n_cameras - c0 : per_launch;
         a.n_cameras = nc;
-        if (device_cameras) a.camera_list = device_cameras + c0;
+        if (source == sdfv::CameraSource::kInPlace) a.camera_list = cameras + c0;
         else if (!ring) memcpy(a.cameras, cameras + c0, nc * sizeof(sdfv_camera));
         point_outputs_at(a, pixels_per_cam, c0, d.rgba, d.rgba8, d.aux, d.depth);
         hipStream_t on = main;
@@ -289,6 +239,15 @@ int raymarch_rows(const sdfv_march_desc& d, uint32_t y0, uint32_t y1, uint32_t b
     return rc;
 }
 
+// Rows [y0, y1) of the image (band_step 1), or the 16-row bands y0 / 16, y0 / 16 + band_step, ... below y1 == height.
+int raymarch_rows(const sdfv_march_desc& d, uint32_t y0, uint32_t y1, uint32_t band_step, uint32_t band_height, void* stream) {
+    const uint32_t lod_filter = g_options.raymarch_lod_filter;
+    if (int rc = check_march_call(d, y0, y1, lod_filter)) return rc;
+    sdfv::RaymarchArgs a;
+    fill_march_args(d, y0, y1, band_step, band_height, a);
+    return launch_march_batch(d, a, lod_filter, (hipStream_t)stream);
+}
+
 // Argument checks and RaymarchArgs / SlabMarchArgs shared by the two forms of a round of the sharded march.
 int slab_round_args(const sdfv_render_params* rp, const sdfv_grid* slab, uint32_t ghost_lo, uint32_t ghost_hi,
                            const float* tex0, const float* tex1, const sdfv_camera* camera, uint32_t width, uint32_t height,
@@ -313,7 +272,7 @@ int slab_round_args(const sdfv_render_params* rp, const sdfv_grid* slab, uint32_
     const uint64_t resident = (uint64_t)slab->dims[0] * slab->dims[1] * (ghost_lo + (slab->z_end - slab->z_begin) + ghost_hi);
     if (resident >= (1ull << 32)) return set_error(SDFV_ERR_INVALID_ARGUMENT, "slab too large for 32-bit texel indexing");
     if (int rc = need_device()) return rc;
-    derive_raymarch_args(rp, a);
+    derive_raymarch_args(rp, g_options.raymarch_disable, a);
     if (!a.fast_index)
         return set_error(SDFV_ERR_INVALID_ARGUMENT, "box too small for the sharded march: 1e-4 * N / size must be <= 0.25");
     set_march_frame(a, tex0, tex1, width, height, 0, height);
@@ -336,24 +295,6 @@ int slab_round_args(const sdfv_render_params* rp, const sdfv_grid* slab, uint32_
 #pragma GCC visibility push(default)
 extern "C" {
 
-void sdfv_render_params_default(sdfv_render_params* rp, const sdfv_grid* grid) {
-    if (!rp) return;
-    memset(rp, 0, sizeof(*rp));
-    for (int i = 0; i < 3; ++i) {
-        if (grid) {
-            rp->bounds_min[i] = grid->bb_min[i];
-            rp->bounds_max[i] = grid->bb_max[i];
-            rp->tex_size[i] = grid->dims[i];
-        }
-        rp->ambient[i] = 1.0f;  // AmbientLight::new(&ctx, 1.0, Srgba::WHITE), scene/mod.rs:106
-    }
-    rp->lod_dist_between_samples = 1.0f;  // material.rs:28
-    rp->tint[0] = rp->tint[1] = rp->tint[2] = rp->tint[3] = 1.0f;  // Srgba::WHITE, material.rs:29
-    rp->gamma = 0.0f;
-    rp->tone_mapping = 2;   // three-d 0.18 default (ACES)
-    rp->color_mapping = 1;  // three-d 0.18 default (compute to sRGB)
-}
-
 int sdfv_march_volume_advice(const sdfv_grid* grid, uint32_t* kind) {
     if (int rc = check_grid(grid)) return rc;
     if (!kind) return set_error(SDFV_ERR_INVALID_ARGUMENT, "kind is NULL");
@@ -365,9 +306,8 @@ int sdfv_march_volume_advice(const sdfv_grid* grid, uint32_t* kind) {
     sdfv_render_params rp;
     sdfv_render_params_default(&rp, grid);
     sdfv::RaymarchArgs a;
-    derive_raymarch_args(&rp, a);
-    if (!device_facts().gfx950) a.asm_loop = 0;
-    a.last_level_cache_bytes = device_facts().last_level_cache_bytes;
+    derive_raymarch_args(&rp, g_options.raymarch_disable, a);
+    apply_march_policy(a, march_policy(), 1);
     // the launcher's own choice with all three volumes at hand (a grid that is not cubic marches fastest over its distance volume)
     const int mode = sdfv::march_volume_choice(a, true, true, true);
     *kind = mode == sdfv::kMarchIlv ? SDFV_MARCH_VOLUME_INTERLEAVED : mode == sdfv::kMarchPairs ? SDFV_MARCH_VOLUME_PAIRS : SDFV_MARCH_VOLUME_NONE;

@@ -459,7 +459,7 @@ __global__ __launch_bounds__(kBlock) void commit_distance_kernel(const float4* _
         dist[i] = load_once(tex0 + i).x;
 }
 
-// The y-pair volume the hand-written march loop gathers from (raymarch_kernels.hip SDFV_MARCH_ASM_INTERIOR_PAIRS): texel
+// The y-pair volume the hand-written march loop gathers from (march_asm_loop.h SDFV_MARCH_ASM_INTERIOR_PAIRS): texel
 // (x, y, z) = (d[z][y][x], d[z][min(y + 1, H - 1)][x]).  Reads the compact distance volume twice (the second time one row
 // on: served by the caches), writes 8 B/voxel; once per load, pays for itself from the second frame on.
 // Launched over (x chunks, y, z): no index division; the stores stream past L2 (nt), the reads keep it.
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(kBlock) void commit_pairs_kernel(const float* __res
     __builtin_nontemporal_store(v, reinterpret_cast<v2f*>(pairs) + i);
 }
 
-// The y-interleaved volume (raymarch_kernels.hip SDFV_MARCH_ASM_INTERIOR_ILV): rows 2p and 2p + 1 of a slice stored as one
+// The y-interleaved volume (march_asm_loop.h SDFV_MARCH_ASM_INTERIOR_ILV): rows 2p and 2p + 1 of a slice stored as one
 // row of (d[2p][x], d[2p+1][x]) pairs; 4 B/voxel, H even.  One thread per PAIR: two coalesced 4-byte reads, one 8-byte store.
 // (Flat index, cached accesses: the (x, p, z) launch with streamed stores that serves commit_pairs_kernel is 10 % slower here.)
 __global__ __launch_bounds__(kBlock) void commit_interleaved_kernel(const float* __restrict__ dist, float2* __restrict__ ilv,

@@ -1,4 +1,4 @@
-// raymarch_kernels.h -- launch interface of the sphere-tracing kernel (see raymarch_kernels.hip).
+// raymarch_kernels.h -- launch interface of the sphere-tracing kernels (raymarch_kernels.hip, raymarch_slab_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -102,12 +102,8 @@ struct SlabMarchArgs {
 hipError_t launch_raymarch_slab(const RaymarchArgs& a, const SlabMarchArgs& s, hipStream_t stream);
 
 // lod_filter: SDFV_OPT_RAYMARCH_LOD_FILTER as the caller's thread has it; read only when rp.lod_dist_between_samples != 1 (then
-// the caller has checked that the lod is a power of two in [2, 2^15]).
+// the caller has checked that the lod is a power of two in [2, 2^15]).  The plan of march_plan.h, then the kernel it names.
 hipError_t launch_raymarch(const RaymarchArgs& a, hipStream_t stream, uint32_t lod_filter);
-// would the launcher march over a pair (kind kMarchPairs) / y-interleaved (kind kMarchIlv) volume for these arguments, pointers apart?
-bool march_volume_applicable(const RaymarchArgs& a, int kind);
-// the launcher's choice among the volumes taken as present: kMarchIlv, kMarchPairs, or 0 = neither (dist / tex0.r is marched)
-int march_volume_choice(const RaymarchArgs& a, bool have_dist, bool have_pairs, bool have_ilv);
 // n cameras from a HOST array into DEVICE memory, stream-ordered, without a copy engine: launches that carry 32 cameras each
 // in their kernel arguments (the host array is free again on return)
 hipError_t launch_store_cameras(const sdfv_camera* host, uint32_t n, sdfv_camera* device, hipStream_t stream);

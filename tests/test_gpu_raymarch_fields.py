@@ -179,7 +179,7 @@ def test_row_ranges_and_camera_batches_over_steep(pkg):
 def test_sharded_march_equals_single_gpu_march_over_fields(pkg, par, field, grid):
     """parallel.ShardedMarch, z-sharded over 3 "ranks" in lockstep on the one GPU: the merged image and every aux word
     test_gpu_sharded_march.py compares equal the single-GPU march's.  Normals: the slab kernel computes them only where the
-    launcher's rule allows the clamping fetch for the taps, (1e-4 + h) * N / size <= 0.45 on every axis (api_march.hip: derive_raymarch_args); over
+    launcher's rule allows the clamping fetch for the taps, (1e-4 + h) * N / size <= 0.45 on every axis (march_plan.cpp: derive_raymarch_args); over
     odd20x34x27 the y axis gives 0.474, so there every normal stays zero -- asserted, so that a change of the rule shows."""
     from test_gpu_sharded_march import run_lockstep
     world = 3
