@@ -1,8 +1,9 @@
 """CPU tests of sdfv_program_compile (include/sdfgrid.h, "SDF programs compiled to kernels of their own"): the interface is
 declared, exported and bound; a program compiles for gfx950 with no device; the code object holds exactly the kernels of the
 routes asked for, within the registers the interpreter's kernels are held to; the generated source states operands as bit
-patterns; every promised error; the run-time compiler library is loaded on the first compile only; the host mirror does not
-care whether a handle is compiled.  What the specialised kernels COMPUTE is tests/test_gpu_program_compile.py's."""
+patterns; the same program gives the same code object, twice and from four threads at once; every promised error; the run-time
+compiler library is loaded on the first compile only; the host mirror does not care whether a handle is compiled.  What the
+specialised kernels COMPUTE is tests/test_gpu_program_compile*.py's."""
 import ctypes as C
 import importlib
 import os
@@ -10,12 +11,15 @@ import re
 import struct
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
 
+import program_compile_cases as CC
 import program_fuzz as Z
 import program_geometry as G
+import program_ref as R
 from kernel_objects import LLVM_TOOLS, have_llvm_tools, kernel_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -92,7 +96,10 @@ def test_compiles_for_gfx950_without_a_device(pkg, PM, tmp_path, name):
 
     As built: 37-45 VGPRs for every fill and sampler, 47-67 VGPRs and 46-54 SGPRs for the march kernels whatever the program
     (DESIGN.md 3.6.2 has the table and how the march's operands are kept from being hoisted out of its loops)."""
-    plain = builders(PM)[name].build()
+    every_route_compiles_within_the_interpreters_registers(PM, builders(PM)[name].build(), tmp_path, name)
+
+
+def every_route_compiles_within_the_interpreters_registers(PM, plain, tmp_path, name):
     for routes, want in ((PM.FILL, FILL_KERNELS), (PM.POINTS, POINTS_KERNELS), (PM.MARCH, MARCH_KERNELS),
                          (PM.FILL | PM.POINTS | PM.MARCH, FILL_KERNELS + POINTS_KERNELS + MARCH_KERNELS)):
         c = plain.compile(routes, arch="gfx950")
@@ -111,6 +118,52 @@ def test_compiles_for_gfx950_without_a_device(pkg, PM, tmp_path, name):
         ops_c, bb_c = c.ops()
         ops_p, bb_p = plain.ops()
         assert ops_c.tobytes() == ops_p.tobytes() and bb_c == bb_p    # the same instructions and box
+
+
+@pytest.mark.skipif(not have_llvm_tools(), reason="LLVM binary tools not installed")
+@pytest.mark.parametrize("name", ["tiny_k", "pow2_k", "identities", "subnormal_sizes"])
+def test_the_folding_programs_compile_for_every_route(pkg, PM, tmp_path, name):
+    """tests/program_compile_cases.py's programs of subnormal, zero, signed-zero and power-of-two operands: the same kernels
+    within the same resources as the programs above."""
+    every_route_compiles_within_the_interpreters_registers(PM, CC.folding_programs(PM)[name].build(), tmp_path, name)
+
+
+# ---- the same program, the same code object: twice, and from four threads at once ----
+THREAD_PROGRAMS = ("anchor", "all_ops", "late_material", "ties")
+
+
+def test_compiling_twice_gives_the_same_bytes(PM):
+    plain = R.catalogue(PM)["all_ops"].build()
+    first, second = (plain.compile(arch="gfx950").compiled_code() for _ in range(2))
+    assert first[:4] == b"\x7fELF" and first == second
+
+
+def test_four_threads_compile_what_a_serial_compile_gives(pkg, PM):
+    """Compilations are serialised inside the library (one run-time compiler, one mutex): four host threads that each compile a
+    program of their own twice, at the same time, get the code objects a serial compile of the same program gives, byte for
+    byte, and no error text."""
+    plains = {n: R.catalogue(PM)[n].build() for n in THREAD_PROGRAMS}
+    serial = {n: p.compile(PM.FILL, arch="gfx950").compiled_code() for n, p in plains.items()}
+    assert len(set(serial.values())) == len(serial)                  # four different code objects
+    got, errors = {}, []
+
+    def work(name):
+        try:
+            got[name] = [plains[name].compile(PM.FILL, arch="gfx950").compiled_code() for _ in range(2)]
+            got[name].append(pkg.lib.sdfv_last_error().decode())
+        except Exception as e:  # noqa: BLE001
+            errors.append((name, repr(e)))
+
+    threads = [threading.Thread(target=work, args=(n,), daemon=True) for n in THREAD_PROGRAMS]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(120.0)                                                # (eight compiles of about half a second each)
+    assert not any(t.is_alive() for t in threads), "a compiling thread did not come back"
+    assert not errors, errors
+    for name in THREAD_PROGRAMS:
+        a, b, error_text = got[name]
+        assert a == serial[name] and b == serial[name] and error_text == "", name
 
 
 # ---- the generated source ----
