@@ -585,7 +585,7 @@ int sdfv_mesh_extract(const sdfv_demo_params *params, uint32_t sdf_id, const flo
 int sdfv_mesh_free(sdfv_mesh *mesh);
 /* sdfv_mesh_extract keeps its scratch (about 13 bytes per lattice point, about 17 once dual contouring has run: its third
  * scan) for the calling thread's next extraction;
- * this releases it -- and the three side streams a batch of more than 64 cameras makes (SDFV_OPT_RAYMARCH_BATCH_STREAMS) and the
+ * this releases it -- and the second block sdfv_program_mesh_extract_sparse keeps beside it, the three side streams a batch of more than 64 cameras makes (SDFV_OPT_RAYMARCH_BATCH_STREAMS) and the
  * camera ring (SDFV_OPT_RAYMARCH_CAMERA_STAGING). */
 int sdfv_mesh_trim(void);
 
@@ -664,6 +664,71 @@ int sdfv_program_mesh_extract(const sdfv_program *p, const float bb_min[3], cons
 int sdfv_program_mesh_postproc(const sdfv_program *p, sdfv_vertex *vertices, size_t n, void *stream);
 /* host buffer, evaluated ON THE DEVICE, like the other *_host calls */
 int sdfv_program_mesh_postproc_host(const sdfv_program *p, sdfv_vertex *vertices_host, size_t n);
+
+/* ---- SDF programs: sparse meshing (marching cubes that samples only near the surface) ----
+ * sdfv_program_mesh_extract evaluates the program at all (cells + 1)^3 lattice points; the surface touches O(cells^2) of them.
+ * A signed distance says where the rest is: if |d(p) - d(q)| <= L * |p - q| for all p, q, a block of space whose centre has
+ * |d| > L * (half the block's diagonal) holds no zero of d and needs no samples.  Arithmetic as above: IEEE f32, every step
+ * rounded on its own, left to right as written, nothing contracted.  N = cells, size = bb_max - bb_min, a leaf block is 4 cells.
+ *   lattice    sdfv_program_mesh_extract's: point i of an axis at u = (float)i / (float)N, p = u * size + min;
+ *              d(p) = sample(p, true).distance
+ *   blocks     a block has a side of s cells and an origin o whose components are multiples of s.  The list starts as the one
+ *              block s = N, o = 0, which is not tested.  While s > 4: s = s / 2; every block of the list is replaced, in list
+ *              order, by its eight children at offsets (0|s, 0|s, 0|s), x fastest; every child is tested, the survivors stay, in
+ *              that order.  The test of a block: d at its centre lattice point o + s / 2,
+ *                e_a = (float)s / (float)N * size_a
+ *                r   = 0.5f * sqrt((e_x*e_x + e_y*e_y) + e_z*e_z)
+ *                t   = (L * r) * 1.001f
+ *              kept iff !(|d| > t): a NaN distance keeps the block.  The BRICKS are the list at s = 4 (N = 4: the one block).
+ *              The factor 1.001 pays for the rounding of d and r: a leaf's r is at least two cells' worth of distance, against
+ *              which an f32 distance is off by parts in 10^7.
+ *   ownership  lattice point g belongs to the block with index min(g_a / 4, N / 4 - 1) per axis; an edge belongs to the block of
+ *              its lower end.  So a brick owns 4 points per axis, 5 where it is the box's last brick on that axis.
+ *   vertices   one per crossing edge (the ends differ in d < 0) whose owner is a brick: bricks in list order, within a brick its
+ *              owned points in local lattice order (x fastest), within a point its edges in axis order.  Position (t = d0 /
+ *              (d0 - d1), ...), normal = normal(p, None) and, with SDFV_MESH_WITH_MATERIALS, the material fields are
+ *              sdfv_program_mesh_extract's, bit for bit.
+ *   triangles  for every brick in list order and each of its 64 cells (x fastest): the cell's csrc/mc_table.inc triangles as in
+ *              sdfv_program_mesh_extract, but only if every crossing edge of the cell has an owner that is a brick; otherwise
+ *              the cell emits nothing.
+ *   promise    if the Lipschitz bound holds, every block that touches a crossing edge is a brick, and the mesh equals
+ *              sdfv_program_mesh_extract's at the same cells, box and flags AS A SET: the same vertex records, word for word,
+ *              the same triangles over them; only the order differs.  If it does not hold, the mesh has holes where blocks were
+ *              pruned wrongly; no index is out of range and nothing outside the scratch is read.
+ *   L          1 (lipschitz = 0 means 1) for a program whose PUSH_AFFINE matrices are rigid and whose PLANE normals have unit
+ *              length: every opcode keeps a 1-Lipschitz distance 1-Lipschitz.  Otherwise the caller's to state: the product,
+ *              over nested frames, of the largest stretch (largest singular value) of each PUSH_AFFINE's matrix -- which is the
+ *              INVERSE of the placement --, times the length of a PLANE's normal where that exceeds 1.  A larger L is always
+ *              safe and only costs evaluations; the library does not derive L from the program.
+ * Two calls with equal arguments return equal bytes.  A compiled handle is accepted and interprets (the mesh routes are not
+ * compiled routes).  Synchronises `stream` (once per level and once for the counts).  The scratch is the calling thread's, beside
+ * sdfv_program_mesh_extract's, about 1.4 KB per brick, kept for the next call and released by sdfv_mesh_trim.  Brick,
+ * vertex and triangle counts are 32-bit: more than 0xffffffff / 375 bricks (3 vertices for each of a brick's 125 points, the
+ * most it could own) are refused with SDFV_ERR_INVALID_ARGUMENT before anything could wrap. */
+typedef struct sdfv_sparse_mesh_stats {
+    uint32_t size;           /* in: sizeof(sdfv_sparse_mesh_stats), size-prefixed like sdfv_compiled_info */
+    uint32_t levels;         /* tested levels: log2(cells / 4) */
+    uint32_t tested[12];     /* blocks tested per level, coarsest first */
+    uint32_t kept[12];       /* ... and kept */
+    uint64_t bricks;         /* live leaf blocks (= kept[levels - 1]; 1 when cells == 4) */
+    uint64_t evaluations;    /* sum(tested) + 125 * bricks: program runs before the vertex phase */
+    uint64_t scratch_bytes;  /* device scratch this call needed (the implementation's figure, not part of the meaning) */
+} sdfv_sparse_mesh_stats;
+typedef struct sdfv_sparse_mesh_desc {
+    uint32_t size;           /* sizeof(sdfv_sparse_mesh_desc) as the CALLER compiled it (sdfv_march_desc's rule) */
+    uint32_t reserved;       /* 0 */
+    const sdfv_program *program;
+    const float *bb_min, *bb_max;   /* both NULL = the program's box, or both given (HOST, 3 floats) */
+    uint32_t cells;          /* per axis: a power of two, 4 .. 4096 */
+    uint32_t algorithm;      /* SDFV_MESHER_MARCHING_CUBES only: anything else is "Unsupported algorithm" */
+    uint32_t flags;          /* 0 or SDFV_MESH_WITH_MATERIALS */
+    float lipschitz;         /* L: 0 = 1.0f; otherwise finite and >= 1 */
+    sdfv_mesh *out;          /* freed with sdfv_mesh_free */
+    sdfv_sparse_mesh_stats *stats;  /* HOST or NULL; written when the call succeeds */
+} sdfv_sparse_mesh_desc;
+/* Argument errors (SDFV_ERR_INVALID_ARGUMENT, *out zeroed first where it is given) in this order: desc NULL, desc->size,
+ * reserved, out NULL, program NULL, half a box, algorithm, cells, flags, lipschitz, stats->size; then SDFV_ERR_NO_DEVICE. */
+int sdfv_program_mesh_extract_sparse(const sdfv_sparse_mesh_desc *desc, void *stream);
 
 /* ---- Meshing a sampled lattice (the reference's `mesh` command meshes ANY SDFSurface: all it asks is sample and normal) ----
  * The same extractor for an SDF the library cannot evaluate: a provider library, an application's own SDFSurface, a surface the

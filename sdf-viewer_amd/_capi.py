@@ -108,6 +108,22 @@ class CompiledInfo(C.Structure):
 
 assert C.sizeof(CompiledInfo) == 64
 
+
+class SparseMeshStats(C.Structure):
+    """sdfv_sparse_mesh_stats (size-prefixed): what sdfv_program_mesh_extract_sparse reports about its refinement."""
+    _fields_ = [("size", C.c_uint32), ("levels", C.c_uint32), ("tested", C.c_uint32 * 12), ("kept", C.c_uint32 * 12),
+                ("bricks", C.c_uint64), ("evaluations", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+
+class SparseMeshDesc(C.Structure):
+    """sdfv_sparse_mesh_desc: the descriptor of sdfv_program_mesh_extract_sparse (size-prefixed)."""
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("program", C.c_void_p), ("bb_min", C.POINTER(C.c_float)),
+                ("bb_max", C.POINTER(C.c_float)), ("cells", C.c_uint32), ("algorithm", C.c_uint32), ("flags", C.c_uint32),
+                ("lipschitz", C.c_float), ("out", C.POINTER(Mesh)), ("stats", C.POINTER(SparseMeshStats))]
+
+
+assert C.sizeof(SparseMeshStats) == 128 and C.sizeof(SparseMeshDesc) == 64
+
 PROTOTYPES = {
     "sdfv_raymarch_ex": (C.c_int, [C.POINTER(MarchDesc), C.c_void_p]),
     "sdfv_abi_version": (C.c_uint32, []),
@@ -217,6 +233,7 @@ PROTOTYPES = {
                                             C.c_uint32, C.POINTER(Mesh), C.c_void_p]),
     "sdfv_program_mesh_postproc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sdfv_program_mesh_postproc_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "sdfv_program_mesh_extract_sparse": (C.c_int, [C.POINTER(SparseMeshDesc), C.c_void_p]),
     # meshing a sampled lattice
     "sdfv_lattice_points": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_size_t, C.c_size_t, C.c_void_p,
                                       C.c_void_p]),

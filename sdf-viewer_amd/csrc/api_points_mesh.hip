@@ -9,6 +9,7 @@
 #include "dual_contour_kernels.h"
 #include "lattice_mesh_kernels.h"
 #include "grid_mesh_kernels.h"
+#include "sparse_mesh_kernels.h"
 
 using namespace sdfv;
 
@@ -223,6 +224,189 @@ int sdfv_program_mesh_extract(const sdfv_program* p, const float bb_min[3], cons
         });
 }
 
+// ---- sparse meshing of a program: refine blocks towards the surface, then marching cubes over the surviving bricks ----
+namespace {
+thread_local MeshScratch g_sparse_scratch;  // beside g_mesh_scratch, and released with it
+
+// The scratch of one phase: the totals (256 bytes), then the block list at a FIXED offset, so that a block that has to grow
+// takes the list along with one copy, then what the phase adds.  Refinement of `n` parents: 8 n candidates; the brick phase
+// over `n` bricks: 125 n points and 64 n cells.
+struct SparseLayout {
+    size_t list = 256, a = 0, b = 0, c = 0, d = 0, e = 0, tmp = 0, need = 0, tmp_bytes = 0;
+    static size_t up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+    static SparseLayout refinement(size_t n_parents) {
+        SparseLayout l;
+        const size_t cand = n_parents * 8;
+        l.a = l.list + up(cand * 4);  // cand
+        l.b = l.a + up(cand * 4);     // pos
+        l.tmp = l.b + up(cand * 4);
+        l.tmp_bytes = sdfv::mesh_scan_tmp_bytes(cand);
+        l.need = l.tmp + up(l.tmp_bytes);
+        return l;
+    }
+    static SparseLayout bricks(size_t n) {
+        SparseLayout l;
+        const size_t points = n * sdfv::kBrickPoints, cells = n * sdfv::kBrickCells;
+        l.a = l.list + up(n * 4);            // dist
+        l.b = l.a + up(points * 4);          // point_first
+        l.c = l.b + up((points + 1) * 4);    // cell_first
+        l.d = l.c + up((cells + 1) * 4);     // point_mask
+        l.e = l.d + up(points);              // neighbours
+        l.tmp = l.e + up(n * 32);
+        l.tmp_bytes = sdfv::mesh_scan_tmp_bytes(points + 1);
+        l.need = l.tmp + up(l.tmp_bytes);
+        return l;
+    }
+};
+
+// Make the calling thread's sparse scratch at least `need` bytes on the current device, keeping the first `keep` list entries.
+int sparse_scratch(size_t need, size_t keep, hipStream_t st) {
+    const int device_now = current_device();
+    MeshScratch& s = g_sparse_scratch;
+    if (s.bytes >= need && s.device == device_now) return SDFV_OK;
+    void* fresh = nullptr;
+    SDFV_HIP(hipMalloc(&fresh, need));
+    if (keep && s.p && s.device == device_now) {
+        hipError_t e = hipMemcpyAsync((char*)fresh + 256, (char*)s.p + 256, keep * 4, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            (void)hipFree(fresh);
+            return hip_fail(e, "sparse scratch copy");
+        }
+    }
+    s.release();
+    s.p = fresh;
+    s.bytes = need;
+    s.device = device_now;
+    return SDFV_OK;
+}
+
+// t = (L * r) * 1.001f for blocks of s cells (include/sdfgrid.h): f32, one rounding per step (this file is built with
+// -ffp-contract=off like the kernels)
+float sparse_threshold(const sdfv::MeshGrid& g, uint32_t s, float L) {
+    float e[3];
+    for (int a = 0; a < 3; ++a) e[a] = (float)s / (float)g.cells[a] * g.bb_size[a];
+    const float r = 0.5f * sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+    return (L * r) * 1.001f;
+}
+
+int extract_sparse(const sdfv_prog_op* dev_ops, uint32_t n_ops, const sdfv::MeshGrid& g, float L, bool materials, sdfv_mesh* out,
+                   sdfv_sparse_mesh_stats* stats, hipStream_t st) {
+    const uint32_t N = g.cells[0];
+    sdfv_sparse_mesh_stats s{};
+    while ((4u << s.levels) < N) ++s.levels;
+    size_t scratch = 0;
+    sdfv::SparseWork w{};
+    auto place = [&](const SparseLayout& l, size_t keep) {
+        if (int rc = sparse_scratch(l.need, keep, st)) return rc;
+        char* base = static_cast<char*>(g_sparse_scratch.p);
+        w.list = (uint32_t*)(base + l.list);
+        w.scan_tmp = base + l.tmp;
+        w.scan_tmp_bytes = l.tmp_bytes;
+        scratch = l.need > scratch ? l.need : scratch;
+        return (int)SDFV_OK;
+    };
+    // ---- refinement: the root (key 0) is not tested
+    uint32_t n = 1;
+    for (uint32_t level = 0; level < s.levels && n; ++level) {
+        const SparseLayout l = SparseLayout::refinement(n);
+        if (int rc = place(l, level ? n : 0)) return rc;
+        char* base = static_cast<char*>(g_sparse_scratch.p);
+        w.cand = (uint32_t*)(base + l.a);
+        w.pos = (uint32_t*)(base + l.b);
+        if (level == 0) SDFV_HIP(hipMemsetAsync(w.list, 0, 4, st));
+        const uint32_t shift = 31u - (uint32_t)__builtin_clz(N >> (level + 1));  // children of N / 2^(level + 1) cells
+        SDFV_HIP(sdfv::launch_sparse_refine(dev_ops, n_ops, g, shift, sparse_threshold(g, 1u << shift, L), w, n, (uint32_t*)base, st));
+        s.tested[level] = n * 8u;
+        SDFV_HIP(hipMemcpyAsync(&n, base, 4, hipMemcpyDeviceToHost, st));
+        SDFV_HIP(hipStreamSynchronize(st));
+        s.kept[level] = n;
+        s.evaluations += s.tested[level];
+    }
+    s.bricks = n;
+    s.evaluations += (uint64_t)sdfv::kBrickPoints * n;
+    sdfv_mesh m{};
+    if (n) {
+        if ((uint64_t)n * 3u * sdfv::kBrickPoints > 0xffffffffull)
+            return set_error(SDFV_ERR_INVALID_ARGUMENT, "%u bricks: more than %u could overflow the 32-bit vertex and triangle counts", n,
+                             0xffffffffu / (3u * sdfv::kBrickPoints));
+        // ---- the brick phase
+        const SparseLayout l = SparseLayout::bricks(n);
+        if (int rc = place(l, s.levels ? n : 0)) return rc;
+        char* base = static_cast<char*>(g_sparse_scratch.p);
+        w.dist = (float*)(base + l.a);
+        w.point_first = (uint32_t*)(base + l.b);
+        w.cell_first = (uint32_t*)(base + l.c);
+        w.point_mask = (uint8_t*)(base + l.d);
+        w.neighbours = (uint32_t*)(base + l.e);
+        if (s.levels == 0) SDFV_HIP(hipMemsetAsync(w.list, 0, 4, st));
+        SDFV_HIP(sdfv::launch_sparse_brick_lattice(dev_ops, n_ops, g, w, n, st));
+        SDFV_HIP(sdfv::launch_sparse_count(g, w, n, st));
+        uint32_t totals[2] = {0, 0};  // vertices, triangles: the extra last entry of each scan
+        SDFV_HIP(hipMemcpyAsync(&totals[0], w.point_first + (size_t)n * sdfv::kBrickPoints, 4, hipMemcpyDeviceToHost, st));
+        SDFV_HIP(hipMemcpyAsync(&totals[1], w.cell_first + (size_t)n * sdfv::kBrickCells, 4, hipMemcpyDeviceToHost, st));
+        SDFV_HIP(hipStreamSynchronize(st));
+        m.n_vertices = totals[0];
+        m.n_indices = (size_t)totals[1] * 3;
+        if (m.n_vertices) SDFV_HIP(hipMalloc((void**)&m.vertices, m.n_vertices * sizeof(sdfv_vertex)));
+        if (m.n_indices) {
+            hipError_t e = hipMalloc((void**)&m.indices, m.n_indices * 4);
+            if (e != hipSuccess) {
+                (void)hipFree(m.vertices);
+                return hip_fail(e, "hipMalloc(indices)");
+            }
+        }
+        hipError_t e = sdfv::launch_sparse_positions(g, w, n, m.vertices, m.n_vertices, st);
+        if (e == hipSuccess) e = sdfv::launch_program_vertex_normals(dev_ops, n_ops, m.vertices, m.n_vertices, materials, st);
+        if (e == hipSuccess) e = sdfv::launch_sparse_triangles(g, w, n, m.indices, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);  // the next extraction on this thread reuses the scratch
+        if (e != hipSuccess) {
+            (void)hipFree(m.vertices);
+            (void)hipFree(m.indices);
+            return hip_fail(e, "sparse mesh emit");
+        }
+    }
+    *out = m;
+    if (stats) {
+        s.size = stats->size;
+        s.scratch_bytes = scratch;
+        memcpy(stats, &s, sizeof(s));
+    }
+    return SDFV_OK;
+}
+}  // namespace
+
+int sdfv_program_mesh_extract_sparse(const sdfv_sparse_mesh_desc* desc, void* stream) {
+    sdfv_sparse_mesh_desc d;
+    if (int rc = read_sized_desc(desc, sizeof(sdfv_sparse_mesh_desc), "sdfv_sparse_mesh_desc", d)) {
+        if (desc && desc->size >= sizeof(sdfv_sparse_mesh_desc) && desc->out) memset(desc->out, 0, sizeof(*desc->out));
+        return rc;
+    }
+    if (d.out) memset(d.out, 0, sizeof(*d.out));
+    if (d.reserved) return set_error(SDFV_ERR_INVALID_ARGUMENT, "sdfv_sparse_mesh_desc.reserved must be 0");
+    if (!d.out) return set_error(SDFV_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (!d.program) return set_error(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
+    if ((d.bb_min == nullptr) != (d.bb_max == nullptr))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "bounding box: bb_min and bb_max are both given or both NULL (the program's box)");
+    if (d.algorithm != SDFV_MESHER_MARCHING_CUBES) return set_error(SDFV_ERR_INVALID_ARGUMENT, "Unsupported algorithm %u", d.algorithm);
+    if (d.cells < 4 || d.cells > 4096 || (d.cells & (d.cells - 1u)))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "cells %u is not a power of two in [4, 4096]", d.cells);
+    if (d.flags & ~SDFV_MESH_WITH_MATERIALS) return set_error(SDFV_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", d.flags);
+    if (!(d.lipschitz == 0.0f || (d.lipschitz >= 1.0f && d.lipschitz <= 3.402823466e+38f)))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "lipschitz %g is neither 0 (= 1) nor a finite number >= 1", (double)d.lipschitz);
+    if (d.stats && d.stats->size < sizeof(sdfv_sparse_mesh_stats))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "sdfv_sparse_mesh_stats.size = %u is smaller than the structure (%zu)", d.stats->size,
+                         sizeof(sdfv_sparse_mesh_stats));
+    if (int rc = need_device()) return rc;
+    const sdfv_prog_op* dev_ops = nullptr;
+    uint32_t n_ops = 0;
+    const float* bb = nullptr;
+    if (int rc = program_on_device(d.program, &dev_ops, &n_ops, &bb)) return rc;
+    return extract_sparse(dev_ops, n_ops, lattice_grid(d.bb_min ? d.bb_min : bb, d.bb_max ? d.bb_max : bb + 3, d.cells),
+                          d.lipschitz == 0.0f ? 1.0f : d.lipschitz, (d.flags & SDFV_MESH_WITH_MATERIALS) != 0, d.out, d.stats,
+                          (hipStream_t)stream);
+}
+
 // ---- meshing a sampled lattice: the SDF is the caller's, the library sees (cells + 1)^3 distances ----
 namespace {
 int check_lattice(const float* dist, const float bb_min[3], const float bb_max[3]) {
@@ -361,6 +545,7 @@ int sdfv_grid_vertex_materials(const sdfv_grid* grid, const float* tex0, const f
 
 int sdfv_mesh_trim(void) {
     g_mesh_scratch.release();
+    g_sparse_scratch.release();
     release_march_caches();
     return SDFV_OK;
 }

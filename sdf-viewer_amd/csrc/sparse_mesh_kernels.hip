@@ -1,0 +1,344 @@
+// sparse_mesh_kernels.hip -- sparse marching cubes over SDF programs on gfx950 (include/sdfgrid.h, "SDF programs: sparse
+// meshing"): the program is evaluated only where a 1-Lipschitz distance cannot rule the surface out.
+//
+// Shape.  As in program_mesh_kernels.hip the interpreter costs one program run per WAVE, so nothing evaluates under a sparse
+// mask: both evaluating kernels run over compact lists, one element per thread, every lane but the last wave's tail live.
+//  * sdfprog_sparse_refine: one CHILD block per thread (8 per block of the list), distance only at its centre lattice point,
+//    kept iff !(|d| > threshold); sparse_compact moves the survivors up behind an exclusive scan -- no atomics, the order is the
+//    header's.  One launch per level; the host reads one count per level.
+//  * sdfprog_sparse_bricks: thread t has lattice point t % 125 of brick t / 125: all 5^3 points of a brick, its upper faces
+//    included, because a pruned neighbour would leave them unknown.  Distances brick-major.
+//  * sparse_brick_edges, sparse_brick_neighbours, sparse_brick_cells, sparse_brick_positions, sparse_brick_triangles: the
+//    SDF-free steps of mesh_kernels.hip over bricks.  A brick owns the points with local index < 4 per axis (<= 4 where it is
+//    the box's last brick), and the edges that start there; a cell on a brick's upper faces reads the records of up to seven
+//    neighbours, which sparse_brick_neighbours has looked up once per brick by binary search in the brick list (sorted by Morton
+//    key; a directory of (cells / 4)^3 words would be 4 GiB at 4096 cells).  A cell whose crossing edge has no owner among the
+//    bricks (the program broke its Lipschitz promise) emits nothing: no index is ever out of range.
+// A block is its Morton key in units of its own side, x the lowest bit; keys are below 2^30 (1024 bricks per axis at the most).
+// The kernels carry C names: tests and profiles find them under the same symbol whatever the toolchain mangles.
+#include "sparse_mesh_kernels.h"
+
+#include "kernel_common.h"
+#include "mesh_lattice.h"
+#include "program_eval.h"
+
+namespace sdfv {
+
+namespace {
+
+#define SDFV_MC_TABLE __constant__ const
+#include "mc_table.inc"
+#undef SDFV_MC_TABLE
+
+constexpr uint32_t kKept = 0x80000000u;
+constexpr uint32_t kNoBrick = 0xffffffffu;
+
+// every third bit of a Morton key -> a 10-bit coordinate, and back
+__device__ __forceinline__ uint32_t gather3(uint32_t x) {
+    x &= 0x09249249u;
+    x = (x ^ (x >> 2)) & 0x030c30c3u;
+    x = (x ^ (x >> 4)) & 0x0300f00fu;
+    x = (x ^ (x >> 8)) & 0x030000ffu;
+    x = (x ^ (x >> 16)) & 0x000003ffu;
+    return x;
+}
+__device__ __forceinline__ uint32_t spread3(uint32_t x) {
+    x &= 0x000003ffu;
+    x = (x ^ (x << 16)) & 0x030000ffu;
+    x = (x ^ (x << 8)) & 0x0300f00fu;
+    x = (x ^ (x << 4)) & 0x030c30c3u;
+    x = (x ^ (x << 2)) & 0x09249249u;
+    return x;
+}
+
+__device__ __forceinline__ bool inside(float d) { return d < 0.0f; }  // Signed: negative inside
+
+// thread t of a brick-major array of 125 per brick -> the brick and the local point (x fastest)
+__device__ __forceinline__ void unbrick(uint32_t t, uint32_t& b, uint32_t& lx, uint32_t& ly, uint32_t& lz) {
+    b = t / kBrickPoints;
+    const uint32_t l = t - b * kBrickPoints;
+    lz = l / 25u;
+    const uint32_t r = l - lz * 25u;
+    ly = r / 5u;
+    lx = r - ly * 5u;
+}
+
+// index of the brick with this key, or kNoBrick: the list is sorted
+__device__ __forceinline__ uint32_t find_brick(const uint32_t* __restrict__ bricks, uint32_t n, uint32_t key) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (bricks[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && bricks[lo] == key ? lo : kNoBrick;
+}
+
+// The cube case of cell (cx, cy, cz) of a brick whose distances start at d: corner bit = x | y << 1 | z << 2.
+__device__ __forceinline__ uint32_t brick_cell_case(const float* __restrict__ d, uint32_t cx, uint32_t cy, uint32_t cz) {
+    const float* o = d + (cz * 5u + cy) * 5u + cx;
+    uint32_t c = 0;
+    for (uint32_t corner = 0; corner < 8; ++corner)
+        if (inside(o[(corner & 1) + ((corner >> 1) & 1) * 5u + ((corner >> 2) & 1) * 25u])) c |= 1u << corner;
+    return c;
+}
+
+// Does edge e (= 4 * axis + u + 2 * v, the table's numbering) of a cell with cube case cs cross?
+__device__ __forceinline__ bool edge_crosses(uint32_t cs, int e) {
+    const int a = e >> 2, s = e & 3;
+    const int o0 = a == 0 ? 1 : 0, o1 = a == 2 ? 1 : 2;
+    const uint32_t start = ((s & 1) << o0) | ((s >> 1) << o1);
+    return (((cs >> start) ^ (cs >> (start | (1u << a)))) & 1u) != 0;
+}
+
+// Where the record of edge e of cell (cx, cy, cz) of brick `self` (whose key the caller has loaded) is kept: the slot
+// of its owning point in the brick-major arrays, or kNoBrick when the owner is no brick.  The edge starts at local point c + (u, v)
+// on the two other axes; a local index of 4 belongs to the next brick on that axis unless this one is the box's last.
+// (Scalars throughout: e is a run-time value in the triangle kernel, and an array indexed by it would live in scratch.)
+__device__ __forceinline__ bool next_brick(uint32_t& l, uint32_t& b, uint32_t last) {
+    if (l != 4u || b >= last) return false;
+    l = 0;
+    b += 1;
+    return true;
+}
+__device__ __forceinline__ uint32_t edge_owner_slot(const uint32_t* __restrict__ neighbours, uint32_t last, uint32_t self,
+                                                    uint32_t key, uint32_t cx, uint32_t cy, uint32_t cz, int e) {
+    const uint32_t a = (uint32_t)e >> 2, u = (uint32_t)e & 1u, v = ((uint32_t)e >> 1) & 1u;
+    uint32_t lx = cx + (a != 0u ? u : 0u);  // axis 0: (u, v) along (y, z); axis 1: along (x, z); axis 2: along (x, y)
+    uint32_t ly = cy + (a == 0u ? u : (a == 2u ? v : 0u));
+    uint32_t lz = cz + (a != 2u ? v : 0u);
+    uint32_t bx = gather3(key), by = gather3(key >> 1), bz = gather3(key >> 2);
+    const bool fx = next_brick(lx, bx, last), fy = next_brick(ly, by, last), fz = next_brick(lz, bz, last);
+    uint32_t owner = self;
+    if (fx || fy || fz) {
+        owner = neighbours[self * 8u + ((fx ? 1u : 0u) | (fy ? 2u : 0u) | (fz ? 4u : 0u))];
+        if (owner == kNoBrick) return kNoBrick;
+    }
+    return owner * kBrickPoints + (lz * 5u + ly) * 5u + lx;
+}
+
+}  // namespace
+
+extern "C" {
+
+__global__ __launch_bounds__(kBlock) void sdfprog_sparse_refine(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,
+                                                                const uint32_t* __restrict__ parents, uint32_t n, uint32_t shift,
+                                                                float threshold, uint32_t* __restrict__ cand,
+                                                                uint32_t* __restrict__ pos) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t key = parents[t >> 3] * 8u + (t & 7u);
+    const uint32_t half = (1u << shift) >> 1;  // the centre lattice point: o + s / 2
+    float px, py, pz;
+    lattice_position(g, (gather3(key) << shift) + half, (gather3(key >> 1) << shift) + half, (gather3(key >> 2) << shift) + half,
+                     px, py, pz);
+    const float d = prog::run(ops, n_ops, px, py, pz).d;
+    const bool keep = !(fabsf(d) > threshold);  // a NaN distance keeps the block
+    cand[t] = key | (keep ? kKept : 0u);
+    pos[t] = keep ? 1u : 0u;
+}
+
+// survivors up, in order; the last thread leaves their number
+__global__ __launch_bounds__(kBlock) void sparse_compact(const uint32_t* __restrict__ cand, const uint32_t* __restrict__ pos,
+                                                         uint32_t n, uint32_t* __restrict__ list, uint32_t* __restrict__ kept) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t c = cand[t], at = pos[t];
+    if (c & kKept) list[at] = c & ~kKept;
+    if (t == n - 1) *kept = at + (c >> 31);
+}
+
+__global__ __launch_bounds__(kBlock) void sdfprog_sparse_bricks(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,
+                                                                const uint32_t* __restrict__ bricks, uint32_t n,
+                                                                float* __restrict__ dist) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    uint32_t b, lx, ly, lz;
+    unbrick(t, b, lx, ly, lz);
+    const uint32_t key = bricks[b];
+    float px, py, pz;
+    lattice_position(g, gather3(key) * 4u + lx, gather3(key >> 1) * 4u + ly, gather3(key >> 2) * 4u + lz, px, py, pz);
+    dist[t] = prog::run(ops, n_ops, px, py, pz).d;
+}
+
+// Which of the point's three +axis edges the brick owns and cross; count -> scan input.  n = 125 * bricks; thread n writes the
+// scan's extra entry.  last = bricks per axis - 1.
+__global__ __launch_bounds__(kBlock) void sparse_brick_edges(uint32_t last, const uint32_t* __restrict__ bricks, uint32_t n,
+                                                             const float* __restrict__ dist, uint8_t* __restrict__ mask,
+                                                             uint32_t* __restrict__ count) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t > n) return;
+    if (t == n) {
+        count[n] = 0;
+        return;
+    }
+    uint32_t b, lx, ly, lz;
+    unbrick(t, b, lx, ly, lz);
+    const uint32_t key = bricks[b];
+    const bool owned = (lx < 4u || gather3(key) == last) && (ly < 4u || gather3(key >> 1) == last) &&
+                       (lz < 4u || gather3(key >> 2) == last);
+    uint32_t m = 0;
+    if (owned) {  // an owned point's +axis neighbour (local index < 4 on that axis) is one of the brick's own 125
+        const bool in0 = inside(dist[t]);
+        if (lx < 4u && inside(dist[t + 1]) != in0) m |= 1u;
+        if (ly < 4u && inside(dist[t + 5]) != in0) m |= 2u;
+        if (lz < 4u && inside(dist[t + 25]) != in0) m |= 4u;
+    }
+    mask[t] = (uint8_t)m;
+    count[t] = __popc(m);
+}
+
+// The up to seven bricks whose points a brick's upper-face cells refer to: neighbours[8 * b + dir] = index of the brick at
+// offset (dir & 1, dir >> 1 & 1, dir >> 2) from brick b, or kNoBrick; entry 0 is b itself.  One binary search per entry, in the
+// brick list, which the refinement leaves sorted by key.  n = 8 * bricks.
+__global__ __launch_bounds__(kBlock) void sparse_brick_neighbours(uint32_t last, const uint32_t* __restrict__ bricks,
+                                                                  uint32_t n_bricks, uint32_t* __restrict__ neighbours) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n_bricks * 8u) return;
+    const uint32_t b = t >> 3, key = bricks[b];
+    const uint32_t bx = gather3(key) + (t & 1u), by = gather3(key >> 1) + ((t >> 1) & 1u), bz = gather3(key >> 2) + ((t >> 2) & 1u);
+    uint32_t at = b;
+    if (t & 7u)
+        at = bx > last || by > last || bz > last ? kNoBrick
+                                                 : find_brick(bricks, n_bricks, spread3(bx) | (spread3(by) << 1) | (spread3(bz) << 2));
+    neighbours[t] = at;
+}
+
+// Triangles per cell: the table's, or none where a crossing edge of the cell has no owner among the bricks.  n = 64 * bricks.
+__global__ __launch_bounds__(kBlock) void sparse_brick_cells(uint32_t last, const uint32_t* __restrict__ bricks, uint32_t n_bricks,
+                                                             const uint32_t* __restrict__ neighbours,
+                                                             const float* __restrict__ dist, uint32_t* __restrict__ count) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t n = n_bricks * kBrickCells;
+    if (t > n) return;
+    if (t == n) {
+        count[n] = 0;
+        return;
+    }
+    const uint32_t b = t >> 6;
+    const uint32_t cx = t & 3u, cy = (t >> 2) & 3u, cz = (t >> 4) & 3u;
+    const uint32_t cs = brick_cell_case(dist + (size_t)b * kBrickPoints, cx, cy, cz);
+    uint32_t n_tri = kMcTriCount[cs];
+    if (n_tri != 0 && (cx == 3u || cy == 3u || cz == 3u)) {  // only an upper-face cell has edges of other owners
+        const uint32_t key = bricks[b];
+#pragma unroll
+        for (int e = 0; e < 12; ++e)
+            if (edge_crosses(cs, e) && edge_owner_slot(neighbours, last, b, key, cx, cy, cz, e) == kNoBrick) n_tri = 0;
+    }
+    count[t] = n_tri;
+}
+
+// One vertex per owned crossing edge, bricks in list order, points in local order, then axis order: edge_position with the
+// point's lattice index in the whole box.  n = 125 * bricks.
+__global__ __launch_bounds__(kBlock) void sparse_brick_positions(MeshGrid g, const uint32_t* __restrict__ bricks, uint32_t n,
+                                                                 const float* __restrict__ dist, const uint8_t* __restrict__ mask,
+                                                                 const uint32_t* __restrict__ first, float* __restrict__ vertices) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t m = mask[t];
+    if (m == 0) return;
+    uint32_t b, lx, ly, lz;
+    unbrick(t, b, lx, ly, lz);
+    const uint32_t key = bricks[b];
+    const uint32_t idx[3] = {gather3(key) * 4u + lx, gather3(key >> 1) * 4u + ly, gather3(key >> 2) * 4u + lz};
+    const uint32_t stride[3] = {1u, 5u, 25u};
+    const float d0 = dist[t];
+    uint32_t id = first[t];
+    for (int a = 0; a < 3; ++a) {
+        if (!(m & (1u << a))) continue;
+        float* o = vertices + (size_t)id * 12;
+        edge_position(g, idx, a, d0, dist[t + stride[a]], o[0], o[1], o[2]);
+        ++id;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void sparse_brick_triangles(uint32_t last, const uint32_t* __restrict__ bricks,
+                                                                 uint32_t n_bricks, const uint32_t* __restrict__ neighbours,
+                                                                 const float* __restrict__ dist,
+                                                                 const uint8_t* __restrict__ mask,
+                                                                 const uint32_t* __restrict__ point_first,
+                                                                 const uint32_t* __restrict__ cell_first,
+                                                                 uint32_t* __restrict__ indices) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n_bricks * kBrickCells) return;
+    const uint32_t begin = cell_first[t], n_tri = cell_first[t + 1] - begin;  // 0 too where sparse_brick_cells refused the cell
+    if (n_tri == 0) return;
+    const uint32_t b = t >> 6;
+    const uint32_t cx = t & 3u, cy = (t >> 2) & 3u, cz = (t >> 4) & 3u;
+    const uint32_t cs = brick_cell_case(dist + (size_t)b * kBrickPoints, cx, cy, cz);
+    const uint32_t key = bricks[b];
+    uint32_t* out = indices + (size_t)begin * 3;
+    for (uint32_t q = 0; q < n_tri * 3; ++q) {
+        const int e = kMcTriEdges[cs][q];
+        const uint32_t slot = edge_owner_slot(neighbours, last, b, key, cx, cy, cz, e);  // a brick's: sparse_brick_cells has looked
+        out[q] = slot == kNoBrick ? 0u : point_first[slot] + __popc((uint32_t)mask[slot] & ((1u << (e >> 2)) - 1u));
+    }
+}
+
+}  // extern "C"
+
+namespace {
+MeshWork scan_work(const SparseWork& w) {
+    MeshWork m{};
+    m.scan_tmp = w.scan_tmp;
+    m.scan_tmp_bytes = w.scan_tmp_bytes;
+    return m;
+}
+bool sparse_grid(const MeshGrid& g) {  // one power of two, 4 .. 4096, on every axis
+    const uint32_t n = g.cells[0];
+    return n >= 4 && n <= 4096 && (n & (n - 1)) == 0 && g.cells[1] == n && g.cells[2] == n;
+}
+}  // namespace
+
+hipError_t launch_sparse_refine(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, uint32_t shift, float threshold,
+                                const SparseWork& w, uint32_t n_parents, uint32_t* kept_dev, hipStream_t stream) {
+    if (!sparse_grid(g) || n_parents == 0 || n_parents > 0x10000000u || shift < 2 || (2u << shift) > g.cells[0])
+        return hipErrorInvalidValue;  // children of 4 .. cells / 2 cells, and 8 of them per parent in 32 bits
+    const uint32_t n = n_parents * 8u;
+    hipLaunchKernelGGL(sdfprog_sparse_refine, dim3(blocks_for(n)), dim3(kBlock), 0, stream, ops, n_ops, g, w.list, n, shift,
+                       threshold, w.cand, w.pos);
+    if (hipError_t e = mesh_exclusive_scan(scan_work(w), w.pos, n, stream); e != hipSuccess) return e;
+    hipLaunchKernelGGL(sparse_compact, dim3(blocks_for(n)), dim3(kBlock), 0, stream, w.cand, w.pos, n, w.list, kept_dev);
+    return hipGetLastError();
+}
+
+hipError_t launch_sparse_brick_lattice(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const SparseWork& w,
+                                       uint32_t n_bricks, hipStream_t stream) {
+    if (!sparse_grid(g) || n_bricks == 0 || (uint64_t)n_bricks * kBrickPoints >= 0xffffffffull) return hipErrorInvalidValue;
+    const uint32_t n = n_bricks * kBrickPoints;
+    hipLaunchKernelGGL(sdfprog_sparse_bricks, dim3(blocks_for(n)), dim3(kBlock), 0, stream, ops, n_ops, g, w.list, n, w.dist);
+    return hipGetLastError();
+}
+
+hipError_t launch_sparse_count(const MeshGrid& g, const SparseWork& w, uint32_t n_bricks, hipStream_t stream) {
+    if (!sparse_grid(g) || n_bricks == 0 || (uint64_t)n_bricks * kBrickPoints >= 0xffffffffull) return hipErrorInvalidValue;
+    const uint32_t last = g.cells[0] / 4u - 1u, n_points = n_bricks * kBrickPoints, n_cells = n_bricks * kBrickCells;
+    hipLaunchKernelGGL(sparse_brick_edges, dim3(blocks_for((uint64_t)n_points + 1)), dim3(kBlock), 0, stream, last, w.list, n_points,
+                       w.dist, w.point_mask, w.point_first);
+    if (hipError_t e = mesh_exclusive_scan(scan_work(w), w.point_first, (size_t)n_points + 1, stream); e != hipSuccess) return e;
+    hipLaunchKernelGGL(sparse_brick_neighbours, dim3(blocks_for((uint64_t)n_bricks * 8)), dim3(kBlock), 0, stream, last, w.list,
+                       n_bricks, w.neighbours);
+    hipLaunchKernelGGL(sparse_brick_cells, dim3(blocks_for((uint64_t)n_cells + 1)), dim3(kBlock), 0, stream, last, w.list, n_bricks,
+                       w.neighbours, w.dist, w.cell_first);
+    return mesh_exclusive_scan(scan_work(w), w.cell_first, (size_t)n_cells + 1, stream);
+}
+
+hipError_t launch_sparse_positions(const MeshGrid& g, const SparseWork& w, uint32_t n_bricks, sdfv_vertex* vertices, size_t n,
+                                   hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (!vertices || n_bricks == 0) return hipErrorInvalidValue;
+    const uint32_t n_points = n_bricks * kBrickPoints;
+    hipLaunchKernelGGL(sparse_brick_positions, dim3(blocks_for(n_points)), dim3(kBlock), 0, stream, g, w.list, n_points, w.dist,
+                       w.point_mask, w.point_first, reinterpret_cast<float*>(vertices));
+    return hipGetLastError();
+}
+
+hipError_t launch_sparse_triangles(const MeshGrid& g, const SparseWork& w, uint32_t n_bricks, uint32_t* indices,
+                                   hipStream_t stream) {
+    if (indices && n_bricks)
+        hipLaunchKernelGGL(sparse_brick_triangles, dim3(blocks_for((uint64_t)n_bricks * kBrickCells)), dim3(kBlock), 0, stream,
+                           g.cells[0] / 4u - 1u, w.list, n_bricks, w.neighbours, w.dist, w.point_mask, w.point_first, w.cell_first,
+                           indices);
+    return hipGetLastError();
+}
+
+}  // namespace sdfv

@@ -223,6 +223,28 @@ class CompiledProgram:
                                             _stream_ptr(stream)))
         return mesh_tensors(m)
 
+    def mesh_sparse(self, n, bb=None, materials=False, lipschitz=0.0, stream=None, want_stats=False):
+        """sdfv_program_mesh_extract_sparse: marching cubes over n^3 cells (n a power of two, 4 .. 4096) of `bb`, sampling only the
+        4-cell bricks that a distance with Lipschitz constant `lipschitz` (0.0: 1) cannot rule out -> (vertices [V, 12] float32,
+        indices [3 * triangles] int32), the set mesh(n, bb, materials) returns in another order; with want_stats also a dict
+        (levels, tested, kept, bricks, evaluations, scratch_bytes)."""
+        from . import _stream_ptr, f3, mesh_tensors
+        m, s, d = _capi.Mesh(), _capi.SparseMeshStats(), _capi.SparseMeshDesc()
+        s.size, d.size = C.sizeof(s), C.sizeof(d)
+        d.program = self.h
+        lo, hi = (None, None) if bb is None else (f3(bb[:3]), f3(bb[3:]))
+        if bb is not None:
+            d.bb_min, d.bb_max = lo, hi
+        d.cells, d.algorithm, d.flags = int(n), _capi.MESHER_MARCHING_CUBES, _capi.MESH_WITH_MATERIALS if materials else 0
+        d.lipschitz = float(lipschitz)
+        d.out, d.stats = C.pointer(m), C.pointer(s)
+        check(lib.sdfv_program_mesh_extract_sparse(C.byref(d), _stream_ptr(stream)))
+        v, i = mesh_tensors(m)
+        if not want_stats:
+            return v, i
+        return v, i, dict(levels=s.levels, tested=list(s.tested[:s.levels]), kept=list(s.kept[:s.levels]), bricks=s.bricks,
+                          evaluations=s.evaluations, scratch_bytes=s.scratch_bytes)
+
     def normal_points(self, points, eps=0.0, stream=None, out=None):
         """SDFSurface::normal(p, eps) of the program (eps <= 0: None): [n, 3] float32 CUDA tensor -> [n, 3] (out: optional result
         tensor)."""
