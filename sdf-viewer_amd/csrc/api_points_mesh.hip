@@ -23,55 +23,93 @@ struct MeshScratch {
         if (p) (void)hipFree(p);
         *this = MeshScratch{};
     }
-};
-thread_local MeshScratch g_mesh_scratch;  // freed by sdfv_mesh_trim(); a thread that exits without it leaks the block
-
-// Meshers::mesh for any kind of SDF: the arguments are checked by the caller.  An SDF kind supplies two things:
-// `lattice(g, w, stream)` writes the distances of the lattice points into w.dist (or points w.dist at distances that exist: a
-// caller's lattice, which no step writes), and `attributes(vertices, n, final, stream)` everything but
-// the position of n vertices whose positions are written.  Counting, the scans, the positions of the crossing edges, the
-// triangles (mesh_kernels.h) and dual contouring's solve and quads (dual_contour_kernels.h) do not depend on the SDF.  `final` is
-// false only for dual contouring's Hermite records: crossing-edge vertices in a temporary, of which the solve reads position and
-// normal and nothing else.  The scratch is the calling thread's one block.
-// An SDF kind whose attributes are cheap enough to write under the positions' sparse mask may also give
-// `fused(g, w, vertices, n, stream)`: marching cubes then calls it in the place of positions + attributes (the demo tree does).
-// The lattice is `g`: any number of cells per axis (MeshGrid::launchable).
-template <typename LatticeFn, typename AttributesFn, typename FusedFn = std::nullptr_t>
-int extract_mesh(const sdfv::MeshGrid& g, uint32_t algorithm, sdfv_mesh* out, hipStream_t st, LatticeFn&& lattice,
-                 AttributesFn&& attributes, FusedFn&& fused = nullptr) {
-    const bool dual = algorithm == SDFV_MESHER_DUAL_CONTOURING_PARTICLE;
-    const size_t n_points = g.n_points(), n_cells = g.n_cells();
-    // One scratch block per host thread, grown on demand and kept between calls (allocating ~13 B per lattice point
-    // afresh costs more than the extraction itself); sdfv_mesh_trim() gives it back.
-    sdfv::MeshWork w{};
-    w.scan_tmp_bytes = sdfv::mesh_scan_tmp_bytes(n_points);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_dist = 0, o_first = o_dist + up(n_points * 4), o_cfirst = o_first + up(n_points * 4),
-                 o_mask = o_cfirst + up(n_cells * 4), o_tmp = o_mask + up(n_points), o_totals = o_tmp + up(w.scan_tmp_bytes),
-                 o_qfirst = o_totals + 256, need = o_qfirst + (dual ? up(n_points * 4) : 0);  // dual contouring: one more scan
-    const int device_now = current_device();
-    if (g_mesh_scratch.bytes < need || g_mesh_scratch.device != device_now) {
-        g_mesh_scratch.release();
-        SDFV_HIP(hipMalloc(&g_mesh_scratch.p, need));
-        g_mesh_scratch.bytes = need;
-        g_mesh_scratch.device = device_now;
+    // Make the block at least `need` bytes on the current device, keeping the `keep` bytes at offset `at` (none: the block's
+    // content is then not defined, and the old block goes before the new one comes).
+    int reserve(size_t need, size_t at, size_t keep, hipStream_t st) {
+        const int device_now = current_device();
+        if (bytes >= need && device == device_now) return SDFV_OK;
+        if (!keep || device != device_now) release();
+        void* fresh = nullptr;
+        SDFV_HIP(hipMalloc(&fresh, need));
+        if (p) {
+            hipError_t e = hipMemcpyAsync((char*)fresh + at, (char*)p + at, keep, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) {
+                (void)hipFree(fresh);
+                return hip_fail(e, "sparse scratch copy");
+            }
+            release();
+        }
+        p = fresh;
+        bytes = need;
+        device = device_now;
+        return SDFV_OK;
     }
-    char* base = static_cast<char*>(g_mesh_scratch.p);
-    w.dist = (float*)(base + o_dist);
-    w.point_first = (uint32_t*)(base + o_first);
-    w.cell_first = (uint32_t*)(base + o_cfirst);
-    w.point_mask = (uint8_t*)(base + o_mask);
-    w.scan_tmp = base + o_tmp;
-    w.quad_first = dual ? (uint32_t*)(base + o_qfirst) : nullptr;
-    struct { void* p; } totals{base + o_totals};
-    SDFV_HIP(lattice(g, w, st));
-    SDFV_HIP(dual ? sdfv::launch_dc_count(g, w, (uint32_t*)totals.p, st) : sdfv::launch_mesh_count(g, w, (uint32_t*)totals.p, st));
-    uint32_t n[3] = {0, 0, 0};  // marching cubes: vertices, triangles; dual contouring: Hermite records, vertices, quads
-    SDFV_HIP(hipMemcpyAsync(n, totals.p, dual ? 12 : 8, hipMemcpyDeviceToHost, st));
-    SDFV_HIP(hipStreamSynchronize(st));
-    sdfv_mesh m{};
-    m.n_vertices = dual ? n[1] : n[0];
-    m.n_indices = dual ? (size_t)n[2] * 6 : (size_t)n[1] * 3;
+};
+// One block per host thread and route, grown on demand and kept between calls (allocating ~13 B per lattice point afresh costs
+// more than the extraction itself); sdfv_mesh_trim() gives both back, a thread that exits without it leaks them.
+thread_local MeshScratch g_mesh_scratch, g_sparse_scratch;
+
+// The sub-blocks of a scratch block, in the order they are taken, each on a 256-byte boundary.  Without a block (base NULL)
+// nothing is handed out and `at` only adds up: a layout is written once, run once for its size and once over the block.
+struct Carve {
+    char* base;
+    size_t at = 0;
+    template <typename T>
+    T* take(size_t n) {
+        T* sub = base ? reinterpret_cast<T*>(base + at) : nullptr;
+        at += (n * sizeof(T) + 255) & ~(size_t)255;
+        return sub;
+    }
+};
+
+// The dense extraction's scratch; dual contouring has one more scan.  Returns the bytes it takes.
+size_t lay_out(sdfv::MeshWork& w, void* block, size_t n_points, size_t n_cells, bool dual) {
+    Carve c{static_cast<char*>(block)};
+    w.scan_tmp_bytes = sdfv::mesh_scan_tmp_bytes(n_points);
+    w.dist = c.take<float>(n_points);
+    w.point_first = c.take<uint32_t>(n_points);
+    w.cell_first = c.take<uint32_t>(n_cells);
+    w.point_mask = c.take<uint8_t>(n_points);
+    w.scan_tmp = c.take<char>(w.scan_tmp_bytes);
+    w.totals = c.take<uint32_t>(64);
+    w.quad_first = dual ? c.take<uint32_t>(n_points) : nullptr;
+    return c.at;
+}
+
+// The two phases of the sparse extraction's: the totals word (256 bytes), then the block list at a FIXED offset, so that a block
+// that has to grow takes the list along with one copy, then what the phase adds.  Refinement of n parents: room for their 8 n
+// children in the list, and 8 n candidates ...
+constexpr size_t kSparseListAt = 256;
+size_t lay_out_refinement(sdfv::SparseWork& w, void* block, size_t n_parents) {
+    Carve c{static_cast<char*>(block)};
+    const size_t children = n_parents * 8;
+    w.mesh.scan_tmp_bytes = sdfv::mesh_scan_tmp_bytes(children);
+    w.mesh.totals = c.take<uint32_t>(64);
+    w.list = c.take<uint32_t>(children);
+    w.cand = c.take<uint32_t>(children);
+    w.pos = c.take<uint32_t>(children);
+    w.mesh.scan_tmp = c.take<char>(w.mesh.scan_tmp_bytes);
+    return c.at;
+}
+// ... the brick phase over n bricks: 125 n points and 64 n cells, each scan with one entry more (the total).
+size_t lay_out_bricks(sdfv::SparseWork& w, void* block, size_t n) {
+    Carve c{static_cast<char*>(block)};
+    const size_t points = n * sdfv::kBrickPoints, cells = n * sdfv::kBrickCells;
+    w.mesh.scan_tmp_bytes = sdfv::mesh_scan_tmp_bytes(points + 1);
+    w.mesh.totals = c.take<uint32_t>(64);
+    w.list = c.take<uint32_t>(n);
+    w.mesh.dist = c.take<float>(points);
+    w.mesh.point_first = c.take<uint32_t>(points + 1);
+    w.mesh.cell_first = c.take<uint32_t>(cells + 1);
+    w.mesh.point_mask = c.take<uint8_t>(points);
+    w.neighbours = c.take<uint32_t>(n * 8);
+    w.mesh.scan_tmp = c.take<char>(w.mesh.scan_tmp_bytes);
+    return c.at;
+}
+
+// The output buffers for the counts in m.  On failure nothing is left allocated.
+int allocate_mesh(sdfv_mesh& m) {
     if (m.n_vertices) SDFV_HIP(hipMalloc((void**)&m.vertices, m.n_vertices * sizeof(sdfv_vertex)));
     if (m.n_indices) {
         hipError_t e = hipMalloc((void**)&m.indices, m.n_indices * 4);
@@ -80,6 +118,48 @@ int extract_mesh(const sdfv::MeshGrid& g, uint32_t algorithm, sdfv_mesh* out, hi
             return hip_fail(e, "hipMalloc(indices)");
         }
     }
+    return SDFV_OK;
+}
+// ... and the end of an extraction whose emit chain returned e: the mesh goes out once the stream is done with it (the next
+// extraction on this thread reuses the scratch), or, on any failure, both buffers go back.
+int finish_mesh(hipError_t e, const sdfv_mesh& m, sdfv_mesh* out, hipStream_t st, const char* what) {
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        (void)hipFree(m.vertices);
+        (void)hipFree(m.indices);
+        return hip_fail(e, what);
+    }
+    *out = m;
+    return SDFV_OK;
+}
+
+// Meshers::mesh for any kind of SDF: the arguments are checked by the caller.  An SDF kind supplies two things:
+// `lattice(g, w, stream)` writes the distances of the lattice points into w.dist (or points w.dist at distances that exist: a
+// caller's lattice, which no step writes), and `attributes(vertices, n, final, stream)` everything but
+// the position of n vertices whose positions are written.  Counting, the scans, the positions of the crossing edges, the
+// triangles (mesh_kernels.h) and dual contouring's solve and quads (dual_contour_kernels.h) do not depend on the SDF.  `final` is
+// false only for dual contouring's Hermite records: crossing-edge vertices in a temporary, of which the solve reads position and
+// normal and nothing else.  The scratch is the calling thread's dense block, laid out by lay_out.
+// An SDF kind whose attributes are cheap enough to write under the positions' sparse mask may also give
+// `fused(g, w, vertices, n, stream)`: marching cubes then calls it in the place of positions + attributes (the demo tree does).
+// The lattice is `g`: any number of cells per axis (MeshGrid::launchable).
+template <typename LatticeFn, typename AttributesFn, typename FusedFn = std::nullptr_t>
+int extract_mesh(const sdfv::MeshGrid& g, uint32_t algorithm, sdfv_mesh* out, hipStream_t st, LatticeFn&& lattice,
+                 AttributesFn&& attributes, FusedFn&& fused = nullptr) {
+    const bool dual = algorithm == SDFV_MESHER_DUAL_CONTOURING_PARTICLE;
+    const size_t n_points = g.n_points(), n_cells = g.n_cells();
+    sdfv::MeshWork w{};
+    if (int rc = g_mesh_scratch.reserve(lay_out(w, nullptr, n_points, n_cells, dual), 0, 0, st)) return rc;
+    lay_out(w, g_mesh_scratch.p, n_points, n_cells, dual);
+    SDFV_HIP(lattice(g, w, st));
+    SDFV_HIP(dual ? sdfv::launch_dc_count(g, w, w.totals, st) : sdfv::launch_mesh_count(g, w, w.totals, st));
+    uint32_t n[3] = {0, 0, 0};  // marching cubes: vertices, triangles; dual contouring: Hermite records, vertices, quads
+    SDFV_HIP(hipMemcpyAsync(n, w.totals, dual ? 12 : 8, hipMemcpyDeviceToHost, st));
+    SDFV_HIP(hipStreamSynchronize(st));
+    sdfv_mesh m{};
+    m.n_vertices = dual ? n[1] : n[0];
+    m.n_indices = dual ? (size_t)n[2] * 6 : (size_t)n[1] * 3;
+    if (int rc = allocate_mesh(m)) return rc;
     hipError_t e = hipSuccess;
     void* hermite = nullptr;  // dual contouring: n[0] Hermite records, then the list of the n[1] active cells
     if (!dual) {
@@ -101,15 +181,9 @@ int extract_mesh(const sdfv::MeshGrid& g, uint32_t algorithm, sdfv_mesh* out, hi
         if (e == hipSuccess) e = attributes(m.vertices, m.n_vertices, true, st);
         if (e == hipSuccess) e = sdfv::launch_dc_quads(g, w, m.indices, st);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);  // the next extraction on this thread reuses the scratch
-    if (hermite) (void)hipFree(hermite);
-    if (e != hipSuccess) {
-        (void)hipFree(m.vertices);
-        (void)hipFree(m.indices);
-        return hip_fail(e, "mesh emit");
-    }
-    *out = m;
-    return SDFV_OK;
+    const int rc = finish_mesh(e, m, out, st, "mesh emit");
+    if (hermite) (void)hipFree(hermite);  // after finish_mesh: the stream is done with it, or has failed
+    return rc;
 }
 
 // ... over the cube every mesher of the reference takes: max_voxels_per_axis cells on each axis of the box
@@ -226,61 +300,6 @@ int sdfv_program_mesh_extract(const sdfv_program* p, const float bb_min[3], cons
 
 // ---- sparse meshing of a program: refine blocks towards the surface, then marching cubes over the surviving bricks ----
 namespace {
-thread_local MeshScratch g_sparse_scratch;  // beside g_mesh_scratch, and released with it
-
-// The scratch of one phase: the totals (256 bytes), then the block list at a FIXED offset, so that a block that has to grow
-// takes the list along with one copy, then what the phase adds.  Refinement of `n` parents: 8 n candidates; the brick phase
-// over `n` bricks: 125 n points and 64 n cells.
-struct SparseLayout {
-    size_t list = 256, a = 0, b = 0, c = 0, d = 0, e = 0, tmp = 0, need = 0, tmp_bytes = 0;
-    static size_t up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    static SparseLayout refinement(size_t n_parents) {
-        SparseLayout l;
-        const size_t cand = n_parents * 8;
-        l.a = l.list + up(cand * 4);  // cand
-        l.b = l.a + up(cand * 4);     // pos
-        l.tmp = l.b + up(cand * 4);
-        l.tmp_bytes = sdfv::mesh_scan_tmp_bytes(cand);
-        l.need = l.tmp + up(l.tmp_bytes);
-        return l;
-    }
-    static SparseLayout bricks(size_t n) {
-        SparseLayout l;
-        const size_t points = n * sdfv::kBrickPoints, cells = n * sdfv::kBrickCells;
-        l.a = l.list + up(n * 4);            // dist
-        l.b = l.a + up(points * 4);          // point_first
-        l.c = l.b + up((points + 1) * 4);    // cell_first
-        l.d = l.c + up((cells + 1) * 4);     // point_mask
-        l.e = l.d + up(points);              // neighbours
-        l.tmp = l.e + up(n * 32);
-        l.tmp_bytes = sdfv::mesh_scan_tmp_bytes(points + 1);
-        l.need = l.tmp + up(l.tmp_bytes);
-        return l;
-    }
-};
-
-// Make the calling thread's sparse scratch at least `need` bytes on the current device, keeping the first `keep` list entries.
-int sparse_scratch(size_t need, size_t keep, hipStream_t st) {
-    const int device_now = current_device();
-    MeshScratch& s = g_sparse_scratch;
-    if (s.bytes >= need && s.device == device_now) return SDFV_OK;
-    void* fresh = nullptr;
-    SDFV_HIP(hipMalloc(&fresh, need));
-    if (keep && s.p && s.device == device_now) {
-        hipError_t e = hipMemcpyAsync((char*)fresh + 256, (char*)s.p + 256, keep * 4, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            (void)hipFree(fresh);
-            return hip_fail(e, "sparse scratch copy");
-        }
-    }
-    s.release();
-    s.p = fresh;
-    s.bytes = need;
-    s.device = device_now;
-    return SDFV_OK;
-}
-
 // t = (L * r) * 1.001f for blocks of s cells (include/sdfgrid.h): f32, one rounding per step (this file is built with
 // -ffp-contract=off like the kernels)
 float sparse_threshold(const sdfv::MeshGrid& g, uint32_t s, float L) {
@@ -297,28 +316,21 @@ int extract_sparse(const sdfv_prog_op* dev_ops, uint32_t n_ops, const sdfv::Mesh
     while ((4u << s.levels) < N) ++s.levels;
     size_t scratch = 0;
     sdfv::SparseWork w{};
-    auto place = [&](const SparseLayout& l, size_t keep) {
-        if (int rc = sparse_scratch(l.need, keep, st)) return rc;
-        char* base = static_cast<char*>(g_sparse_scratch.p);
-        w.list = (uint32_t*)(base + l.list);
-        w.scan_tmp = base + l.tmp;
-        w.scan_tmp_bytes = l.tmp_bytes;
-        scratch = l.need > scratch ? l.need : scratch;
-        return (int)SDFV_OK;
+    // the block for a phase that takes `need` bytes, with the first `keep` entries of the list as they are
+    auto reserve = [&](size_t need, size_t keep) {
+        scratch = need > scratch ? need : scratch;
+        return g_sparse_scratch.reserve(need, kSparseListAt, keep * 4, st);
     };
     // ---- refinement: the root (key 0) is not tested
     uint32_t n = 1;
     for (uint32_t level = 0; level < s.levels && n; ++level) {
-        const SparseLayout l = SparseLayout::refinement(n);
-        if (int rc = place(l, level ? n : 0)) return rc;
-        char* base = static_cast<char*>(g_sparse_scratch.p);
-        w.cand = (uint32_t*)(base + l.a);
-        w.pos = (uint32_t*)(base + l.b);
+        if (int rc = reserve(lay_out_refinement(w, nullptr, n), level ? n : 0)) return rc;
+        lay_out_refinement(w, g_sparse_scratch.p, n);
         if (level == 0) SDFV_HIP(hipMemsetAsync(w.list, 0, 4, st));
         const uint32_t shift = 31u - (uint32_t)__builtin_clz(N >> (level + 1));  // children of N / 2^(level + 1) cells
-        SDFV_HIP(sdfv::launch_sparse_refine(dev_ops, n_ops, g, shift, sparse_threshold(g, 1u << shift, L), w, n, (uint32_t*)base, st));
+        SDFV_HIP(sdfv::launch_sparse_refine(dev_ops, n_ops, g, shift, sparse_threshold(g, 1u << shift, L), w, n, w.mesh.totals, st));
         s.tested[level] = n * 8u;
-        SDFV_HIP(hipMemcpyAsync(&n, base, 4, hipMemcpyDeviceToHost, st));
+        SDFV_HIP(hipMemcpyAsync(&n, w.mesh.totals, 4, hipMemcpyDeviceToHost, st));
         SDFV_HIP(hipStreamSynchronize(st));
         s.kept[level] = n;
         s.evaluations += s.tested[level];
@@ -331,40 +343,22 @@ int extract_sparse(const sdfv_prog_op* dev_ops, uint32_t n_ops, const sdfv::Mesh
             return set_error(SDFV_ERR_INVALID_ARGUMENT, "%u bricks: more than %u could overflow the 32-bit vertex and triangle counts", n,
                              0xffffffffu / (3u * sdfv::kBrickPoints));
         // ---- the brick phase
-        const SparseLayout l = SparseLayout::bricks(n);
-        if (int rc = place(l, s.levels ? n : 0)) return rc;
-        char* base = static_cast<char*>(g_sparse_scratch.p);
-        w.dist = (float*)(base + l.a);
-        w.point_first = (uint32_t*)(base + l.b);
-        w.cell_first = (uint32_t*)(base + l.c);
-        w.point_mask = (uint8_t*)(base + l.d);
-        w.neighbours = (uint32_t*)(base + l.e);
+        if (int rc = reserve(lay_out_bricks(w, nullptr, n), s.levels ? n : 0)) return rc;
+        lay_out_bricks(w, g_sparse_scratch.p, n);
         if (s.levels == 0) SDFV_HIP(hipMemsetAsync(w.list, 0, 4, st));
         SDFV_HIP(sdfv::launch_sparse_brick_lattice(dev_ops, n_ops, g, w, n, st));
         SDFV_HIP(sdfv::launch_sparse_count(g, w, n, st));
         uint32_t totals[2] = {0, 0};  // vertices, triangles: the extra last entry of each scan
-        SDFV_HIP(hipMemcpyAsync(&totals[0], w.point_first + (size_t)n * sdfv::kBrickPoints, 4, hipMemcpyDeviceToHost, st));
-        SDFV_HIP(hipMemcpyAsync(&totals[1], w.cell_first + (size_t)n * sdfv::kBrickCells, 4, hipMemcpyDeviceToHost, st));
+        SDFV_HIP(hipMemcpyAsync(&totals[0], w.mesh.point_first + (size_t)n * sdfv::kBrickPoints, 4, hipMemcpyDeviceToHost, st));
+        SDFV_HIP(hipMemcpyAsync(&totals[1], w.mesh.cell_first + (size_t)n * sdfv::kBrickCells, 4, hipMemcpyDeviceToHost, st));
         SDFV_HIP(hipStreamSynchronize(st));
         m.n_vertices = totals[0];
         m.n_indices = (size_t)totals[1] * 3;
-        if (m.n_vertices) SDFV_HIP(hipMalloc((void**)&m.vertices, m.n_vertices * sizeof(sdfv_vertex)));
-        if (m.n_indices) {
-            hipError_t e = hipMalloc((void**)&m.indices, m.n_indices * 4);
-            if (e != hipSuccess) {
-                (void)hipFree(m.vertices);
-                return hip_fail(e, "hipMalloc(indices)");
-            }
-        }
-        hipError_t e = sdfv::launch_sparse_positions(g, w, n, m.vertices, m.n_vertices, st);
+        if (int rc = allocate_mesh(m)) return rc;
+        hipError_t e = sdfv::launch_sparse_positions(g, w, n, m.vertices, m.n_vertices, st);  // marching cubes' chain, as extract_mesh
         if (e == hipSuccess) e = sdfv::launch_program_vertex_normals(dev_ops, n_ops, m.vertices, m.n_vertices, materials, st);
         if (e == hipSuccess) e = sdfv::launch_sparse_triangles(g, w, n, m.indices, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);  // the next extraction on this thread reuses the scratch
-        if (e != hipSuccess) {
-            (void)hipFree(m.vertices);
-            (void)hipFree(m.indices);
-            return hip_fail(e, "sparse mesh emit");
-        }
+        if (int rc = finish_mesh(e, m, out, st, "sparse mesh emit")) return rc;
     }
     *out = m;
     if (stats) {

@@ -21,7 +21,7 @@ struct MeshGrid {
     bool launchable() const { return n_cells() != 0 && n_points() <= 0xffffffffull; }
 };
 
-struct MeshWork {           // device scratch of one extraction, sized by mesh_work_bytes()
+struct MeshWork {           // device scratch of one extraction: sub-blocks of the calling thread's block (api_points_mesh.hip)
     float* dist;            // [points] ScalarSource at every lattice point
     uint32_t* point_first;  // [points] first vertex id of the point's edges (exclusive scan of the edge counts)
     uint8_t* point_mask;    // [points] bit a: the edge towards +axis a crosses the surface
@@ -30,6 +30,7 @@ struct MeshWork {           // device scratch of one extraction, sized by mesh_w
     uint32_t* quad_first;   // [points] dual contouring only (NULL otherwise): first quad of the point's interior crossing edges
     void* scan_tmp;
     size_t scan_tmp_bytes;
+    uint32_t* totals;       // [3] the counts the host reads back to allocate the output
 };
 
 size_t mesh_scan_tmp_bytes(size_t n);
@@ -42,7 +43,7 @@ hipError_t launch_mesh_lattice(const sdfv_demo_params& prm, uint32_t sdf_id, con
 // 2. edge masks, triangle counts, both scans.  Leaves the totals in totals_dev[0] (vertices), [1] (triangles).
 hipError_t launch_mesh_count(const MeshGrid& g, const MeshWork& w, uint32_t* totals_dev, hipStream_t stream);
 //    Its two parts, for an extractor that counts something else per cell (dual_contour_kernels.hip): edge masks + the point scan
-//    (checks the grid too), and the in-place exclusive scan of n counts through w.scan_tmp.
+//    (checks the grid too), and the in-place exclusive scan of n counts through w.scan_tmp (the brick route's scans too).
 hipError_t launch_mesh_edge_masks(const MeshGrid& g, const MeshWork& w, hipStream_t stream);
 hipError_t mesh_exclusive_scan(const MeshWork& w, uint32_t* counts, size_t n, hipStream_t stream);
 // 3. (the host reads the totals and allocates)

@@ -1,8 +1,9 @@
 // mesh_lattice.h -- the lattice arithmetic the mesh kernels share on the device (mesh_kernels.hip: the demo tree and every SDF-free
-// step; program_mesh_kernels.hip: SDF programs; dual_contour_kernels.hip): which point or cell a thread has, where a lattice point
-// lies, where the vertex of a crossing edge lies and which vertex record it is.  One statement of each, so that the extractors
-// cannot drift apart: the translation units are built with -ffp-contract=off, every float step below is one rounded f32
-// operation, every division is a 32-bit one.
+// step; program_mesh_kernels.hip: SDF programs; dual_contour_kernels.hip; sparse_mesh_kernels.hip: bricks): which point or cell a
+// thread has, where a lattice point lies, which side of the surface a distance is on, the cube case of a cell, which corner of a
+// cell owns a table edge, where the vertex of a crossing edge lies and which vertex record it is.  One statement of each, so that
+// the extractors cannot drift apart (the steps built from these, over either point layout, are mesh_steps.h's): the translation
+// units are built with -ffp-contract=off, every float step below is one rounded f32 operation, every division is a 32-bit one.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -38,16 +39,48 @@ struct Lattice {
     }
 };
 
-// The vertex record of edge e of the cell whose lowest corner is lattice point `origin`, e = 4 * axis + u + 2 * v (the
-// marching-cubes table's numbering): the edge along `axis` that starts at the corner offset by u along the lower and v along the
-// higher of the two other axes.  That corner owns the edge; its records come in axis order from point_first[corner] on.
+__device__ __forceinline__ bool inside(float d) { return d < 0.0f; }  // Signed: negative inside
+
+// The cube case of the cell whose lowest corner's distance is *corner, in an array with the strides sy and sz towards +y and +z
+// (1 towards +x): corner bit = x | y << 1 | z << 2.
+template <typename Stride>
+__device__ __forceinline__ uint32_t cube_case(const float* __restrict__ corner, Stride sy, Stride sz) {
+    uint32_t c = 0;
+    for (uint32_t q = 0; q < 8; ++q)
+        if (inside(corner[(q & 1) + ((q >> 1) & 1) * sy + ((q >> 2) & 1) * sz])) c |= 1u << q;
+    return c;
+}
+
+// Edge e of a cell, e = 4 * axis + u + 2 * v (the marching-cubes table's numbering): the edge along `axis` that starts at the
+// corner offset by u along the lower (o0) and v along the higher (o1) of the two other axes.  That corner owns the edge.
+// dx, dy, dz: the same offset per axis, each 0 or 1.  (Scalars: e is a run-time value in the triangle kernels, and an array
+// indexed by it would live in scratch.)
+struct CellEdge {
+    uint32_t axis, u, v, dx, dy, dz;
+};
+__device__ __forceinline__ CellEdge cell_edge(int e) {
+    const uint32_t a = (uint32_t)e >> 2, u = (uint32_t)e & 1u, v = ((uint32_t)e >> 1) & 1u;
+    // axis 0: (u, v) along (y, z); axis 1: along (x, z); axis 2: along (x, y)
+    return CellEdge{a, u, v, a != 0u ? u : 0u, a == 0u ? u : (a == 2u ? v : 0u), a != 2u ? v : 0u};
+}
+// the two other axes of an axis, increasing
+__device__ __forceinline__ int lower_other(uint32_t axis) { return axis == 0u ? 1 : 0; }
+__device__ __forceinline__ int higher_other(uint32_t axis) { return axis == 2u ? 1 : 2; }
+
+// The vertex record of the edge towards +axis of the point in slot `owner`: a point's records come in axis order from
+// point_first[owner] on.
+__device__ __forceinline__ uint32_t owner_record(size_t owner, uint32_t axis, const uint8_t* __restrict__ mask,
+                                                 const uint32_t* __restrict__ point_first) {
+    return point_first[owner] + __popc((uint32_t)mask[owner] & ((1u << axis) - 1u));
+}
+
+// The vertex record of edge e of the cell whose lowest corner is lattice point `origin` of the dense lattice.
 __device__ __forceinline__ uint32_t edge_record(const Lattice& L, size_t origin, int e, const uint8_t* __restrict__ mask,
                                                 const uint32_t* __restrict__ point_first) {
     const size_t stride[3] = {1, L.nx, (size_t)L.nx * L.ny};
-    const int a = e >> 2, s = e & 3;
-    const int o0 = a == 0 ? 1 : 0, o1 = a == 2 ? 1 : 2;  // the two other axes, increasing
-    const size_t owner = origin + (s & 1) * stride[o0] + (s >> 1) * stride[o1];
-    return point_first[owner] + __popc((uint32_t)mask[owner] & ((1u << a) - 1u));
+    const CellEdge c = cell_edge(e);
+    const size_t owner = origin + c.u * stride[lower_other(c.axis)] + c.v * stride[higher_other(c.axis)];
+    return owner_record(owner, c.axis, mask, point_first);
 }
 
 __device__ __forceinline__ float unit_coord(uint32_t i, uint32_t cells) { return (float)i / (float)cells; }

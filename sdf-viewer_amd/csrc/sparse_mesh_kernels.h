@@ -1,7 +1,7 @@
 // sparse_mesh_kernels.h -- launch interface of sparse marching cubes over SDF programs (see sparse_mesh_kernels.hip;
 // include/sdfgrid.h, "SDF programs: sparse meshing"): the block refinement, the brick lattice, and counting, positions and
 // triangles over bricks.  The vertex attributes are program_mesh_kernels.h's launch_program_vertex_normals, the scans
-// mesh_kernels.h's mesh_exclusive_scan.
+// mesh_kernels.h's mesh_exclusive_scan over the MeshWork a SparseWork holds.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,13 +21,12 @@ struct SparseWork {
     uint32_t* list;         // the blocks of the current level, [n]; after the last level: the bricks
     uint32_t* cand;         // refinement: [8 * n] children, key | kept << 31
     uint32_t* pos;          // refinement: [8 * n] kept (0 / 1), then its exclusive scan
-    float* dist;            // [125 * bricks] brick-major, x fastest within a brick
-    uint32_t* point_first;  // [125 * bricks + 1] first vertex id of the point's owned edges; the last entry is the total
-    uint32_t* cell_first;   // [64 * bricks + 1] first triangle of the cell; the last entry is the total
-    uint8_t* point_mask;    // [125 * bricks] bit a: the brick owns the edge towards +axis a and it crosses
     uint32_t* neighbours;   // [8 * bricks] index of the brick at offset (dir & 1, dir >> 1 & 1, dir >> 2), or 0xffffffff
-    void* scan_tmp;
-    size_t scan_tmp_bytes;
+    // What the brick phase has in common with a dense extraction, brick-major (x fastest within a brick):
+    //   dist [125 * bricks]; point_mask [125 * bricks], bit a: the brick owns the edge towards +axis a and it crosses;
+    //   point_first [125 * bricks + 1] and cell_first [64 * bricks + 1], the last entry of each the total.
+    // scan_tmp serves both phases; totals is one word, the survivors of a refinement level; quad_first stays NULL.
+    MeshWork mesh;
 };
 
 // g: `cells` on every axis, a power of two; ops: the DEVICE copy of the validated program.

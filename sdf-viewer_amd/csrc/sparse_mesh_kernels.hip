@@ -8,8 +8,10 @@
 //    header's.  One launch per level; the host reads one count per level.
 //  * sdfprog_sparse_bricks: thread t has lattice point t % 125 of brick t / 125: all 5^3 points of a brick, its upper faces
 //    included, because a pruned neighbour would leave them unknown.  Distances brick-major.
-//  * sparse_brick_edges, sparse_brick_neighbours, sparse_brick_cells, sparse_brick_positions, sparse_brick_triangles: the
-//    SDF-free steps of mesh_kernels.hip over bricks.  A brick owns the points with local index < 4 per axis (<= 4 where it is
+//  * sparse_brick_edges, sparse_brick_positions, sparse_brick_triangles: the SDF-free steps of mesh_steps.h (edge_mask_step,
+//    edge_vertex_step, triangle_step: the very code mesh_kernels.hip runs) over BrickLayout, which says what thread t's point
+//    is in the brick-major arrays and which edges it owns.  sparse_brick_neighbours, sparse_brick_cells: the brick route's own.
+//    A brick owns the points with local index < 4 per axis (<= 4 where it is
 //    the box's last brick), and the edges that start there; a cell on a brick's upper faces reads the records of up to seven
 //    neighbours, which sparse_brick_neighbours has looked up once per brick by binary search in the brick list (sorted by Morton
 //    key; a directory of (cells / 4)^3 words would be 4 GiB at 4096 cells).  A cell whose crossing edge has no owner among the
@@ -19,16 +21,12 @@
 #include "sparse_mesh_kernels.h"
 
 #include "kernel_common.h"
-#include "mesh_lattice.h"
+#include "mesh_steps.h"
 #include "program_eval.h"
 
 namespace sdfv {
 
 namespace {
-
-#define SDFV_MC_TABLE __constant__ const
-#include "mc_table.inc"
-#undef SDFV_MC_TABLE
 
 constexpr uint32_t kKept = 0x80000000u;
 constexpr uint32_t kNoBrick = 0xffffffffu;
@@ -51,8 +49,6 @@ __device__ __forceinline__ uint32_t spread3(uint32_t x) {
     return x;
 }
 
-__device__ __forceinline__ bool inside(float d) { return d < 0.0f; }  // Signed: negative inside
-
 // thread t of a brick-major array of 125 per brick -> the brick and the local point (x fastest)
 __device__ __forceinline__ void unbrick(uint32_t t, uint32_t& b, uint32_t& lx, uint32_t& ly, uint32_t& lz) {
     b = t / kBrickPoints;
@@ -73,27 +69,44 @@ __device__ __forceinline__ uint32_t find_brick(const uint32_t* __restrict__ bric
     return lo < n && bricks[lo] == key ? lo : kNoBrick;
 }
 
-// The cube case of cell (cx, cy, cz) of a brick whose distances start at d: corner bit = x | y << 1 | z << 2.
+// Thread t's point of the brick-major arrays (mesh_steps.h).  A brick owns the points with local index < 4 per axis (<= 4 where
+// it is the box's last brick on that axis), and of an owned point the edges towards a local index <= 4: the +axis neighbour of
+// such a point is one of the brick's own 125.  last = bricks per axis - 1.
+struct BrickLayout {
+    const uint32_t* __restrict__ bricks;
+    uint32_t last;
+    uint32_t stride[3] = {1u, 5u, 25u};
+    __device__ __forceinline__ LatticePoint point(uint32_t t) const {
+        uint32_t b, lx, ly, lz;
+        unbrick(t, b, lx, ly, lz);
+        const uint32_t key = bricks[b];
+        const bool owned = (lx < 4u || gather3(key) == last) && (ly < 4u || gather3(key >> 1) == last) &&
+                           (lz < 4u || gather3(key >> 2) == last);
+        LatticePoint p;
+        p.idx[0] = gather3(key) * 4u + lx;
+        p.idx[1] = gather3(key >> 1) * 4u + ly;
+        p.idx[2] = gather3(key >> 2) * 4u + lz;
+        p.edges = owned ? (lx < 4u ? 1u : 0u) | (ly < 4u ? 2u : 0u) | (lz < 4u ? 4u : 0u) : 0u;
+        return p;
+    }
+};
+
+// The cube case of cell (cx, cy, cz) of a brick whose distances start at d.
 __device__ __forceinline__ uint32_t brick_cell_case(const float* __restrict__ d, uint32_t cx, uint32_t cy, uint32_t cz) {
-    const float* o = d + (cz * 5u + cy) * 5u + cx;
-    uint32_t c = 0;
-    for (uint32_t corner = 0; corner < 8; ++corner)
-        if (inside(o[(corner & 1) + ((corner >> 1) & 1) * 5u + ((corner >> 2) & 1) * 25u])) c |= 1u << corner;
-    return c;
+    return cube_case(d + (cz * 5u + cy) * 5u + cx, 5u, 25u);
 }
 
-// Does edge e (= 4 * axis + u + 2 * v, the table's numbering) of a cell with cube case cs cross?
+// Does edge e of a cell with cube case cs cross?  From the corners' sides, not from the edge masks as cell_edges of
+// dual_contour_kernels.hip has it: a brick's masks hold its OWN edges only, and those of an upper-face cell are other bricks'.
 __device__ __forceinline__ bool edge_crosses(uint32_t cs, int e) {
-    const int a = e >> 2, s = e & 3;
-    const int o0 = a == 0 ? 1 : 0, o1 = a == 2 ? 1 : 2;
-    const uint32_t start = ((s & 1) << o0) | ((s >> 1) << o1);
-    return (((cs >> start) ^ (cs >> (start | (1u << a)))) & 1u) != 0;
+    const CellEdge c = cell_edge(e);
+    const uint32_t start = c.dx | c.dy << 1 | c.dz << 2;
+    return (((cs >> start) ^ (cs >> (start | (1u << c.axis)))) & 1u) != 0;
 }
 
 // Where the record of edge e of cell (cx, cy, cz) of brick `self` (whose key the caller has loaded) is kept: the slot
-// of its owning point in the brick-major arrays, or kNoBrick when the owner is no brick.  The edge starts at local point c + (u, v)
-// on the two other axes; a local index of 4 belongs to the next brick on that axis unless this one is the box's last.
-// (Scalars throughout: e is a run-time value in the triangle kernel, and an array indexed by it would live in scratch.)
+// of its owning point in the brick-major arrays, or kNoBrick when the owner is no brick.  The edge starts at the cell's corner
+// cell_edge(e) names; a local index of 4 belongs to the next brick on that axis unless this one is the box's last.
 __device__ __forceinline__ bool next_brick(uint32_t& l, uint32_t& b, uint32_t last) {
     if (l != 4u || b >= last) return false;
     l = 0;
@@ -102,10 +115,8 @@ __device__ __forceinline__ bool next_brick(uint32_t& l, uint32_t& b, uint32_t la
 }
 __device__ __forceinline__ uint32_t edge_owner_slot(const uint32_t* __restrict__ neighbours, uint32_t last, uint32_t self,
                                                     uint32_t key, uint32_t cx, uint32_t cy, uint32_t cz, int e) {
-    const uint32_t a = (uint32_t)e >> 2, u = (uint32_t)e & 1u, v = ((uint32_t)e >> 1) & 1u;
-    uint32_t lx = cx + (a != 0u ? u : 0u);  // axis 0: (u, v) along (y, z); axis 1: along (x, z); axis 2: along (x, y)
-    uint32_t ly = cy + (a == 0u ? u : (a == 2u ? v : 0u));
-    uint32_t lz = cz + (a != 2u ? v : 0u);
+    const CellEdge c = cell_edge(e);
+    uint32_t lx = cx + c.dx, ly = cy + c.dy, lz = cz + c.dz;
     uint32_t bx = gather3(key), by = gather3(key >> 1), bz = gather3(key >> 2);
     const bool fx = next_brick(lx, bx, last), fy = next_brick(ly, by, last), fz = next_brick(lz, bz, last);
     uint32_t owner = self;
@@ -171,20 +182,7 @@ __global__ __launch_bounds__(kBlock) void sparse_brick_edges(uint32_t last, cons
         count[n] = 0;
         return;
     }
-    uint32_t b, lx, ly, lz;
-    unbrick(t, b, lx, ly, lz);
-    const uint32_t key = bricks[b];
-    const bool owned = (lx < 4u || gather3(key) == last) && (ly < 4u || gather3(key >> 1) == last) &&
-                       (lz < 4u || gather3(key >> 2) == last);
-    uint32_t m = 0;
-    if (owned) {  // an owned point's +axis neighbour (local index < 4 on that axis) is one of the brick's own 125
-        const bool in0 = inside(dist[t]);
-        if (lx < 4u && inside(dist[t + 1]) != in0) m |= 1u;
-        if (ly < 4u && inside(dist[t + 5]) != in0) m |= 2u;
-        if (lz < 4u && inside(dist[t + 25]) != in0) m |= 4u;
-    }
-    mask[t] = (uint8_t)m;
-    count[t] = __popc(m);
+    edge_mask_step(BrickLayout{bricks, last}, t, dist, mask, count);
 }
 
 // The up to seven bricks whose points a brick's upper-face cells refer to: neighbours[8 * b + dir] = index of the brick at
@@ -234,21 +232,7 @@ __global__ __launch_bounds__(kBlock) void sparse_brick_positions(MeshGrid g, con
                                                                  const uint32_t* __restrict__ first, float* __restrict__ vertices) {
     const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= n) return;
-    const uint32_t m = mask[t];
-    if (m == 0) return;
-    uint32_t b, lx, ly, lz;
-    unbrick(t, b, lx, ly, lz);
-    const uint32_t key = bricks[b];
-    const uint32_t idx[3] = {gather3(key) * 4u + lx, gather3(key >> 1) * 4u + ly, gather3(key >> 2) * 4u + lz};
-    const uint32_t stride[3] = {1u, 5u, 25u};
-    const float d0 = dist[t];
-    uint32_t id = first[t];
-    for (int a = 0; a < 3; ++a) {
-        if (!(m & (1u << a))) continue;
-        float* o = vertices + (size_t)id * 12;
-        edge_position(g, idx, a, d0, dist[t + stride[a]], o[0], o[1], o[2]);
-        ++id;
-    }
+    edge_vertex_step(g, BrickLayout{bricks, g.cells[0] / 4u - 1u}, t, dist, mask, first, StorePosition{vertices});
 }
 
 __global__ __launch_bounds__(kBlock) void sparse_brick_triangles(uint32_t last, const uint32_t* __restrict__ bricks,
@@ -266,23 +250,15 @@ __global__ __launch_bounds__(kBlock) void sparse_brick_triangles(uint32_t last, 
     const uint32_t cx = t & 3u, cy = (t >> 2) & 3u, cz = (t >> 4) & 3u;
     const uint32_t cs = brick_cell_case(dist + (size_t)b * kBrickPoints, cx, cy, cz);
     const uint32_t key = bricks[b];
-    uint32_t* out = indices + (size_t)begin * 3;
-    for (uint32_t q = 0; q < n_tri * 3; ++q) {
-        const int e = kMcTriEdges[cs][q];
+    triangle_step(cs, n_tri, indices + (size_t)begin * 3, [&](int e) {
         const uint32_t slot = edge_owner_slot(neighbours, last, b, key, cx, cy, cz, e);  // a brick's: sparse_brick_cells has looked
-        out[q] = slot == kNoBrick ? 0u : point_first[slot] + __popc((uint32_t)mask[slot] & ((1u << (e >> 2)) - 1u));
-    }
+        return slot == kNoBrick ? 0u : owner_record(slot, (uint32_t)e >> 2, mask, point_first);
+    });
 }
 
 }  // extern "C"
 
 namespace {
-MeshWork scan_work(const SparseWork& w) {
-    MeshWork m{};
-    m.scan_tmp = w.scan_tmp;
-    m.scan_tmp_bytes = w.scan_tmp_bytes;
-    return m;
-}
 bool sparse_grid(const MeshGrid& g) {  // one power of two, 4 .. 4096, on every axis
     const uint32_t n = g.cells[0];
     return n >= 4 && n <= 4096 && (n & (n - 1)) == 0 && g.cells[1] == n && g.cells[2] == n;
@@ -296,7 +272,7 @@ hipError_t launch_sparse_refine(const sdfv_prog_op* ops, uint32_t n_ops, const M
     const uint32_t n = n_parents * 8u;
     hipLaunchKernelGGL(sdfprog_sparse_refine, dim3(blocks_for(n)), dim3(kBlock), 0, stream, ops, n_ops, g, w.list, n, shift,
                        threshold, w.cand, w.pos);
-    if (hipError_t e = mesh_exclusive_scan(scan_work(w), w.pos, n, stream); e != hipSuccess) return e;
+    if (hipError_t e = mesh_exclusive_scan(w.mesh, w.pos, n, stream); e != hipSuccess) return e;
     hipLaunchKernelGGL(sparse_compact, dim3(blocks_for(n)), dim3(kBlock), 0, stream, w.cand, w.pos, n, w.list, kept_dev);
     return hipGetLastError();
 }
@@ -305,7 +281,7 @@ hipError_t launch_sparse_brick_lattice(const sdfv_prog_op* ops, uint32_t n_ops, 
                                        uint32_t n_bricks, hipStream_t stream) {
     if (!sparse_grid(g) || n_bricks == 0 || (uint64_t)n_bricks * kBrickPoints >= 0xffffffffull) return hipErrorInvalidValue;
     const uint32_t n = n_bricks * kBrickPoints;
-    hipLaunchKernelGGL(sdfprog_sparse_bricks, dim3(blocks_for(n)), dim3(kBlock), 0, stream, ops, n_ops, g, w.list, n, w.dist);
+    hipLaunchKernelGGL(sdfprog_sparse_bricks, dim3(blocks_for(n)), dim3(kBlock), 0, stream, ops, n_ops, g, w.list, n, w.mesh.dist);
     return hipGetLastError();
 }
 
@@ -313,13 +289,13 @@ hipError_t launch_sparse_count(const MeshGrid& g, const SparseWork& w, uint32_t 
     if (!sparse_grid(g) || n_bricks == 0 || (uint64_t)n_bricks * kBrickPoints >= 0xffffffffull) return hipErrorInvalidValue;
     const uint32_t last = g.cells[0] / 4u - 1u, n_points = n_bricks * kBrickPoints, n_cells = n_bricks * kBrickCells;
     hipLaunchKernelGGL(sparse_brick_edges, dim3(blocks_for((uint64_t)n_points + 1)), dim3(kBlock), 0, stream, last, w.list, n_points,
-                       w.dist, w.point_mask, w.point_first);
-    if (hipError_t e = mesh_exclusive_scan(scan_work(w), w.point_first, (size_t)n_points + 1, stream); e != hipSuccess) return e;
+                       w.mesh.dist, w.mesh.point_mask, w.mesh.point_first);
+    if (hipError_t e = mesh_exclusive_scan(w.mesh, w.mesh.point_first, (size_t)n_points + 1, stream); e != hipSuccess) return e;
     hipLaunchKernelGGL(sparse_brick_neighbours, dim3(blocks_for((uint64_t)n_bricks * 8)), dim3(kBlock), 0, stream, last, w.list,
                        n_bricks, w.neighbours);
     hipLaunchKernelGGL(sparse_brick_cells, dim3(blocks_for((uint64_t)n_cells + 1)), dim3(kBlock), 0, stream, last, w.list, n_bricks,
-                       w.neighbours, w.dist, w.cell_first);
-    return mesh_exclusive_scan(scan_work(w), w.cell_first, (size_t)n_cells + 1, stream);
+                       w.neighbours, w.mesh.dist, w.mesh.cell_first);
+    return mesh_exclusive_scan(w.mesh, w.mesh.cell_first, (size_t)n_cells + 1, stream);
 }
 
 hipError_t launch_sparse_positions(const MeshGrid& g, const SparseWork& w, uint32_t n_bricks, sdfv_vertex* vertices, size_t n,
@@ -327,8 +303,8 @@ hipError_t launch_sparse_positions(const MeshGrid& g, const SparseWork& w, uint3
     if (n == 0) return hipSuccess;
     if (!vertices || n_bricks == 0) return hipErrorInvalidValue;
     const uint32_t n_points = n_bricks * kBrickPoints;
-    hipLaunchKernelGGL(sparse_brick_positions, dim3(blocks_for(n_points)), dim3(kBlock), 0, stream, g, w.list, n_points, w.dist,
-                       w.point_mask, w.point_first, reinterpret_cast<float*>(vertices));
+    hipLaunchKernelGGL(sparse_brick_positions, dim3(blocks_for(n_points)), dim3(kBlock), 0, stream, g, w.list, n_points, w.mesh.dist,
+                       w.mesh.point_mask, w.mesh.point_first, reinterpret_cast<float*>(vertices));
     return hipGetLastError();
 }
 
@@ -336,7 +312,7 @@ hipError_t launch_sparse_triangles(const MeshGrid& g, const SparseWork& w, uint3
                                    hipStream_t stream) {
     if (indices && n_bricks)
         hipLaunchKernelGGL(sparse_brick_triangles, dim3(blocks_for((uint64_t)n_bricks * kBrickCells)), dim3(kBlock), 0, stream,
-                           g.cells[0] / 4u - 1u, w.list, n_bricks, w.neighbours, w.dist, w.point_mask, w.point_first, w.cell_first,
+                           g.cells[0] / 4u - 1u, w.list, n_bricks, w.neighbours, w.mesh.dist, w.mesh.point_mask, w.mesh.point_first, w.mesh.cell_first,
                            indices);
     return hipGetLastError();
 }
