@@ -11,9 +11,9 @@ DUAL = MR.DUAL
 bits = MR.bits
 
 
-def extract(d, bb, algorithm=0):
+def extract(d, bb, algorithm=0, zeros_ok=False):
     """What sdfv_lattice_mesh_extract leaves for the lattice d [k, j, i] over bb -> mesh_ref.extract's (vertices, indices, info)."""
-    return MR.extract(d, bb, algorithm, lambda p: MR.lattice_normals(d, bb, p))
+    return MR.extract(d, bb, algorithm, lambda p: MR.lattice_normals(d, bb, p), zeros_ok=zeros_ok)
 
 
 def sphere_lattice(n, bb, radius=0.6):

@@ -302,14 +302,62 @@ def evaluate(scene, points):
     return r.d, 2.0 * r.e, table[r.mat], r.decided
 
 
+# ---- what the mesh statements need beside the distance (tests/mesh_geometry.py) ----
+def lipschitz(scene):
+    """The Lipschitz constant of the scene's distance: 1 through every node (placements are rigid, a scale divides the point and
+    multiplies the distance, min, max, their smooth forms, |.| and a constant offset keep it), max(1, |n|) for a plane."""
+    if isinstance(scene, Prim):
+        return max(1.0, float(np.linalg.norm(scene.params[:3]))) if scene.kind == "plane" else 1.0
+    if isinstance(scene, Comb):
+        return max(lipschitz(scene.a), lipschitz(scene.b))
+    return lipschitz(scene.child)
+
+
+TETRA = np.array([[1.0, -1.0, -1.0], [-1.0, 1.0, -1.0], [-1.0, -1.0, 1.0], [1.0, 1.0, 1.0]])
+
+
+def tetra_normal(scene, points, eps=0.001):
+    """normal_default_impl as a definition: v = sum_i k_i d(p + k_i e) over the four tetrahedral taps k_i, in float64, the taps at
+    the positions f32 arithmetic gives them (p.x + e, p.x + -1.0f * e, each one rounded sum); n = v / |v|.
+    -> (n [m, 3] float64, tol_sin [m], decided [m]).  tol_sin bounds the sine of the angle between n and the f32 result: with B
+    the evaluator's bound at the taps (the largest of the four), U = 2^-24,
+      E = 4 sqrt(3) (B + sqrt(3) U (|p|_inf + e))  +  12 sqrt(3) U (|d(p)| + B + sqrt(3) e)
+    (the taps' own errors with their signs, |k_i| = sqrt(3); the three f32 additions per component of terms that are at most
+    |d(p)| + B + sqrt(3) e: the derivation of test_program_march_cpu.py's sphere test without its curvature term, since the taps
+    ARE the definition here), tol_sin = E / |v|.  decided iff tol_sin < 0.05."""
+    p = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+    e = np.float32(eps)
+    me = np.float32(-1.0) * e
+    v, worst = np.zeros((len(p), 3)), np.zeros(len(p))
+    for k in TETRA:
+        tap = np.stack([p[:, a] + (e if k[a] > 0 else me) for a in range(3)], axis=1)      # float32 + float32: one rounding
+        d, bound, _, _ = evaluate(scene, tap)
+        v += k[None, :] * d[:, None]
+        worst = np.maximum(worst, bound)
+    d0 = evaluate(scene, p)[0]
+    length = np.linalg.norm(v, axis=1)
+    r3 = np.sqrt(3.0)
+    E = 4.0 * r3 * (worst + r3 * U * (np.abs(p.astype(np.float64)).max(axis=1) + float(e))) + \
+        12.0 * r3 * U * (np.abs(d0) + worst + r3 * float(e))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tol = np.where(length > 0.0, E / length, np.inf)
+        n = np.where(length[:, None] > 0.0, v / length[:, None], 0.0)
+    return n, tol, tol < 0.05
+
+
 # ---- points whose distance is known by construction ----
 def _unit(v):
     return v / np.linalg.norm(v, axis=1, keepdims=True)
 
 
-def known_points(prim, rng, n):
+def known_points(prim, rng, n, with_normals=False):
     """-> {feature: (points [n, 3] float64, distance [n] float64, lipschitz)}: surface point q + t * unit outward normal, t within
-    the primitive's reach, so that the distance there is t (for the plane: |n| t, and the field's Lipschitz constant is |n|)."""
+    the primitive's reach, so that the distance there is t (for the plane: |n| t, and the field's Lipschitz constant is |n|).
+    with_normals: each entry also carries (unit outward normal [n, 3], margin [n], rho [n]): the direction the point was offset
+    along, how far the point lies from where ANOTHER piece of the primitive's surface becomes the nearest one (a ball of that
+    radius sees one smooth piece only), and the smallest radius of curvature of the level set through the point (inf: flat)."""
+    if with_normals:
+        return _known_points_with_normals(prim, rng, n)
     kind, a = prim.kind, prim.params
     sgn = lambda shape: rng.choice(np.array([-1.0, 1.0]), shape)   # noqa: E731
     out = {}
@@ -394,6 +442,111 @@ def known_points(prim, rng, n):
         t = rng.uniform(-1.5, 1.5, n)
         t[:: 16] = 0.0
         out["plane"] = (q + t[:, None] * (nrm / ln)[None, :], ln * t, ln)
+    else:
+        raise ValueError(kind)
+    return out
+
+
+def _known_points_with_normals(prim, rng, n):
+    """known_points' constructions once more, keeping what each point was built from: q on the surface, the unit outward normal
+    m there, p = q + t m.  -> {feature: (points, distance, lipschitz, normal, margin, rho)}"""
+    kind, a = prim.kind, prim.params
+    sgn = lambda shape: rng.choice(np.array([-1.0, 1.0]), shape)   # noqa: E731
+    rows, inf = np.arange(n), np.full(n, np.inf)
+    out = {}
+
+    def offsets(inward, outward=0.5):
+        t = np.where(rng.random(n) < 0.5, rng.uniform(0.0, outward, n), -rng.uniform(0.0, 0.9 * inward, n) if inward > 0 else 0.0)
+        t[:: 16] = 0.0
+        return t
+
+    def axis_normal(ax, s):
+        m = np.zeros((n, 3))
+        m[rows, ax] = s
+        return m
+
+    if kind == "sphere":
+        m = _unit(rng.normal(size=(n, 3)))
+        t = offsets(a[0])
+        out["surface"] = (m * (a[0] + t)[:, None], t, 1.0, m, a[0] + t, a[0] + t)
+    elif kind == "cube":
+        t = offsets(a[0])
+        p = rng.uniform(-1.0, 1.0, (n, 3)) * (a[0] + t)[:, None]
+        ax, s = rng.integers(0, 3, n), sgn(n)
+        p[rows, ax] = s * (a[0] + t)
+        others = np.abs(p).copy()
+        others[rows, ax] = 0.0
+        out["face"] = (p, t, 1.0, axis_normal(ax, s), ((a[0] + t) - others.max(axis=1)) / np.sqrt(2.0), inf)
+    elif kind == "box":
+        h = np.array(a[:3])
+        t = offsets(h.min())
+        depth = np.maximum(-t, 0.0)
+        p = rng.uniform(-1.0, 1.0, (n, 3)) * (h[None, :] - depth[:, None])
+        ax, s = rng.integers(0, 3, n), sgn(n)
+        p[rows, ax] = s * (h[ax] + t)
+        room = h[None, :] - np.abs(p) - depth[:, None]          # per other axis: how far from where that face (or its edge) is as near
+        room[rows, ax] = np.inf
+        out["face"] = (p, t, 1.0, axis_normal(ax, s), room.min(axis=1) / np.sqrt(2.0), inf)
+        t = offsets(0.0)
+        p = rng.uniform(-1.0, 1.0, (n, 3)) * h
+        ax = rng.integers(0, 3, n)
+        phi = rng.uniform(0.0, np.pi / 2, n)
+        m = np.zeros((n, 3))
+        for k, w in ((1, np.cos(phi)), (2, np.sin(phi))):
+            j, s = (ax + k) % 3, sgn(n)
+            p[rows, j] = s * (h[j] + t * w)
+            m[rows, j] = s * w
+        margin = np.minimum(h[ax] - np.abs(p[rows, ax]), t * np.minimum(np.cos(phi), np.sin(phi)))
+        out["edge"] = (p, t, 1.0, m, margin, t)
+        t = offsets(0.0)
+        dd, s = np.abs(_unit(rng.normal(size=(n, 3)))), sgn((n, 3))
+        out["corner"] = (s * (h[None, :] + t[:, None] * dd), t, 1.0, s * dd, (t[:, None] * dd).min(axis=1), t)
+    elif kind == "cylinder":
+        r, hh = a[0], a[1]
+        th = rng.uniform(0.0, 2 * np.pi, n)
+        radial = np.stack([np.cos(th), np.sin(th), np.zeros(n)], axis=1)
+        t = offsets(min(r, hh))
+        depth = np.maximum(-t, 0.0)
+        z = rng.uniform(-1.0, 1.0, n) * (hh - depth)
+        p = radial * (r + t)[:, None]
+        p[:, 2] = z
+        out["side"] = (p, t, 1.0, radial, np.minimum((hh - np.abs(z) - depth) / np.sqrt(2.0), r + t), r + t)
+        t = offsets(min(r, hh))
+        depth = np.maximum(-t, 0.0)
+        rho_xy = np.sqrt(rng.random(n)) * (r - depth)
+        s = sgn(n)
+        p = radial * rho_xy[:, None]
+        p[:, 2] = s * (hh + t)
+        out["cap"] = (p, t, 1.0, axis_normal(np.full(n, 2), s), (r - rho_xy - depth) / np.sqrt(2.0), inf)
+        t = offsets(0.0)
+        phi = rng.uniform(0.0, np.pi / 2, n)
+        s = sgn(n)
+        p = radial * (r + t * np.cos(phi))[:, None]
+        p[:, 2] = s * (hh + t * np.sin(phi))
+        m = radial * np.cos(phi)[:, None]
+        m[:, 2] = s * np.sin(phi)
+        out["rim"] = (p, t, 1.0, m, t * np.minimum(np.cos(phi), np.sin(phi)), t)
+    elif kind == "torus":
+        R, r = a[0], a[1]
+        th = rng.uniform(0.0, 2 * np.pi, n)
+        radial = np.stack([np.cos(th), np.sin(th), np.zeros(n)], axis=1)
+        phi = rng.uniform(0.0, 2 * np.pi, n)
+        c = np.cos(phi)
+        t = np.where(rng.random(n) < 0.5, rng.uniform(0.0, 0.5, n) * np.where(c < 0.0, 0.5 * (R - r), 1.0), -rng.uniform(0.0, 0.9 * r, n))
+        t[:: 16] = 0.0
+        w = r + t
+        p = radial * (R + w * c)[:, None]
+        p[:, 2] = w * np.sin(phi)
+        m = radial * c[:, None]
+        m[:, 2] = np.sin(phi)
+        out["tube"] = (p, t, 1.0, m, np.minimum(w, R + w * c), np.minimum(w, np.abs(R + w * c) / np.maximum(np.abs(c), 1e-12)))
+    elif kind == "plane":
+        nrm = np.array(a[:3])
+        ln = np.linalg.norm(nrm)
+        q = rng.uniform(-1.5, 1.5, (n, 3))
+        q = q - ((q @ nrm + a[3]) / (ln * ln))[:, None] * nrm[None, :]
+        t = rng.uniform(-1.5, 1.5, n)
+        out["plane"] = (q + t[:, None] * (nrm / ln)[None, :], ln * t, ln, np.tile(nrm / ln, (n, 1)), inf, inf)
     else:
         raise ValueError(kind)
     return out

@@ -44,10 +44,10 @@ def normals(ops, p, eps=0.0):
     return np.stack([vx * inv, vy * inv, vz * inv], axis=-1).astype(F)
 
 
-def extract(ops, n, bb, materials=False, algorithm=0):
+def extract(ops, n, bb, materials=False, algorithm=0, zeros_ok=False):
     """What sdfv_program_mesh_extract leaves for n cells over bb -> mesh_ref.extract's (vertices, indices, info)."""
     return MR.extract(lattice(ops, n, bb)[1], bb, algorithm, lambda p: normals(ops, p),
-                      (lambda p: R.run(ops, p, False)[:, 1:7]) if materials else None)
+                      (lambda p: R.run(ops, p, False)[:, 1:7]) if materials else None, zeros_ok=zeros_ok)
 
 
 def postproc(ops, vertices):

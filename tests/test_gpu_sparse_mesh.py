@@ -2,7 +2,8 @@
 restatement of tests/sparse_mesh_ref.py -- vertices, indices and stats bit for bit and in order -- and against the dense extractor
 of the same process as sets: vertex records as 12 words, triangles as rotations of record triples.  The programs, sizes, boxes and
 Lipschitz constants are sparse_mesh_ref.PROMISE's, for which tests/test_sparse_mesh_cpu.py shows that the promise holds; the steep
-plane breaks it on purpose.  No test uses more than 64 cells."""
+plane breaks it on purpose.  No test HERE uses more than 64 cells, the most the restatement can run: the promise at 1024 cells and
+the route at 2048 are tests/test_gpu_mesh_meaning.py's, against float64 geometry and the dense mesh on the device."""
 import ctypes as C
 import functools
 import importlib
