@@ -934,8 +934,12 @@ int sdfv_program_raymarch_check(const sdfv_program_march_desc *desc, sdfv_progra
  *
  * *out is a NEW handle (handles stay immutable) with the same instructions and box, freed with sdfv_program_free and accepted by
  * every entry point that takes an sdfv_program.  The routes named in `routes` launch the specialised kernels -- same argument
- * checks, same options, same launch geometry, same stream as the interpreted call --; every other route (mesh, normals, the
- * box launch and the scan of sdfv_program_grid_pass, the host mirror) interprets as before.
+ * checks, same options, same launch geometry, same stream as the interpreted call --; every other route (the box launch and
+ * the scan of sdfv_program_grid_pass, the host mirror, and meshing on a handle compiled without SDFV_COMPILE_MESH) interprets
+ * as before.  SDFV_COMPILE_MESH covers the steps of meshing that evaluate the program: the lattice and the vertex phase of
+ * sdfv_program_mesh_extract (both algorithms), the block refinement, the brick lattice and the vertex phase of
+ * sdfv_program_mesh_extract_sparse, sdfv_program_normal_points and sdfv_program_mesh_postproc; the SDF-free steps (edge masks,
+ * scans, positions, dual contouring's solve, triangles) are the library's own kernels for every handle.
  * arch: NULL = the current device's architecture (SDFV_ERR_NO_DEVICE without one), or a name such as "gfx950", with which the
  * call needs no device.  When a device is current and matches, the call also loads the code object and makes the device copy of
  * the instructions before it returns, so the first covered call can be captured into a graph; on another device the first
@@ -947,6 +951,8 @@ int sdfv_program_raymarch_check(const sdfv_program_march_desc *desc, sdfv_progra
 #define SDFV_COMPILE_FILL   1u /* sdfv_program_fill_grid_commit, and sdfv_program_grid_pass where it IS the dense fill */
 #define SDFV_COMPILE_POINTS 2u /* sdfv_program_sample_points (+ _host, which runs on the device) */
 #define SDFV_COMPILE_MARCH  4u /* sdfv_program_raymarch */
+/* Bit 8 is NOT a route: it is refused as an unknown bit, as it always was, and so is every bit above 16. */
+#define SDFV_COMPILE_MESH 16u /* sdfv_program_mesh_extract, _mesh_extract_sparse, _normal_points, _mesh_postproc (not their _host forms) */
 int sdfv_program_compile(const sdfv_program *p, uint32_t routes, const char *arch, sdfv_program **out);
 typedef struct sdfv_compiled_info {
     uint32_t size;   /* in: sizeof(sdfv_compiled_info), size-prefixed like sdfv_march_desc */
@@ -955,7 +961,16 @@ typedef struct sdfv_compiled_info {
     double compile_seconds;
     uint64_t code_bytes;
     uint64_t launches; /* specialised kernels launched through this handle: 1 per fill, the staged and the tail launch of a sampler
-                        * call, 1 per chunk of 16 cameras of a march */
+                        * call, 1 per chunk of 16 cameras of a march.  With SDFV_COMPILE_MESH, one per specialised kernel launched:
+                        *   sdfv_program_mesh_extract        1 (lattice) + v, v = 0 for an empty mesh, else 1 for marching cubes and
+                        *                                    2 for dual contouring (the vertex kernel over the Hermite records and
+                        *                                    over the solved vertices);
+                        *   sdfv_program_mesh_extract_sparse r + b + v: r = the refinement levels run (stats.levels, fewer when a
+                        *                                    level keeps no block), b = 1 if any brick survived (the brick lattice),
+                        *                                    v = 1 if the mesh has a vertex;
+                        *   sdfv_program_normal_points       as a sampler call: the staged launch (16-byte aligned arrays, n >= 256)
+                        *                                    and the tail launch (n % 256 != 0, or unaligned arrays: all of n);
+                        *   sdfv_program_mesh_postproc       1 (0 for n = 0) */
 } sdfv_compiled_info;
 int sdfv_program_compiled_info(const sdfv_program *p, sdfv_compiled_info *info); /* info->size too small: SDFV_ERR_INVALID_ARGUMENT */
 /* The code object (an ELF for `arch`) and the generated translation unit (NUL-terminated); both stay valid until the handle is

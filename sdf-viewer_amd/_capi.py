@@ -293,6 +293,7 @@ PASS_FRESH_GRID, PASS_SAME_LOAD, PASS_VIRGIN_GRID, PASS_VOLUME_INTERLEAVED, PASS
  OP_INTERSECT, OP_SUBTRACT, OP_SMOOTH_UNION, OP_SMOOTH_SUBTRACT, OP_ROUND, OP_SHELL, OP_MATERIAL) = range(1, 19)
 PROGRAM_MAX_OPS, PROGRAM_MAX_VALUES, PROGRAM_MAX_FRAMES = 256, 8, 4
 COMPILE_FILL, COMPILE_POINTS, COMPILE_MARCH = 1, 2, 4  # SDFV_COMPILE_*: the routes sdfv_program_compile specialises
+COMPILE_MESH = 16  # (bit 8 is no route)
 ERR_COMPILE = -6
 FILL_FORM = {"auto": 0, "rows": 1, "flat": 2}
 COMM_ID_BYTES = 128

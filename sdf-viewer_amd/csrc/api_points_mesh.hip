@@ -5,6 +5,7 @@
 #include "api_internal.h"
 #include "mesh_kernels.h"
 #include "points_kernels.h"
+#include "program_kernels.h"
 #include "program_mesh_kernels.h"
 #include "dual_contour_kernels.h"
 #include "lattice_mesh_kernels.h"
@@ -283,6 +284,8 @@ int sdfv_program_mesh_extract(const sdfv_program* p, const float bb_min[3], cons
     if (int rc = check_mesher(algorithm, max_voxels_per_axis)) return rc;
     if (flags & ~SDFV_MESH_WITH_MATERIALS) return set_error(SDFV_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", flags);
     if (int rc = need_device()) return rc;
+    sdfv::ProgramKernels compiled;  // (a compiled handle on the wrong device is refused before its device copy is made)
+    if (int rc = program_compiled_kernels(p, SDFV_COMPILE_MESH, &compiled)) return rc;
     const sdfv_prog_op* dev_ops = nullptr;
     uint32_t n_ops = 0;
     const float* bb = nullptr;
@@ -291,10 +294,10 @@ int sdfv_program_mesh_extract(const sdfv_program* p, const float bb_min[3], cons
     return extract_mesh(
         bb_min ? bb_min : bb, bb_max ? bb_max : bb + 3, max_voxels_per_axis, algorithm, out, (hipStream_t)stream,
         [&](const sdfv::MeshGrid& g, const sdfv::MeshWork& w, hipStream_t st) {
-            return sdfv::launch_program_mesh_lattice(dev_ops, n_ops, g, w, st);
+            return sdfv::launch_program_mesh_lattice(dev_ops, n_ops, g, w, compiled, st);
         },
         [&](sdfv_vertex* vertices, size_t n, bool final, hipStream_t st) {  // the materials belong to the output vertices only
-            return sdfv::launch_program_vertex_normals(dev_ops, n_ops, vertices, n, materials && final, st);
+            return sdfv::launch_program_vertex_normals(dev_ops, n_ops, vertices, n, materials && final, compiled, st);
         });
 }
 
@@ -309,8 +312,8 @@ float sparse_threshold(const sdfv::MeshGrid& g, uint32_t s, float L) {
     return (L * r) * 1.001f;
 }
 
-int extract_sparse(const sdfv_prog_op* dev_ops, uint32_t n_ops, const sdfv::MeshGrid& g, float L, bool materials, sdfv_mesh* out,
-                   sdfv_sparse_mesh_stats* stats, hipStream_t st) {
+int extract_sparse(const sdfv_prog_op* dev_ops, uint32_t n_ops, const sdfv::ProgramKernels& compiled, const sdfv::MeshGrid& g, float L,
+                   bool materials, sdfv_mesh* out, sdfv_sparse_mesh_stats* stats, hipStream_t st) {
     const uint32_t N = g.cells[0];
     sdfv_sparse_mesh_stats s{};
     while ((4u << s.levels) < N) ++s.levels;
@@ -328,7 +331,7 @@ int extract_sparse(const sdfv_prog_op* dev_ops, uint32_t n_ops, const sdfv::Mesh
         lay_out_refinement(w, g_sparse_scratch.p, n);
         if (level == 0) SDFV_HIP(hipMemsetAsync(w.list, 0, 4, st));
         const uint32_t shift = 31u - (uint32_t)__builtin_clz(N >> (level + 1));  // children of N / 2^(level + 1) cells
-        SDFV_HIP(sdfv::launch_sparse_refine(dev_ops, n_ops, g, shift, sparse_threshold(g, 1u << shift, L), w, n, w.mesh.totals, st));
+        SDFV_HIP(sdfv::launch_sparse_refine(dev_ops, n_ops, g, shift, sparse_threshold(g, 1u << shift, L), w, n, w.mesh.totals, compiled, st));
         s.tested[level] = n * 8u;
         SDFV_HIP(hipMemcpyAsync(&n, w.mesh.totals, 4, hipMemcpyDeviceToHost, st));
         SDFV_HIP(hipStreamSynchronize(st));
@@ -346,7 +349,7 @@ int extract_sparse(const sdfv_prog_op* dev_ops, uint32_t n_ops, const sdfv::Mesh
         if (int rc = reserve(lay_out_bricks(w, nullptr, n), s.levels ? n : 0)) return rc;
         lay_out_bricks(w, g_sparse_scratch.p, n);
         if (s.levels == 0) SDFV_HIP(hipMemsetAsync(w.list, 0, 4, st));
-        SDFV_HIP(sdfv::launch_sparse_brick_lattice(dev_ops, n_ops, g, w, n, st));
+        SDFV_HIP(sdfv::launch_sparse_brick_lattice(dev_ops, n_ops, g, w, n, compiled, st));
         SDFV_HIP(sdfv::launch_sparse_count(g, w, n, st));
         uint32_t totals[2] = {0, 0};  // vertices, triangles: the extra last entry of each scan
         SDFV_HIP(hipMemcpyAsync(&totals[0], w.mesh.point_first + (size_t)n * sdfv::kBrickPoints, 4, hipMemcpyDeviceToHost, st));
@@ -356,7 +359,7 @@ int extract_sparse(const sdfv_prog_op* dev_ops, uint32_t n_ops, const sdfv::Mesh
         m.n_indices = (size_t)totals[1] * 3;
         if (int rc = allocate_mesh(m)) return rc;
         hipError_t e = sdfv::launch_sparse_positions(g, w, n, m.vertices, m.n_vertices, st);  // marching cubes' chain, as extract_mesh
-        if (e == hipSuccess) e = sdfv::launch_program_vertex_normals(dev_ops, n_ops, m.vertices, m.n_vertices, materials, st);
+        if (e == hipSuccess) e = sdfv::launch_program_vertex_normals(dev_ops, n_ops, m.vertices, m.n_vertices, materials, compiled, st);
         if (e == hipSuccess) e = sdfv::launch_sparse_triangles(g, w, n, m.indices, st);
         if (int rc = finish_mesh(e, m, out, st, "sparse mesh emit")) return rc;
     }
@@ -392,11 +395,13 @@ int sdfv_program_mesh_extract_sparse(const sdfv_sparse_mesh_desc* desc, void* st
         return set_error(SDFV_ERR_INVALID_ARGUMENT, "sdfv_sparse_mesh_stats.size = %u is smaller than the structure (%zu)", d.stats->size,
                          sizeof(sdfv_sparse_mesh_stats));
     if (int rc = need_device()) return rc;
+    sdfv::ProgramKernels compiled;  // (as above: the wrong device is refused first)
+    if (int rc = program_compiled_kernels(d.program, SDFV_COMPILE_MESH, &compiled)) return rc;
     const sdfv_prog_op* dev_ops = nullptr;
     uint32_t n_ops = 0;
     const float* bb = nullptr;
     if (int rc = program_on_device(d.program, &dev_ops, &n_ops, &bb)) return rc;
-    return extract_sparse(dev_ops, n_ops, lattice_grid(d.bb_min ? d.bb_min : bb, d.bb_max ? d.bb_max : bb + 3, d.cells),
+    return extract_sparse(dev_ops, n_ops, compiled, lattice_grid(d.bb_min ? d.bb_min : bb, d.bb_max ? d.bb_max : bb + 3, d.cells),
                           d.lipschitz == 0.0f ? 1.0f : d.lipschitz, (d.flags & SDFV_MESH_WITH_MATERIALS) != 0, d.out, d.stats,
                           (hipStream_t)stream);
 }

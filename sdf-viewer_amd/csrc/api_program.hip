@@ -120,12 +120,15 @@ int sdfv::program_on_device(const sdfv_program* cp, const sdfv_prog_op** out, ui
 
 // The prologue of the entry points that run a program over n elements (`names`: the buffers in the alignment message); n == 0 leaves *ops NULL.
 static int program_elements_ready(const sdfv_program* p, const void* in, const void* out, size_t n, const char* names,
-                                  const sdfv_prog_op** ops, uint32_t* n_ops) {
+                                  const sdfv_prog_op** ops, uint32_t* n_ops, sdfv::ProgramKernels* compiled) {
     if (!p) return set_error(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
     if (int rc = check_point_buffers(in, out, n)) return rc;
     if (int rc = check_word_aligned(names, in, out)) return rc;
     if (int rc = need_device()) return rc;
-    return n ? program_on_device(p, ops, n_ops) : SDFV_OK;
+    if (n == 0) return SDFV_OK;
+    // (a compiled handle on the wrong device is refused before its device copy is made)
+    if (int rc = program_compiled_kernels(p, SDFV_COMPILE_MESH, compiled)) return rc;
+    return program_on_device(p, ops, n_ops);
 }
 
 #pragma GCC visibility push(default)
@@ -180,17 +183,19 @@ int sdfv_program_sample_points(const sdfv_program* p, const float* points, size_
 int sdfv_program_normal_points(const sdfv_program* p, const float* points, size_t n, float eps, float* out, void* stream) {
     const sdfv_prog_op* dev_ops = nullptr;
     uint32_t n_ops = 0;
-    if (int rc = program_elements_ready(p, points, out, n, "points and out", &dev_ops, &n_ops)) return rc;
+    sdfv::ProgramKernels compiled;
+    if (int rc = program_elements_ready(p, points, out, n, "points and out", &dev_ops, &n_ops, &compiled)) return rc;
     if (!dev_ops) return SDFV_OK;
-    SDFV_HIP_RETURN(sdfv::launch_program_normal_points(dev_ops, n_ops, points, n, eps, out, (hipStream_t)stream));
+    SDFV_HIP_RETURN(sdfv::launch_program_normal_points(dev_ops, n_ops, points, n, eps, out, compiled, (hipStream_t)stream));
 }
 
 int sdfv_program_mesh_postproc(const sdfv_program* p, sdfv_vertex* vertices, size_t n, void* stream) {
     const sdfv_prog_op* dev_ops = nullptr;
     uint32_t n_ops = 0;
-    if (int rc = program_elements_ready(p, vertices, vertices, n, "vertices", &dev_ops, &n_ops)) return rc;
+    sdfv::ProgramKernels compiled;
+    if (int rc = program_elements_ready(p, vertices, vertices, n, "vertices", &dev_ops, &n_ops, &compiled)) return rc;
     if (!dev_ops) return SDFV_OK;
-    SDFV_HIP_RETURN(sdfv::launch_program_mesh_postproc(dev_ops, n_ops, vertices, n, (hipStream_t)stream));
+    SDFV_HIP_RETURN(sdfv::launch_program_mesh_postproc(dev_ops, n_ops, vertices, n, compiled, (hipStream_t)stream));
 }
 
 int sdfv_program_raymarch_check(const sdfv_program_march_desc* desc, sdfv_program_march_desc* checked, float* normal_h) {

@@ -6,7 +6,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#if defined(__HIPCC_RTC__)  // the run-time compiler is handed the headers by name (program_compile.hip)
+#include "sdfgrid.h"
+#else
 #include "../../include/sdfgrid.h"
+#endif
 
 namespace sdfv {
 
@@ -33,6 +37,7 @@ struct MeshWork {           // device scratch of one extraction: sub-blocks of t
     uint32_t* totals;       // [3] the counts the host reads back to allocate the output
 };
 
+#if !defined(__HIPCC_RTC__)  // (host only: the run-time compiler reads this header for MeshGrid)
 size_t mesh_scan_tmp_bytes(size_t n);
 // An extraction is six steps on one stream (five for the demo tree's marching cubes: see the end); the first and the fifth evaluate the SDF, the others do not and serve every kind of
 // SDF (the demo tree here, SDF programs in program_mesh_kernels.hip) and both meshers (dual_contour_kernels.h has algorithm 4's
@@ -61,5 +66,6 @@ hipError_t launch_mesh_fused_vertices(const sdfv_demo_params& prm, uint32_t sdf_
                                       sdfv_vertex* vertices, size_t n, hipStream_t stream);
 // 6. triangle indices
 hipError_t launch_mesh_triangles(const MeshGrid& g, const MeshWork& w, uint32_t* indices, hipStream_t stream);
+#endif
 
 }  // namespace sdfv

@@ -6,7 +6,8 @@
 //  * holds the instructions as a constexpr sdfv_prog_op array (operands as their 32-bit patterns, never as decimal text),
 //  * defines ONE evaluator that calls prog::step() once per instruction on a constant (with a register fence between steps:
 //    DESIGN.md 3.6.2), and
-//  * instantiates the kernel bodies of program_device.h -- the text the library's own kernels are instantiated from -- with it,
+//  * instantiates the kernel bodies of program_device.h and, for SDFV_COMPILE_MESH, of program_mesh_device.h -- the text the
+//    library's own kernels are instantiated from -- with it,
 //    one extern "C" kernel per variant the compiled routes launch (kKernelNames), and nothing for a route not asked for,
 // and hands it to the run-time compiler (libhiprtc, bound with dlopen on the first compile like RCCL in slab_comm.hip)
 // together with the project's headers, embedded in this library as strings by the Makefile (gen_embed_headers.c), and the
@@ -60,11 +61,16 @@ const EmbeddedHeader kStandIns[] = {
 // The specialised kernels, by sdfv::ProgramKernel, and the route each belongs to.
 const char* const kKernelNames[sdfv::kProgramKernels] = {
     "sdfprogc_fill_tx64", "sdfprogc_fill_tx64_nt", "sdfprogc_fill_tx128", "sdfprogc_fill_tx128_nt", "sdfprogc_fill_tx256", "sdfprogc_fill_tx256_nt",
-    "sdfprogc_sample_points", "sdfprogc_sample_points_staged", "sdfprogc_march", "sdfprogc_march_aux"};
+    "sdfprogc_sample_points", "sdfprogc_sample_points_staged", "sdfprogc_march", "sdfprogc_march_aux",
+    "sdfprogc_mesh_lattice", "sdfprogc_mesh_vertices", "sdfprogc_mesh_vertices_mat", "sdfprogc_normal_points", "sdfprogc_normal_points_staged",
+    "sdfprogc_mesh_postproc", "sdfprogc_mesh_postproc_unaligned", "sdfprogc_sparse_refine", "sdfprogc_sparse_bricks"};
 uint32_t route_of(int kernel) {
-    return kernel <= sdfv::kKernelFillTx256Nt ? SDFV_COMPILE_FILL : (kernel <= sdfv::kKernelPointsStaged ? SDFV_COMPILE_POINTS : SDFV_COMPILE_MARCH);
+    if (kernel <= sdfv::kKernelFillTx256Nt) return SDFV_COMPILE_FILL;
+    if (kernel <= sdfv::kKernelPointsStaged) return SDFV_COMPILE_POINTS;
+    return kernel <= sdfv::kKernelMarchAux ? SDFV_COMPILE_MARCH : SDFV_COMPILE_MESH;
 }
-constexpr uint32_t kAllRoutes = SDFV_COMPILE_FILL | SDFV_COMPILE_POINTS | SDFV_COMPILE_MARCH;
+// (bit 8 is no route: it stays among the unknown bits)
+constexpr uint32_t kAllRoutes = SDFV_COMPILE_FILL | SDFV_COMPILE_POINTS | SDFV_COMPILE_MARCH | SDFV_COMPILE_MESH;
 
 // ---- the run-time compiler: the slice of hiprtc.h this file needs ----
 struct Hiprtc {
@@ -144,8 +150,9 @@ std::string generate_source(const std::vector<sdfv_prog_op>& ops, uint32_t route
     std::string s;
     s.reserve(ops.size() * 260 + 4096);
     s += "// generated by sdfv_program_compile: one SDF program, its instructions as constants\n"
-         "#include \"program_device.h\"\n\n"
-         "namespace {\n"
+         "#include \"program_device.h\"\n";
+    if (routes & SDFV_COMPILE_MESH) s += "#include \"program_mesh_device.h\"\n";
+    s += "\nnamespace {\n"
          "constexpr float f32(uint32_t bits) { return __builtin_bit_cast(float, bits); }\n";
     append(s, "constexpr uint32_t kOpCount = %zuu;\n", ops.size());
     s += "constexpr sdfv_prog_op kOps[kOpCount] = {\n";
@@ -222,6 +229,54 @@ std::string generate_source(const std::vector<sdfv_prog_op>& ops, uint32_t route
     if (routes & SDFV_COMPILE_MARCH)
         s += "__global__ __launch_bounds__(kBlock) void sdfprogc_march(ProgramMarchArgs a) { program_march<false>(a, Compiled<true>{}); }\n"
              "__global__ __launch_bounds__(kBlock) void sdfprogc_march_aux(ProgramMarchArgs a) { program_march<true>(a, Compiled<true>{}); }\n";
+    if (routes & SDFV_COMPILE_MESH)
+        // The parameter lists are those of the sdfprog_* twins (program_mesh_kernels.hip, sparse_mesh_kernels.hip), ops / n_ops
+        // included: one argument array serves either launch.  The four taps sit in tap_normal's loop, which is not unrolled: one
+        // copy of the evaluator, its operands kept from being hoisted out of that loop as in the march (Tap); the material run
+        // and the lattices stand outside any loop (Once).
+        s += "using Once = Compiled<false>;\n"
+             "using Tap = Compiled<true>;\n"
+             "__global__ __launch_bounds__(kBlock) void sdfprogc_mesh_lattice(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,\n"
+             "                                                                float* __restrict__ dist) {\n"
+             "    mesh_lattice_points(Once{}, g, dist);\n"
+             "}\n"
+             "__global__ __launch_bounds__(kBlock) void sdfprogc_mesh_vertices(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
+             "                                                                 float4* __restrict__ vertices, uint32_t n) {\n"
+             "    mesh_vertices<false>(Once{}, Tap{}, ops, vertices, n);\n"
+             "}\n"
+             "__global__ __launch_bounds__(kBlock) void sdfprogc_mesh_vertices_mat(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
+             "                                                                     float4* __restrict__ vertices, uint32_t n) {\n"
+             "    mesh_vertices<true>(Once{}, Tap{}, ops, vertices, n);\n"
+             "}\n"
+             "__global__ __launch_bounds__(kBlock) void sdfprogc_normal_points(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
+             "                                                                 const float* __restrict__ points, size_t first, size_t n,\n"
+             "                                                                 float eps, float* __restrict__ out) {\n"
+             "    map_elements<3, 3>(ProgramNormalEval<Tap>{Tap{}, eps}, points, first, n, out);\n"
+             "}\n"
+             "__global__ __launch_bounds__(kBlock) void sdfprogc_normal_points_staged(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
+             "                                                                        const float4* __restrict__ points, float eps,\n"
+             "                                                                        float4* __restrict__ out) {\n"
+             "    map_elements_staged<3, 3>(ProgramNormalEval<Tap>{Tap{}, eps}, points, out);\n"
+             "}\n"
+             "__global__ __launch_bounds__(kBlock) void sdfprogc_mesh_postproc(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
+             "                                                                 float4* __restrict__ vertices, size_t n) {\n"
+             "    mesh_postproc_aligned(Once{}, Tap{}, ops, vertices, n);\n"
+             "}\n"
+             "__global__ __launch_bounds__(kBlock) void sdfprogc_mesh_postproc_unaligned(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
+             "                                                                           float* __restrict__ vertices, size_t n) {\n"
+             "    mesh_postproc_words(Once{}, Tap{}, ops, vertices, n);\n"
+             "}\n"
+             "__global__ __launch_bounds__(kBlock) void sdfprogc_sparse_refine(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,\n"
+             "                                                                 const uint32_t* __restrict__ parents, uint32_t n, uint32_t shift,\n"
+             "                                                                 float threshold, uint32_t* __restrict__ cand,\n"
+             "                                                                 uint32_t* __restrict__ pos) {\n"
+             "    sparse_refine_children(Once{}, g, parents, n, shift, threshold, cand, pos);\n"
+             "}\n"
+             "__global__ __launch_bounds__(kBlock) void sdfprogc_sparse_bricks(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,\n"
+             "                                                                 const uint32_t* __restrict__ bricks, uint32_t n,\n"
+             "                                                                 float* __restrict__ dist) {\n"
+             "    sparse_brick_points(Once{}, g, bricks, n, dist);\n"
+             "}\n";
     s += "}  // extern \"C\"\n";
     return s;
 }
@@ -357,7 +412,7 @@ int sdfv_program_compile(const sdfv_program* p, uint32_t routes, const char* arc
     if (!out) return set_error(SDFV_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
     if (!p) return set_error(SDFV_ERR_INVALID_ARGUMENT, "program is NULL");
-    if (routes == 0) return set_error(SDFV_ERR_INVALID_ARGUMENT, "routes is 0: name at least one of SDFV_COMPILE_FILL, _POINTS, _MARCH");
+    if (routes == 0) return set_error(SDFV_ERR_INVALID_ARGUMENT, "routes is 0: name at least one of SDFV_COMPILE_FILL, _POINTS, _MARCH, _MESH");
     if (routes & ~kAllRoutes) return set_error(SDFV_ERR_INVALID_ARGUMENT, "unknown route bits 0x%x", routes & ~kAllRoutes);
     if (arch && (!arch[0] || strlen(arch) >= sizeof(sdfv_compiled_info::arch) || strchr(arch, ' ')))
         return set_error(SDFV_ERR_INVALID_ARGUMENT, "arch is not a processor name such as \"gfx950\"");

@@ -38,7 +38,10 @@ struct ProgramFillArgs {
 // specialised ones (program_compile.hip holds their names in this order).
 enum ProgramKernel {
     kKernelFillTx64, kKernelFillTx64Nt, kKernelFillTx128, kKernelFillTx128Nt, kKernelFillTx256, kKernelFillTx256Nt,
-    kKernelPoints, kKernelPointsStaged, kKernelMarch, kKernelMarchAux, kProgramKernels
+    kKernelPoints, kKernelPointsStaged, kKernelMarch, kKernelMarchAux,
+    // SDFV_COMPILE_MESH (program_mesh_kernels.hip, sparse_mesh_kernels.hip)
+    kKernelMeshLattice, kKernelMeshVertices, kKernelMeshVerticesMat, kKernelNormalPoints, kKernelNormalPointsStaged,
+    kKernelMeshPostproc, kKernelMeshPostprocUnaligned, kKernelSparseRefine, kKernelSparseBricks, kProgramKernels
 };
 
 #if !defined(__HIPCC_RTC__)

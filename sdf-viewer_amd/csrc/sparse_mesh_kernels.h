@@ -7,7 +7,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#if defined(__HIPCC_RTC__)  // the run-time compiler is handed the headers by name (program_compile.hip)
+#include "sdfgrid.h"
+#else
 #include "../../include/sdfgrid.h"
+#endif
 #include "mesh_kernels.h"
 
 namespace sdfv {
@@ -29,14 +33,18 @@ struct SparseWork {
     MeshWork mesh;
 };
 
-// g: `cells` on every axis, a power of two; ops: the DEVICE copy of the validated program.
+#if !defined(__HIPCC_RTC__)  // (host only: the run-time compiler reads this header for the brick constants)
+struct ProgramKernels;  // program_kernels.h
+// g: `cells` on every axis, a power of two; ops: the DEVICE copy of the validated program; k: the kernels of a handle compiled
+// with SDFV_COMPILE_MESH, or none (the interpreter's are launched, with the same grid, block and stream).
 // One level: the 8 * n_parents children of w.list, blocks of 2^shift cells, are tested at their centre lattice point
 // (kept iff !(|d| > threshold)) and the survivors replace w.list in order; *kept_dev receives their number.
 hipError_t launch_sparse_refine(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, uint32_t shift, float threshold,
-                                const SparseWork& w, uint32_t n_parents, uint32_t* kept_dev, hipStream_t stream);
+                                const SparseWork& w, uint32_t n_parents, uint32_t* kept_dev, const ProgramKernels& k,
+                                hipStream_t stream);
 // The program's distance at the 125 lattice points of every brick into w.dist.
 hipError_t launch_sparse_brick_lattice(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const SparseWork& w,
-                                       uint32_t n_bricks, hipStream_t stream);
+                                       uint32_t n_bricks, const ProgramKernels& k, hipStream_t stream);
 // Edge masks of the owned points, the neighbour table, triangle counts of the cells, both scans (each over one entry more: the
 // total).
 hipError_t launch_sparse_count(const MeshGrid& g, const SparseWork& w, uint32_t n_bricks, hipStream_t stream);
@@ -45,5 +53,6 @@ hipError_t launch_sparse_positions(const MeshGrid& g, const SparseWork& w, uint3
                                    hipStream_t stream);
 hipError_t launch_sparse_triangles(const MeshGrid& g, const SparseWork& w, uint32_t n_bricks, uint32_t* indices,
                                    hipStream_t stream);
+#endif
 
 }  // namespace sdfv

@@ -16,30 +16,24 @@
 //    neighbours, which sparse_brick_neighbours has looked up once per brick by binary search in the brick list (sorted by Morton
 //    key; a directory of (cells / 4)^3 words would be 4 GiB at 4096 cells).  A cell whose crossing edge has no owner among the
 //    bricks (the program broke its Lipschitz promise) emits nothing: no index is ever out of range.
+// The bodies of the two evaluating kernels are program_mesh_device.h's, over an evaluator: the interpreter here, one program's own
+// in the kernels a handle compiled with SDFV_COMPILE_MESH brings, which the two launchers then launch in these kernels' place.
 // A block is its Morton key in units of its own side, x the lowest bit; keys are below 2^30 (1024 bricks per axis at the most).
 // The kernels carry C names: tests and profiles find them under the same symbol whatever the toolchain mangles.
 #include "sparse_mesh_kernels.h"
 
 #include "kernel_common.h"
 #include "mesh_steps.h"
-#include "program_eval.h"
+#include "program_kernels.h"
+#include "program_mesh_device.h"
 
 namespace sdfv {
 
 namespace {
 
-constexpr uint32_t kKept = 0x80000000u;
 constexpr uint32_t kNoBrick = 0xffffffffu;
 
-// every third bit of a Morton key -> a 10-bit coordinate, and back
-__device__ __forceinline__ uint32_t gather3(uint32_t x) {
-    x &= 0x09249249u;
-    x = (x ^ (x >> 2)) & 0x030c30c3u;
-    x = (x ^ (x >> 4)) & 0x0300f00fu;
-    x = (x ^ (x >> 8)) & 0x030000ffu;
-    x = (x ^ (x >> 16)) & 0x000003ffu;
-    return x;
-}
+// a 10-bit coordinate -> every third bit of a Morton key (gather3 of program_mesh_device.h back)
 __device__ __forceinline__ uint32_t spread3(uint32_t x) {
     x &= 0x000003ffu;
     x = (x ^ (x << 16)) & 0x030000ffu;
@@ -47,16 +41,6 @@ __device__ __forceinline__ uint32_t spread3(uint32_t x) {
     x = (x ^ (x << 4)) & 0x030c30c3u;
     x = (x ^ (x << 2)) & 0x09249249u;
     return x;
-}
-
-// thread t of a brick-major array of 125 per brick -> the brick and the local point (x fastest)
-__device__ __forceinline__ void unbrick(uint32_t t, uint32_t& b, uint32_t& lx, uint32_t& ly, uint32_t& lz) {
-    b = t / kBrickPoints;
-    const uint32_t l = t - b * kBrickPoints;
-    lz = l / 25u;
-    const uint32_t r = l - lz * 25u;
-    ly = r / 5u;
-    lx = r - ly * 5u;
 }
 
 // index of the brick with this key, or kNoBrick: the list is sorted
@@ -135,17 +119,7 @@ __global__ __launch_bounds__(kBlock) void sdfprog_sparse_refine(const sdfv_prog_
                                                                 const uint32_t* __restrict__ parents, uint32_t n, uint32_t shift,
                                                                 float threshold, uint32_t* __restrict__ cand,
                                                                 uint32_t* __restrict__ pos) {
-    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= n) return;
-    const uint32_t key = parents[t >> 3] * 8u + (t & 7u);
-    const uint32_t half = (1u << shift) >> 1;  // the centre lattice point: o + s / 2
-    float px, py, pz;
-    lattice_position(g, (gather3(key) << shift) + half, (gather3(key >> 1) << shift) + half, (gather3(key >> 2) << shift) + half,
-                     px, py, pz);
-    const float d = prog::run(ops, n_ops, px, py, pz).d;
-    const bool keep = !(fabsf(d) > threshold);  // a NaN distance keeps the block
-    cand[t] = key | (keep ? kKept : 0u);
-    pos[t] = keep ? 1u : 0u;
+    sparse_refine_children(prog::Interpreter{ops, n_ops}, g, parents, n, shift, threshold, cand, pos);
 }
 
 // survivors up, in order; the last thread leaves their number
@@ -154,21 +128,14 @@ __global__ __launch_bounds__(kBlock) void sparse_compact(const uint32_t* __restr
     const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= n) return;
     const uint32_t c = cand[t], at = pos[t];
-    if (c & kKept) list[at] = c & ~kKept;
+    if (c & kSparseKept) list[at] = c & ~kSparseKept;
     if (t == n - 1) *kept = at + (c >> 31);
 }
 
 __global__ __launch_bounds__(kBlock) void sdfprog_sparse_bricks(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,
                                                                 const uint32_t* __restrict__ bricks, uint32_t n,
                                                                 float* __restrict__ dist) {
-    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-    if (t >= n) return;
-    uint32_t b, lx, ly, lz;
-    unbrick(t, b, lx, ly, lz);
-    const uint32_t key = bricks[b];
-    float px, py, pz;
-    lattice_position(g, gather3(key) * 4u + lx, gather3(key >> 1) * 4u + ly, gather3(key >> 2) * 4u + lz, px, py, pz);
-    dist[t] = prog::run(ops, n_ops, px, py, pz).d;
+    sparse_brick_points(prog::Interpreter{ops, n_ops}, g, bricks, n, dist);
 }
 
 // Which of the point's three +axis edges the brick owns and cross; count -> scan input.  n = 125 * bricks; thread n writes the
@@ -266,21 +233,36 @@ bool sparse_grid(const MeshGrid& g) {  // one power of two, 4 .. 4096, on every 
 }  // namespace
 
 hipError_t launch_sparse_refine(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, uint32_t shift, float threshold,
-                                const SparseWork& w, uint32_t n_parents, uint32_t* kept_dev, hipStream_t stream) {
+                                const SparseWork& w, uint32_t n_parents, uint32_t* kept_dev, const ProgramKernels& k,
+                                hipStream_t stream) {
     if (!sparse_grid(g) || n_parents == 0 || n_parents > 0x10000000u || shift < 2 || (2u << shift) > g.cells[0])
         return hipErrorInvalidValue;  // children of 4 .. cells / 2 cells, and 8 of them per parent in 32 bits
-    const uint32_t n = n_parents * 8u;
-    hipLaunchKernelGGL(sdfprog_sparse_refine, dim3(blocks_for(n)), dim3(kBlock), 0, stream, ops, n_ops, g, w.list, n, shift,
-                       threshold, w.cand, w.pos);
+    uint32_t n = n_parents * 8u;
+    MeshGrid grid = g;
+    const uint32_t* parents = w.list;
+    uint32_t *cand = w.cand, *pos = w.pos;
+    void* params[] = {&ops, &n_ops, &grid, &parents, &n, &shift, &threshold, &cand, &pos};
+    bool mine = false;
+    if (hipError_t e = k.launch(kKernelSparseRefine, dim3(blocks_for(n)), dim3(kBlock), params, stream, &mine); e != hipSuccess) return e;
+    if (!mine)
+        hipLaunchKernelGGL(sdfprog_sparse_refine, dim3(blocks_for(n)), dim3(kBlock), 0, stream, ops, n_ops, g, w.list, n, shift,
+                           threshold, w.cand, w.pos);
     if (hipError_t e = mesh_exclusive_scan(w.mesh, w.pos, n, stream); e != hipSuccess) return e;
     hipLaunchKernelGGL(sparse_compact, dim3(blocks_for(n)), dim3(kBlock), 0, stream, w.cand, w.pos, n, w.list, kept_dev);
     return hipGetLastError();
 }
 
 hipError_t launch_sparse_brick_lattice(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const SparseWork& w,
-                                       uint32_t n_bricks, hipStream_t stream) {
+                                       uint32_t n_bricks, const ProgramKernels& k, hipStream_t stream) {
     if (!sparse_grid(g) || n_bricks == 0 || (uint64_t)n_bricks * kBrickPoints >= 0xffffffffull) return hipErrorInvalidValue;
-    const uint32_t n = n_bricks * kBrickPoints;
+    uint32_t n = n_bricks * kBrickPoints;
+    MeshGrid grid = g;
+    const uint32_t* bricks = w.list;
+    float* dist = w.mesh.dist;
+    void* params[] = {&ops, &n_ops, &grid, &bricks, &n, &dist};
+    bool mine = false;
+    const hipError_t e = k.launch(kKernelSparseBricks, dim3(blocks_for(n)), dim3(kBlock), params, stream, &mine);
+    if (mine) return e;
     hipLaunchKernelGGL(sdfprog_sparse_bricks, dim3(blocks_for(n)), dim3(kBlock), 0, stream, ops, n_ops, g, w.list, n, w.mesh.dist);
     return hipGetLastError();
 }

@@ -34,6 +34,7 @@ from ._capi import ProgOp, SdfvError, check, lib
 PARAM_VALUE, PARAM_NEGATED, PARAM_RECIPROCAL = 0, 1, 2
 # the routes CompiledProgram.compile() specialises (SDFV_COMPILE_*)
 FILL, POINTS, MARCH = _capi.COMPILE_FILL, _capi.COMPILE_POINTS, _capi.COMPILE_MARCH
+MESH = _capi.COMPILE_MESH
 PARAM_MAX_TARGETS = 4
 
 
@@ -366,9 +367,10 @@ class CompiledProgram:
         return s
 
     def compile(self, routes=FILL | POINTS | MARCH, arch=None):
-        """sdfv_program_compile: a NEW handle whose `routes` (FILL | POINTS | MARCH) launch kernels compiled for this very
-        program at run time; everything else about it is this handle's.  arch: None = the current device's, or a name such as
-        "gfx950" (needs no device).  Takes of the order of a second per route: for a model that is filled or rendered many
+        """sdfv_program_compile: a NEW handle whose `routes` (FILL | POINTS | MARCH | MESH) launch kernels compiled for this
+        very program at run time; everything else about it is this handle's.  MESH covers mesh(), mesh_sparse(), normals and
+        postproc on the device -- the steps that evaluate the program -- and is not part of the default.  arch: None = the
+        current device's, or a name such as "gfx950" (needs no device).  Takes of the order of a second per route: for a model that is filled or rendered many
         times, not for an editor's snapshots."""
         h = C.c_void_p()
         check(lib.sdfv_program_compile(self.h, int(routes), None if arch is None else str(arch).encode(), C.byref(h)))
