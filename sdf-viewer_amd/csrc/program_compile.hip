@@ -6,9 +6,10 @@
 //  * holds the instructions as a constexpr sdfv_prog_op array (operands as their 32-bit patterns, never as decimal text),
 //  * defines ONE evaluator that calls prog::step() once per instruction on a constant (with a register fence between steps:
 //    DESIGN.md 3.6.2), and
-//  * instantiates the kernel bodies of program_device.h and, for SDFV_COMPILE_MESH, of program_mesh_device.h -- the text the
-//    library's own kernels are instantiated from -- with it,
-//    one extern "C" kernel per variant the compiled routes launch (kKernelNames), and nothing for a route not asked for,
+//  * defines it as the two evaluator expressions (SDFV_EVAL_ONCE, SDFV_EVAL_LOOPED) of the kernel definitions in
+//    program_device.h and, for SDFV_COMPILE_MESH, program_mesh_device.h -- the definitions the library's own kernels are made
+//    from -- and invokes one definition per kernel the compiled routes launch (the rows of SDFV_PROGRAM_KERNELS,
+//    program_kernels.h), naming it sdfprogc_<stem>, and nothing for a route not asked for,
 // and hands it to the run-time compiler (libhiprtc, bound with dlopen on the first compile like RCCL in slab_comm.hip)
 // together with the project's headers, embedded in this library as strings by the Makefile (gen_embed_headers.c), and the
 // Makefile's code-affecting flags (SDFV_KERNEL_FLAGS).  Same text, same compiler, same flags as hipcc's build of the
@@ -58,17 +59,19 @@ const EmbeddedHeader kStandIns[] = {
      "}\n"},
 };
 
-// The specialised kernels, by sdfv::ProgramKernel, and the route each belongs to.
-const char* const kKernelNames[sdfv::kProgramKernels] = {
-    "sdfprogc_fill_tx64", "sdfprogc_fill_tx64_nt", "sdfprogc_fill_tx128", "sdfprogc_fill_tx128_nt", "sdfprogc_fill_tx256", "sdfprogc_fill_tx256_nt",
-    "sdfprogc_sample_points", "sdfprogc_sample_points_staged", "sdfprogc_march", "sdfprogc_march_aux",
-    "sdfprogc_mesh_lattice", "sdfprogc_mesh_vertices", "sdfprogc_mesh_vertices_mat", "sdfprogc_normal_points", "sdfprogc_normal_points_staged",
-    "sdfprogc_mesh_postproc", "sdfprogc_mesh_postproc_unaligned", "sdfprogc_sparse_refine", "sdfprogc_sparse_bricks"};
-uint32_t route_of(int kernel) {
-    if (kernel <= sdfv::kKernelFillTx256Nt) return SDFV_COMPILE_FILL;
-    if (kernel <= sdfv::kKernelPointsStaged) return SDFV_COMPILE_POINTS;
-    return kernel <= sdfv::kKernelMarchAux ? SDFV_COMPILE_MARCH : SDFV_COMPILE_MESH;
-}
+// The specialised kernels by sdfv::ProgramKernel: each row of SDFV_PROGRAM_KERNELS (program_kernels.h) as its name stem, the
+// name a handle's code object has it under, and its route.
+const struct {
+    const char* stem;
+    const char* name;
+    uint32_t route;
+} kKernels[] = {
+#define SDFV_X(index, stem, route) {#stem, "sdfprogc_" #stem, route},
+    SDFV_PROGRAM_KERNELS(SDFV_X)
+#undef SDFV_X
+};
+static_assert(sizeof(kKernels) / sizeof(kKernels[0]) == sdfv::kProgramKernels, "one row per kernel");
+uint32_t route_of(int kernel) { return kKernels[kernel].route; }
 // (bit 8 is no route: it stays among the unknown bits)
 constexpr uint32_t kAllRoutes = SDFV_COMPILE_FILL | SDFV_COMPILE_POINTS | SDFV_COMPILE_MARCH | SDFV_COMPILE_MESH;
 
@@ -207,77 +210,11 @@ std::string generate_source(const std::vector<sdfv_prog_op>& ops, uint32_t route
          "};\n"
          "}  // namespace\n\n"
          "using namespace sdfv;\n"
-         "extern \"C\" {\n";
-    if (routes & SDFV_COMPILE_FILL) {
-        static const struct { const char* name; int tx; const char* nt; } fills[] = {
-            {"tx64", 64, "false"}, {"tx64_nt", 64, "true"}, {"tx128", 128, "false"}, {"tx128_nt", 128, "true"}, {"tx256", 256, "false"}, {"tx256_nt", 256, "true"}};
-        for (const auto& f : fills)
-            append(s, "__global__ __launch_bounds__(kBlock) void sdfprogc_fill_%s(ProgramFillArgs a) { dense_fill_rows<%d, %s, false>(a, ProgramFillEval<Compiled<false>>(a, Compiled<false>{})); }\n",
-                   f.name, f.tx, f.nt);
-    }
-    if (routes & SDFV_COMPILE_POINTS)
-        s += "__global__ __launch_bounds__(kBlock) void sdfprogc_sample_points(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
-             "                                                                 const float* __restrict__ points, size_t first, size_t n,\n"
-             "                                                                 bool distance_only, float* __restrict__ out) {\n"
-             "    map_elements<3, 7>(ProgramSampleEval<Compiled<false>>{Compiled<false>{}, ops, distance_only}, points, first, n, out);\n"
-             "}\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_sample_points_staged(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
-             "                                                                        const float4* __restrict__ points, bool distance_only,\n"
-             "                                                                        float4* __restrict__ out) {\n"
-             "    map_elements_staged<3, 7>(ProgramSampleEval<Compiled<false>>{Compiled<false>{}, ops, distance_only}, points, out);\n"
-             "}\n";
-    if (routes & SDFV_COMPILE_MARCH)
-        s += "__global__ __launch_bounds__(kBlock) void sdfprogc_march(ProgramMarchArgs a) { program_march<false>(a, Compiled<true>{}); }\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_march_aux(ProgramMarchArgs a) { program_march<true>(a, Compiled<true>{}); }\n";
-    if (routes & SDFV_COMPILE_MESH)
-        // The parameter lists are those of the sdfprog_* twins (program_mesh_kernels.hip, sparse_mesh_kernels.hip), ops / n_ops
-        // included: one argument array serves either launch.  The four taps sit in tap_normal's loop, which is not unrolled: one
-        // copy of the evaluator, its operands kept from being hoisted out of that loop as in the march (Tap); the material run
-        // and the lattices stand outside any loop (Once).
-        s += "using Once = Compiled<false>;\n"
-             "using Tap = Compiled<true>;\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_mesh_lattice(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,\n"
-             "                                                                float* __restrict__ dist) {\n"
-             "    mesh_lattice_points(Once{}, g, dist);\n"
-             "}\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_mesh_vertices(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
-             "                                                                 float4* __restrict__ vertices, uint32_t n) {\n"
-             "    mesh_vertices<false>(Once{}, Tap{}, ops, vertices, n);\n"
-             "}\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_mesh_vertices_mat(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
-             "                                                                     float4* __restrict__ vertices, uint32_t n) {\n"
-             "    mesh_vertices<true>(Once{}, Tap{}, ops, vertices, n);\n"
-             "}\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_normal_points(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
-             "                                                                 const float* __restrict__ points, size_t first, size_t n,\n"
-             "                                                                 float eps, float* __restrict__ out) {\n"
-             "    map_elements<3, 3>(ProgramNormalEval<Tap>{Tap{}, eps}, points, first, n, out);\n"
-             "}\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_normal_points_staged(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
-             "                                                                        const float4* __restrict__ points, float eps,\n"
-             "                                                                        float4* __restrict__ out) {\n"
-             "    map_elements_staged<3, 3>(ProgramNormalEval<Tap>{Tap{}, eps}, points, out);\n"
-             "}\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_mesh_postproc(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
-             "                                                                 float4* __restrict__ vertices, size_t n) {\n"
-             "    mesh_postproc_aligned(Once{}, Tap{}, ops, vertices, n);\n"
-             "}\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_mesh_postproc_unaligned(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,\n"
-             "                                                                           float* __restrict__ vertices, size_t n) {\n"
-             "    mesh_postproc_words(Once{}, Tap{}, ops, vertices, n);\n"
-             "}\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_sparse_refine(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,\n"
-             "                                                                 const uint32_t* __restrict__ parents, uint32_t n, uint32_t shift,\n"
-             "                                                                 float threshold, uint32_t* __restrict__ cand,\n"
-             "                                                                 uint32_t* __restrict__ pos) {\n"
-             "    sparse_refine_children(Once{}, g, parents, n, shift, threshold, cand, pos);\n"
-             "}\n"
-             "__global__ __launch_bounds__(kBlock) void sdfprogc_sparse_bricks(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,\n"
-             "                                                                 const uint32_t* __restrict__ bricks, uint32_t n,\n"
-             "                                                                 float* __restrict__ dist) {\n"
-             "    sparse_brick_points(Once{}, g, bricks, n, dist);\n"
-             "}\n";
-    s += "}  // extern \"C\"\n";
+         "// the kernels of the routes asked for: the definitions the library's sdfprog_* twins are made from, over this program\n"
+         "#define SDFV_EVAL_ONCE(ops, n_ops) Compiled<false>{}\n"
+         "#define SDFV_EVAL_LOOPED(ops, n_ops) Compiled<true>{}\n";
+    for (int k = 0; k < sdfv::kProgramKernels; ++k)
+        if (routes & route_of(k)) append(s, "SDFV_PROGRAM_KERNEL_%s(%s)\n", kKernels[k].stem, kKernels[k].name);
     return s;
 }
 
@@ -358,10 +295,10 @@ int load_on_device(sdfv_program* p, int dev, const sdfv::CompiledProgram::Loaded
     SDFV_HIP(hipModuleLoadData(&l->module, c->code.data()));
     for (int k = 0; k < sdfv::kProgramKernels; ++k) {
         if (!(c->routes & route_of(k))) continue;
-        const hipError_t e = hipModuleGetFunction(&l->fn[k], l->module, kKernelNames[k]);
+        const hipError_t e = hipModuleGetFunction(&l->fn[k], l->module, kKernels[k].name);
         if (e != hipSuccess) {
             (void)hipModuleUnload(l->module);
-            return sdfv::hip_fail(e, kKernelNames[k]);
+            return sdfv::hip_fail(e, kKernels[k].name);
         }
     }
     *out = l.get();

@@ -1,9 +1,10 @@
 // program_device.h -- the bodies of the SDF-program kernels that exist once per way of evaluating a program: the dense fill,
-// the point samplers and the direct march, each over an EVALUATOR (program_eval.h).  hipcc instantiates them with the
-// interpreter (program_kernels.hip, program_march_kernels.hip); the translation unit that sdfv_program_compile generates
+// the point samplers and the direct march, each over an EVALUATOR (program_eval.h), and at the end the kernels themselves, each
+// stated once as a definition over two evaluator expressions.  hipcc instantiates them with the interpreter
+// (program_kernels.hip, program_march_kernels.hip); the translation unit that sdfv_program_compile generates
 // (program_compile.hip) includes this very text and instantiates it with the evaluator of one program.  Everything else of a
-// kernel -- skeleton, texel packing, material fetch, stores -- is the same code either way, which is why the two give the
-// same bits.
+// kernel -- parameters, skeleton, texel packing, material fetch, stores -- is the same code either way, which is why the two
+// take the same arguments and give the same bits.
 #pragma once
 
 #include "kernel_common.h"
@@ -66,3 +67,44 @@ __device__ __forceinline__ void program_march(const ProgramMarchArgs& a, const E
 }
 
 }  // namespace sdfv
+
+// ---- the kernels: SDFV_PROGRAM_KERNEL_<stem>(name), one per row of SDFV_PROGRAM_KERNELS (program_kernels.h) ----
+// Each states a kernel's parameter list and body ONCE; the translation unit that invokes it has defined the two evaluators:
+//   SDFV_EVAL_ONCE(ops, n_ops)    the program where it is run outside any loop (the fill, the samplers, the lattices, the
+//                                 material run),
+//   SDFV_EVAL_LOOPED(ops, n_ops)  ... and inside one (the march, the four taps of a normal).
+// In the library both are prog::Interpreter{ops, n_ops} and the name is sdfprog_<stem>; in the unit sdfv_program_compile
+// generates they are Compiled<false>{} and Compiled<true>{}, which ignore their arguments, and the name is sdfprogc_<stem>.  So
+// the two kernels of a pair cannot differ in their parameters: ProgramKernels::launch hands either the same argument array.
+#define SDFV_PROGRAM_KERNEL_FILL(name, TX, NT)                                       \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(ProgramFillArgs a) {  \
+        dense_fill_rows<TX, NT, false>(a, ProgramFillEval(a, SDFV_EVAL_ONCE(a.ops, a.n_ops))); \
+    }
+#define SDFV_PROGRAM_KERNEL_fill_tx64(name) SDFV_PROGRAM_KERNEL_FILL(name, 64, false)
+#define SDFV_PROGRAM_KERNEL_fill_tx64_nt(name) SDFV_PROGRAM_KERNEL_FILL(name, 64, true)
+#define SDFV_PROGRAM_KERNEL_fill_tx128(name) SDFV_PROGRAM_KERNEL_FILL(name, 128, false)
+#define SDFV_PROGRAM_KERNEL_fill_tx128_nt(name) SDFV_PROGRAM_KERNEL_FILL(name, 128, true)
+#define SDFV_PROGRAM_KERNEL_fill_tx256(name) SDFV_PROGRAM_KERNEL_FILL(name, 256, false)
+#define SDFV_PROGRAM_KERNEL_fill_tx256_nt(name) SDFV_PROGRAM_KERNEL_FILL(name, 256, true)
+
+#define SDFV_PROGRAM_KERNEL_sample_points(name)                                                                        \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,   \
+                                                              const float* __restrict__ points, size_t first, size_t n, \
+                                                              bool distance_only, float* __restrict__ out) {          \
+        auto eval = SDFV_EVAL_ONCE(ops, n_ops);                                                                        \
+        map_elements<3, 7>(ProgramSampleEval<decltype(eval)>{eval, ops, distance_only}, points, first, n, out);        \
+    }
+#define SDFV_PROGRAM_KERNEL_sample_points_staged(name)                                                                 \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,   \
+                                                              const float4* __restrict__ points, bool distance_only,  \
+                                                              float4* __restrict__ out) {                             \
+        auto eval = SDFV_EVAL_ONCE(ops, n_ops);                                                                        \
+        map_elements_staged<3, 7>(ProgramSampleEval<decltype(eval)>{eval, ops, distance_only}, points, out);           \
+    }
+
+#define SDFV_PROGRAM_KERNEL_MARCH(name, AUX)                                          \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(ProgramMarchArgs a) {  \
+        program_march<AUX>(a, SDFV_EVAL_LOOPED(a.f.ops, a.f.n_ops));                  \
+    }
+#define SDFV_PROGRAM_KERNEL_march(name) SDFV_PROGRAM_KERNEL_MARCH(name, false)
+#define SDFV_PROGRAM_KERNEL_march_aux(name) SDFV_PROGRAM_KERNEL_MARCH(name, true)

@@ -14,12 +14,11 @@
 
 namespace sdfv {
 
-extern "C" {
+// the interpreter as the evaluator of the kernel definitions (program_device.h)
+#define SDFV_EVAL_LOOPED(ops, n_ops) prog::Interpreter{ops, n_ops}
 
-__global__ __launch_bounds__(kBlock) void sdfprog_march(ProgramMarchArgs a) { program_march<false>(a, prog::Interpreter{a.f.ops, a.f.n_ops}); }
-__global__ __launch_bounds__(kBlock) void sdfprog_march_aux(ProgramMarchArgs a) { program_march<true>(a, prog::Interpreter{a.f.ops, a.f.n_ops}); }
-
-}  // extern "C"
+SDFV_PROGRAM_KERNEL_march(sdfprog_march)
+SDFV_PROGRAM_KERNEL_march_aux(sdfprog_march_aux)
 
 hipError_t launch_program_march(const ProgramMarchArgs& a, const ProgramKernels& k, hipStream_t stream) {
     if (a.f.width == 0 || a.y1 <= a.y0 || a.n_cameras == 0) return hipSuccess;
@@ -27,11 +26,8 @@ hipError_t launch_program_march(const ProgramMarchArgs& a, const ProgramKernels&
     const uint32_t tiles_x = (a.f.width + 15) / 16, tiles_y = (a.y1 - a.y0 + 15) / 16;
     if (tiles_y > 65535u) return hipErrorInvalidValue;
     void* params[] = {const_cast<ProgramMarchArgs*>(&a)};
-    bool mine = false;
-    const hipError_t e = k.launch(a.aux ? kKernelMarchAux : kKernelMarch, dim3(tiles_x, tiles_y, a.n_cameras), dim3(kBlock), params, stream, &mine);
-    if (mine) return e;
-    hipLaunchKernelGGL(a.aux ? sdfprog_march_aux : sdfprog_march, dim3(tiles_x, tiles_y, a.n_cameras), dim3(kBlock), 0, stream, a);
-    return hipGetLastError();
+    return k.launch(a.aux ? kKernelMarchAux : kKernelMarch, a.aux ? (const void*)sdfprog_march_aux : (const void*)sdfprog_march,
+                    dim3(tiles_x, tiles_y, a.n_cameras), dim3(kBlock), params, stream);
 }
 
 }  // namespace sdfv

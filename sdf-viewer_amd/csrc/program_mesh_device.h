@@ -2,8 +2,9 @@
 // program_device.h has the fill's, the samplers' and the march's: the lattice, the vertex phase, the batched normal,
 // Mesh::postproc (program_mesh_kernels.hip) and the two evaluating kernels of the sparse route (sparse_mesh_kernels.hip).  hipcc
 // instantiates them with the interpreter; the translation unit that sdfv_program_compile generates for SDFV_COMPILE_MESH
-// (program_compile.hip) includes this very text and instantiates it with the evaluator of one program.  Index arithmetic, masks
-// and stores are the same code either way, which is why the two give the same bits.
+// (program_compile.hip) includes this very text and instantiates it with the evaluator of one program.  The nine kernels
+// themselves are stated at the end, once each, as definitions over the two evaluator expressions.  Parameters, index
+// arithmetic, masks and stores are the same code either way, which is why the two take the same arguments and give the same bits.
 #pragma once
 
 #include "kernel_common.h"
@@ -209,3 +210,57 @@ __device__ __forceinline__ void sparse_brick_points(const Eval& eval, const Mesh
 }
 
 }  // namespace sdfv
+
+// ---- the kernels of SDFV_COMPILE_MESH: SDFV_PROGRAM_KERNEL_<stem>(name) over SDFV_EVAL_ONCE / SDFV_EVAL_LOOPED, as in
+// program_device.h.  The four taps sit in tap_normal's loop, which is not unrolled: one copy of the evaluator, the looped one
+// (a compiled program keeps its operands from being hoisted out of that loop, as in the march); the material run and the
+// lattices stand outside any loop. ----
+#define SDFV_PROGRAM_KERNEL_mesh_lattice(name)                                                                                \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g, \
+                                                              float* __restrict__ dist) {                                    \
+        mesh_lattice_points(SDFV_EVAL_ONCE(ops, n_ops), g, dist);                                                             \
+    }
+#define SDFV_PROGRAM_KERNEL_MESH_VERTICES(name, MAT)                                                                         \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,          \
+                                                              float4* __restrict__ vertices, uint32_t n) {                   \
+        mesh_vertices<MAT>(SDFV_EVAL_ONCE(ops, n_ops), SDFV_EVAL_LOOPED(ops, n_ops), ops, vertices, n);                       \
+    }
+#define SDFV_PROGRAM_KERNEL_mesh_vertices(name) SDFV_PROGRAM_KERNEL_MESH_VERTICES(name, false)
+#define SDFV_PROGRAM_KERNEL_mesh_vertices_mat(name) SDFV_PROGRAM_KERNEL_MESH_VERTICES(name, true)
+#define SDFV_PROGRAM_KERNEL_normal_points(name)                                                                              \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,          \
+                                                              const float* __restrict__ points, size_t first, size_t n,      \
+                                                              float eps, float* __restrict__ out) {                          \
+        auto tap = SDFV_EVAL_LOOPED(ops, n_ops);                                                                              \
+        map_elements<3, 3>(ProgramNormalEval<decltype(tap)>{tap, eps}, points, first, n, out);                                \
+    }
+#define SDFV_PROGRAM_KERNEL_normal_points_staged(name)                                                                       \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,          \
+                                                              const float4* __restrict__ points, float eps,                  \
+                                                              float4* __restrict__ out) {                                    \
+        auto tap = SDFV_EVAL_LOOPED(ops, n_ops);                                                                              \
+        map_elements_staged<3, 3>(ProgramNormalEval<decltype(tap)>{tap, eps}, points, out);                                   \
+    }
+#define SDFV_PROGRAM_KERNEL_mesh_postproc(name)                                                                              \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,          \
+                                                              float4* __restrict__ vertices, size_t n) {                     \
+        mesh_postproc_aligned(SDFV_EVAL_ONCE(ops, n_ops), SDFV_EVAL_LOOPED(ops, n_ops), ops, vertices, n);                    \
+    }
+#define SDFV_PROGRAM_KERNEL_mesh_postproc_unaligned(name)                                                                    \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,          \
+                                                              float* __restrict__ vertices, size_t n) {                      \
+        mesh_postproc_words(SDFV_EVAL_ONCE(ops, n_ops), SDFV_EVAL_LOOPED(ops, n_ops), ops, vertices, n);                      \
+    }
+#define SDFV_PROGRAM_KERNEL_sparse_refine(name)                                                                              \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g, \
+                                                              const uint32_t* __restrict__ parents, uint32_t n, uint32_t shift, \
+                                                              float threshold, uint32_t* __restrict__ cand,                  \
+                                                              uint32_t* __restrict__ pos) {                                  \
+        sparse_refine_children(SDFV_EVAL_ONCE(ops, n_ops), g, parents, n, shift, threshold, cand, pos);                       \
+    }
+#define SDFV_PROGRAM_KERNEL_sparse_bricks(name)                                                                              \
+    extern "C" __global__ __launch_bounds__(kBlock) void name(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g, \
+                                                              const uint32_t* __restrict__ bricks, uint32_t n,               \
+                                                              float* __restrict__ dist) {                                    \
+        sparse_brick_points(SDFV_EVAL_ONCE(ops, n_ops), g, bricks, n, dist);                                                  \
+    }

@@ -22,54 +22,20 @@
 
 namespace sdfv {
 
-// The bodies are program_mesh_device.h's, over an evaluator: here the interpreter, in the kernels a handle compiled with
-// SDFV_COMPILE_MESH brings (program_compile.hip) that program's own.  Each launcher below tries the handle's kernel first
-// (ProgramKernels::launch) over ONE argument array -- the two kernels of a pair have the same parameter list -- and launches the
-// interpreter's otherwise, with the same grid, block and stream.
-namespace {
-using Interp = prog::Interpreter;
-}  // namespace
+// The kernels are program_mesh_device.h's definitions with the interpreter as both evaluators; a handle compiled with
+// SDFV_COMPILE_MESH brings the same definitions over that program's own (program_compile.hip).  Each launcher below builds ONE
+// argument array and ProgramKernels::launch hands it to the handle's kernel or to the interpreter's, with the same grid, block
+// and stream.
+#define SDFV_EVAL_ONCE(ops, n_ops) prog::Interpreter{ops, n_ops}
+#define SDFV_EVAL_LOOPED(ops, n_ops) prog::Interpreter{ops, n_ops}
 
-extern "C" {
-
-__global__ __launch_bounds__(kBlock) void sdfprog_mesh_lattice(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,
-                                                               float* __restrict__ dist) {
-    mesh_lattice_points(Interp{ops, n_ops}, g, dist);
-}
-
-__global__ __launch_bounds__(kBlock) void sdfprog_mesh_vertices(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
-                                                                float4* __restrict__ vertices, uint32_t n) {
-    mesh_vertices<false>(Interp{ops, n_ops}, Interp{ops, n_ops}, ops, vertices, n);
-}
-
-__global__ __launch_bounds__(kBlock) void sdfprog_mesh_vertices_mat(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
-                                                                    float4* __restrict__ vertices, uint32_t n) {
-    mesh_vertices<true>(Interp{ops, n_ops}, Interp{ops, n_ops}, ops, vertices, n);
-}
-
-__global__ __launch_bounds__(kBlock) void sdfprog_normal_points(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
-                                                                const float* __restrict__ points, size_t first, size_t n,
-                                                                float eps, float* __restrict__ out) {
-    map_elements<3, 3>(ProgramNormalEval<Interp>{Interp{ops, n_ops}, eps}, points, first, n, out);
-}
-
-__global__ __launch_bounds__(kBlock) void sdfprog_normal_points_staged(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
-                                                                       const float4* __restrict__ points, float eps,
-                                                                       float4* __restrict__ out) {
-    map_elements_staged<3, 3>(ProgramNormalEval<Interp>{Interp{ops, n_ops}, eps}, points, out);
-}
-
-__global__ __launch_bounds__(kBlock) void sdfprog_mesh_postproc(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
-                                                                float4* __restrict__ vertices, size_t n) {
-    mesh_postproc_aligned(Interp{ops, n_ops}, Interp{ops, n_ops}, ops, vertices, n);
-}
-
-__global__ __launch_bounds__(kBlock) void sdfprog_mesh_postproc_unaligned(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops,
-                                                                          float* __restrict__ vertices, size_t n) {
-    mesh_postproc_words(Interp{ops, n_ops}, Interp{ops, n_ops}, ops, vertices, n);
-}
-
-}  // extern "C"
+SDFV_PROGRAM_KERNEL_mesh_lattice(sdfprog_mesh_lattice)
+SDFV_PROGRAM_KERNEL_mesh_vertices(sdfprog_mesh_vertices)
+SDFV_PROGRAM_KERNEL_mesh_vertices_mat(sdfprog_mesh_vertices_mat)
+SDFV_PROGRAM_KERNEL_normal_points(sdfprog_normal_points)
+SDFV_PROGRAM_KERNEL_normal_points_staged(sdfprog_normal_points_staged)
+SDFV_PROGRAM_KERNEL_mesh_postproc(sdfprog_mesh_postproc)
+SDFV_PROGRAM_KERNEL_mesh_postproc_unaligned(sdfprog_mesh_postproc_unaligned)
 
 hipError_t launch_program_mesh_lattice(const sdfv_prog_op* ops, uint32_t n_ops, const MeshGrid& g, const MeshWork& w,
                                        const ProgramKernels& k, hipStream_t stream) {
@@ -77,11 +43,7 @@ hipError_t launch_program_mesh_lattice(const sdfv_prog_op* ops, uint32_t n_ops, 
     MeshGrid grid = g;
     float* dist = w.dist;
     void* params[] = {&ops, &n_ops, &grid, &dist};
-    bool mine = false;
-    const hipError_t e = k.launch(kKernelMeshLattice, dim3(blocks_for(g.n_points())), dim3(kBlock), params, stream, &mine);
-    if (mine) return e;
-    hipLaunchKernelGGL(sdfprog_mesh_lattice, dim3(blocks_for(g.n_points())), dim3(kBlock), 0, stream, ops, n_ops, g, w.dist);
-    return hipGetLastError();
+    return k.launch(kKernelMeshLattice, (const void*)sdfprog_mesh_lattice, dim3(blocks_for(g.n_points())), dim3(kBlock), params, stream);
 }
 
 hipError_t launch_program_vertex_normals(const sdfv_prog_op* ops, uint32_t n_ops, sdfv_vertex* vertices, size_t n_vertices,
@@ -91,36 +53,27 @@ hipError_t launch_program_vertex_normals(const sdfv_prog_op* ops, uint32_t n_ops
     float4* v4 = reinterpret_cast<float4*>(vertices);
     uint32_t n = (uint32_t)n_vertices;
     void* params[] = {&ops, &n_ops, &v4, &n};
-    bool mine = false;
-    const hipError_t e = k.launch(materials ? kKernelMeshVerticesMat : kKernelMeshVertices, dim3(blocks_for(n_vertices)), dim3(kBlock),
-                                  params, stream, &mine);
-    if (mine) return e;
-    hipLaunchKernelGGL(materials ? sdfprog_mesh_vertices_mat : sdfprog_mesh_vertices, dim3(blocks_for(n_vertices)), dim3(kBlock), 0,
-                       stream, ops, n_ops, v4, n);
-    return hipGetLastError();
+    return k.launch(materials ? kKernelMeshVerticesMat : kKernelMeshVertices,
+                    materials ? (const void*)sdfprog_mesh_vertices_mat : (const void*)sdfprog_mesh_vertices,
+                    dim3(blocks_for(n_vertices)), dim3(kBlock), params, stream);
 }
 
 hipError_t launch_program_normal_points(const sdfv_prog_op* ops, uint32_t n_ops, const float* points, size_t n, float eps,
                                         float* out, const ProgramKernels& k, hipStream_t stream) {
-    hipError_t first = hipSuccess;  // of the specialised launches (the interpreter's report through hipGetLastError)
-    bool mine = false;
+    hipError_t first = hipSuccess;  // of the launches
     const hipError_t e = launch_staged_then_tail(
         n, (((uintptr_t)points | (uintptr_t)out) & 15) == 0,
         [&](uint32_t whole) {
             const float4* in4 = reinterpret_cast<const float4*>(points);
             float4* out4 = reinterpret_cast<float4*>(out);
             void* params[] = {&ops, &n_ops, &in4, &eps, &out4};
-            const hipError_t es = k.launch(kKernelNormalPointsStaged, dim3(whole), dim3(kBlock), params, stream, &mine);
+            const hipError_t es = k.launch(kKernelNormalPointsStaged, (const void*)sdfprog_normal_points_staged, dim3(whole), dim3(kBlock), params, stream);
             if (first == hipSuccess) first = es;
-            if (mine) return;
-            hipLaunchKernelGGL(sdfprog_normal_points_staged, dim3(whole), dim3(kBlock), 0, stream, ops, n_ops, in4, eps, out4);
         },
         [&](uint32_t blocks, size_t done) {
             void* params[] = {&ops, &n_ops, &points, &done, &n, &eps, &out};
-            const hipError_t es = k.launch(kKernelNormalPoints, dim3(blocks), dim3(kBlock), params, stream, &mine);
+            const hipError_t es = k.launch(kKernelNormalPoints, (const void*)sdfprog_normal_points, dim3(blocks), dim3(kBlock), params, stream);
             if (first == hipSuccess) first = es;
-            if (mine) return;
-            hipLaunchKernelGGL(sdfprog_normal_points, dim3(blocks), dim3(kBlock), 0, stream, ops, n_ops, points, done, n, eps, out);
         });
     return first != hipSuccess ? first : e;
 }
@@ -132,17 +85,9 @@ hipError_t launch_program_mesh_postproc(const sdfv_prog_op* ops, uint32_t n_ops,
     if (!blocks) return hipErrorInvalidValue;
     const bool aligned = ((uintptr_t)vertices & 15) == 0;
     void* params[] = {&ops, &n_ops, &vertices, &n};  // (float4* or float*: a pointer either way)
-    bool mine = false;
-    const hipError_t e = k.launch(aligned ? kKernelMeshPostproc : kKernelMeshPostprocUnaligned, dim3(blocks), dim3(kBlock), params,
-                                  stream, &mine);
-    if (mine) return e;
-    if (aligned)
-        hipLaunchKernelGGL(sdfprog_mesh_postproc, dim3(blocks), dim3(kBlock), 0, stream, ops, n_ops,
-                           reinterpret_cast<float4*>(vertices), n);
-    else
-        hipLaunchKernelGGL(sdfprog_mesh_postproc_unaligned, dim3(blocks), dim3(kBlock), 0, stream, ops, n_ops,
-                           reinterpret_cast<float*>(vertices), n);
-    return hipGetLastError();
+    return k.launch(aligned ? kKernelMeshPostproc : kKernelMeshPostprocUnaligned,
+                    aligned ? (const void*)sdfprog_mesh_postproc : (const void*)sdfprog_mesh_postproc_unaligned, dim3(blocks),
+                    dim3(kBlock), params, stream);
 }
 
 }  // namespace sdfv

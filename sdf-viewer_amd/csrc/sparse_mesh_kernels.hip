@@ -16,8 +16,9 @@
 //    neighbours, which sparse_brick_neighbours has looked up once per brick by binary search in the brick list (sorted by Morton
 //    key; a directory of (cells / 4)^3 words would be 4 GiB at 4096 cells).  A cell whose crossing edge has no owner among the
 //    bricks (the program broke its Lipschitz promise) emits nothing: no index is ever out of range.
-// The bodies of the two evaluating kernels are program_mesh_device.h's, over an evaluator: the interpreter here, one program's own
-// in the kernels a handle compiled with SDFV_COMPILE_MESH brings, which the two launchers then launch in these kernels' place.
+// The two evaluating kernels are program_mesh_device.h's definitions (SDFV_PROGRAM_KERNEL_sparse_refine, _sparse_bricks) with the
+// interpreter as the evaluator; a handle compiled with SDFV_COMPILE_MESH brings the same definitions over that program's own, and
+// ProgramKernels::launch hands either the one argument array its launcher builds.
 // A block is its Morton key in units of its own side, x the lowest bit; keys are below 2^30 (1024 bricks per axis at the most).
 // The kernels carry C names: tests and profiles find them under the same symbol whatever the toolchain mangles.
 #include "sparse_mesh_kernels.h"
@@ -113,14 +114,12 @@ __device__ __forceinline__ uint32_t edge_owner_slot(const uint32_t* __restrict__
 
 }  // namespace
 
-extern "C" {
+// the two evaluating kernels: program_mesh_device.h's definitions with the interpreter as the evaluator
+#define SDFV_EVAL_ONCE(ops, n_ops) prog::Interpreter{ops, n_ops}
+SDFV_PROGRAM_KERNEL_sparse_refine(sdfprog_sparse_refine)
+SDFV_PROGRAM_KERNEL_sparse_bricks(sdfprog_sparse_bricks)
 
-__global__ __launch_bounds__(kBlock) void sdfprog_sparse_refine(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,
-                                                                const uint32_t* __restrict__ parents, uint32_t n, uint32_t shift,
-                                                                float threshold, uint32_t* __restrict__ cand,
-                                                                uint32_t* __restrict__ pos) {
-    sparse_refine_children(prog::Interpreter{ops, n_ops}, g, parents, n, shift, threshold, cand, pos);
-}
+extern "C" {
 
 // survivors up, in order; the last thread leaves their number
 __global__ __launch_bounds__(kBlock) void sparse_compact(const uint32_t* __restrict__ cand, const uint32_t* __restrict__ pos,
@@ -130,12 +129,6 @@ __global__ __launch_bounds__(kBlock) void sparse_compact(const uint32_t* __restr
     const uint32_t c = cand[t], at = pos[t];
     if (c & kSparseKept) list[at] = c & ~kSparseKept;
     if (t == n - 1) *kept = at + (c >> 31);
-}
-
-__global__ __launch_bounds__(kBlock) void sdfprog_sparse_bricks(const sdfv_prog_op* __restrict__ ops, uint32_t n_ops, MeshGrid g,
-                                                                const uint32_t* __restrict__ bricks, uint32_t n,
-                                                                float* __restrict__ dist) {
-    sparse_brick_points(prog::Interpreter{ops, n_ops}, g, bricks, n, dist);
 }
 
 // Which of the point's three +axis edges the brick owns and cross; count -> scan input.  n = 125 * bricks; thread n writes the
@@ -242,11 +235,9 @@ hipError_t launch_sparse_refine(const sdfv_prog_op* ops, uint32_t n_ops, const M
     const uint32_t* parents = w.list;
     uint32_t *cand = w.cand, *pos = w.pos;
     void* params[] = {&ops, &n_ops, &grid, &parents, &n, &shift, &threshold, &cand, &pos};
-    bool mine = false;
-    if (hipError_t e = k.launch(kKernelSparseRefine, dim3(blocks_for(n)), dim3(kBlock), params, stream, &mine); e != hipSuccess) return e;
-    if (!mine)
-        hipLaunchKernelGGL(sdfprog_sparse_refine, dim3(blocks_for(n)), dim3(kBlock), 0, stream, ops, n_ops, g, w.list, n, shift,
-                           threshold, w.cand, w.pos);
+    if (hipError_t e = k.launch(kKernelSparseRefine, (const void*)sdfprog_sparse_refine, dim3(blocks_for(n)), dim3(kBlock), params, stream);
+        e != hipSuccess)
+        return e;
     if (hipError_t e = mesh_exclusive_scan(w.mesh, w.pos, n, stream); e != hipSuccess) return e;
     hipLaunchKernelGGL(sparse_compact, dim3(blocks_for(n)), dim3(kBlock), 0, stream, w.cand, w.pos, n, w.list, kept_dev);
     return hipGetLastError();
@@ -260,11 +251,7 @@ hipError_t launch_sparse_brick_lattice(const sdfv_prog_op* ops, uint32_t n_ops, 
     const uint32_t* bricks = w.list;
     float* dist = w.mesh.dist;
     void* params[] = {&ops, &n_ops, &grid, &bricks, &n, &dist};
-    bool mine = false;
-    const hipError_t e = k.launch(kKernelSparseBricks, dim3(blocks_for(n)), dim3(kBlock), params, stream, &mine);
-    if (mine) return e;
-    hipLaunchKernelGGL(sdfprog_sparse_bricks, dim3(blocks_for(n)), dim3(kBlock), 0, stream, ops, n_ops, g, w.list, n, w.mesh.dist);
-    return hipGetLastError();
+    return k.launch(kKernelSparseBricks, (const void*)sdfprog_sparse_bricks, dim3(blocks_for(n)), dim3(kBlock), params, stream);
 }
 
 hipError_t launch_sparse_count(const MeshGrid& g, const SparseWork& w, uint32_t n_bricks, hipStream_t stream) {

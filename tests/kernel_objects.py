@@ -15,6 +15,12 @@ def have_llvm_tools():
     return all(os.path.exists(os.path.join(LLVM_TOOLS, t)) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf", "llvm-objdump"))
 
 
+def bare_code_object(co):
+    """One gfx950 code object that is a file of its own (sdfv_program_compiled_code), in unbundle()'s form."""
+    notes = subprocess.run([f"{LLVM_TOOLS}/llvm-readelf", "--notes", str(co)], check=True, capture_output=True, text=True).stdout
+    return [(co, notes)]
+
+
 def unbundle(lib, tmp_path):
     """Every gfx950 code object inside the library `lib`, unbundled under tmp_path: [(path of the .co, text of its metadata notes)]."""
     fat = tmp_path / "fat.bin"
@@ -53,6 +59,23 @@ def kernel_table(code_objects):
             table[name] = dict(vgpr=field("vgpr_count"), sgpr=field("sgpr_count"), vgpr_spill=field("vgpr_spill_count"),
                                sgpr_spill=field("sgpr_spill_count"), lds=field("group_segment_fixed_size"),
                                scratch=field("private_segment_fixed_size"), kernarg=field("kernarg_segment_size"), co=co)
+    return table
+
+
+def kernel_args(code_objects):
+    """mangled name -> [(offset, size, value_kind), ...]: the explicit kernel arguments, in order, from the `.args` list of the
+    code objects' metadata (the hidden_* entries the compiler appends are no part of a launch's argument array)."""
+    table = {}
+    for _, notes in code_objects:
+        for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
+            name = re.search(r"\n\s+\.name:\s+(\S+)\n\s+\.private_segment_fixed_size", blk).group(1)
+            listed = re.search(r"\n\s+\.args:\n(.*?)\n    \.\w+:", blk, re.S)
+            args = []
+            for entry in re.split(r"\n\s+- ", "\n" + listed.group(1))[1:] if listed else []:
+                f = dict(re.findall(r"\.(\w+):\s+(\S+)", entry))
+                if not f["value_kind"].startswith("hidden_"):
+                    args.append((int(f["offset"]), int(f["size"]), f["value_kind"]))
+            table[name] = args
     return table
 
 

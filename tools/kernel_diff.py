@@ -4,6 +4,12 @@ tests/test_abi.py reads (registers, spills, LDS, scratch, kernel-argument bytes)
 (opcode plus the `nt` marker).  Reads the code objects with the LLVM binary tools only (tests/kernel_objects.py).
 
     python tools/kernel_diff.py OLD/libsdfgrid.so NEW/libsdfgrid.so [--pair OLD_SYMBOL=NEW_SYMBOL ...] [--new-ok]
+    python tools/kernel_diff.py --dump-compiled DIR [--tree ROOT]      # the kernels sdfv_program_compile builds, as DIR/<program>.co
+    python tools/kernel_diff.py OLD_DIR/demo3.co NEW_DIR/demo3.co      # ... and two of those compared the same way
+
+An argument that is no .so is read as a bare gfx950 code object.  --dump-compiled: every program of PROGRAMS in
+tests/test_program_compile_mesh_cpu.py compiled with all four routes for gfx950 (no device needed) by the library of the source
+tree ROOT (default: this one), compiled_code() of each written to DIR.
 
 --pair matches a kernel whose symbol changed with its predecessor.  --new-ok: a change that ADDS kernels -- those only in NEW are
 listed with their metadata and are no failure (a kernel only in OLD still is).  The disassembler's "..." (how llvm-objdump prints
@@ -20,7 +26,7 @@ import tempfile
 from collections import Counter
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-from kernel_objects import kernel_table, opcodes, unbundle  # noqa: E402
+from kernel_objects import bare_code_object, kernel_table, opcodes, unbundle  # noqa: E402
 
 EQUAL = ("lds", "scratch", "vgpr_spill", "sgpr_spill", "kernarg")
 
@@ -31,23 +37,49 @@ def build_id(lib):
     return f().decode()
 
 
+def code_objects_of(path, tmp):
+    """unbundle() of a library, or the one bare code object `path` is."""
+    return unbundle(path, tmp) if path.endswith(".so") else bare_code_object(path)
+
+
+def dump_compiled(out_dir, tree):
+    sys.path.insert(0, tree)
+    import importlib
+    import program_compile_cases as CC
+    from test_program_compile_cpu import builders
+    from test_program_compile_mesh_cpu import PROGRAMS
+    PM = importlib.import_module("sdf-viewer_amd.program")
+    b = dict(builders(PM))
+    b.update(CC.folding_programs(PM))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in PROGRAMS:
+        c = b[name].build().compile(PM.FILL | PM.POINTS | PM.MARCH | PM.MESH, arch="gfx950")
+        pathlib.Path(out_dir, name + ".co").write_bytes(c.compiled_code())
+    print(f"{len(PROGRAMS)} code objects in {out_dir} (library of {tree})")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("old")
-    ap.add_argument("new")
+    ap.add_argument("old", nargs="?")
+    ap.add_argument("new", nargs="?")
+    ap.add_argument("--dump-compiled", metavar="DIR")
+    ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--pair", action="append", default=[], metavar="OLD=NEW")
     ap.add_argument("--new-ok", action="store_true")
     args = ap.parse_args()
+    if args.dump_compiled:
+        return dump_compiled(args.dump_compiled, os.path.abspath(args.tree))
     renamed = dict(p.split("=", 1) for p in args.pair)
     with tempfile.TemporaryDirectory() as tmp:
         tables = []
         for k, lib in enumerate((args.old, args.new)):
             d = pathlib.Path(tmp) / str(k)
             d.mkdir()
-            tables.append(kernel_table(unbundle(lib, d)))
+            tables.append(kernel_table(code_objects_of(lib, d)))
         old, new = tables
-        print(f"old: {args.old}  build id {build_id(args.old)}  {len(old)} kernels")
-        print(f"new: {args.new}  build id {build_id(args.new)}  {len(new)} kernels")
+        for tag, lib, table in (("old", args.old, old), ("new", args.new, new)):
+            print(f"{tag}: {lib}  " + (f"build id {build_id(lib)}  " if lib.endswith(".so") else "") + f"{len(table)} kernels")
         bad = False
         for o, n in renamed.items():
             print(f"paired by hand: {o}\n            -> {n}")
