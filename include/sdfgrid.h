@@ -924,6 +924,81 @@ int sdfv_program_raymarch(const sdfv_program_march_desc *desc, void *stream);
  * that both routes refuse the same descriptors with the same messages.  Output pointers are checked for alignment only. */
 int sdfv_program_raymarch_check(const sdfv_program_march_desc *desc, sdfv_program_march_desc *checked, float *normal_h);
 
+/* ---- SDF programs: a list of rays cast on the device, hits with normals and materials ----
+ * The batched form of "where does this ray hit?": picking, probe and collision rays, shadow and occlusion rays, a range-sensor
+ * sweep, a camera model of the caller's own.  n rays in, n records out, in list order; nothing goes through a camera, nothing is
+ * shifted, nothing is packed.  Arithmetic is IEEE f32, every step rounded on its own, left to right, nothing contracted.  Per ray:
+ *   u = dir / length(dir), length = sqrt(x*x + y*y + z*z): one length, three divisions
+ *   the slab test over the descriptor's box [lo, hi] from `origin` along u, per axis a: ta1 = (lo[a] - origin[a]) / u[a],
+ *     ta2 = (hi[a] - origin[a]) / u[a]; tnear = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2)),
+ *     tfar = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2))      (sdfv_program_raymarch's six divisions)
+ *   t0 = fmaxf(t_min, tnear); t1 = fminf(t_max, tfar)
+ *   if !(t1 >= t0 && tfar >= tnear): status 0 and every other field 0 -- a ray off the box, an empty interval, a NaN or zero
+ *     direction, a NaN origin (fmaxf / fminf drop a NaN operand: the second comparison, implied by the first for numbers, is
+ *     what refuses a ray whose slab values are all NaN)
+ *   t = t0; steps = 0; status = -1; then at most max_steps times:
+ *     p = origin + u * t                  (per axis one product and one sum, from t: the position is not accumulated)
+ *     v = program(p); steps += 1
+ *     if v.d < hit_eps: status = 1, stop  (a ray that starts inside the solid hits at t0)
+ *     t = t + v.d
+ *     if t > t1: status = -2, stop        (it left the interval: a miss)
+ *   pos = the last p evaluated, t as the loop left it; status -1: out of steps (a grazing ray, or a NaN distance: it runs the
+ *     loop out and never hangs it)
+ *   at status 1 only:
+ *     sample = sample(pos, false): the seven floats sdfv_program_sample_points writes for pos (SDFV_CAST_MATERIALS; without it
+ *              sample.distance = v.d and the six material fields are 0)
+ *     normal = normal(pos, normal_eps): the bits sdfv_program_normal_points writes for pos (SDFV_CAST_NORMALS; without it 0)
+ *   at every other status sample and normal are 0.
+ * The loop is bounded by max_steps <= 4096 runs of at most SDFV_PROGRAM_MAX_OPS instructions.  Per-ray data is never validated:
+ * garbage gives status 0 or a bounded loop.  A program whose distance overestimates (a Lipschitz bound above 1) may step past a
+ * surface here exactly as it does in sdfv_program_raymarch.
+ * `size` = sizeof(sdfv_program_cast_desc) as the CALLER compiled it, with sdfv_march_desc's rule: a shorter descriptor's absent
+ * fields are 0, and bytes beyond what this library knows must be 0.
+ *   bb_min, bb_max  HOST, 3 floats each, free again when the call returns; both NULL = the box the program was created with
+ *   rays, hits      DEVICE, n each, 4-byte aligned; arrays that are 16-byte aligned are read and written by 16-byte accesses
+ *   max_steps       0 = 256, otherwise 1 .. 4096;  hit_eps  0 = 1e-5f;  normal_eps  0 = 0.001f (normal(p, None)); both otherwise
+ *                   finite and > 0
+ * n == 0 succeeds and touches nothing.  The call only enqueues on `stream`; two calls with equal arguments write equal bytes, and
+ * every byte is what the host mirror (sdfprogram.h, sdfv_program_raycast_host) computes.  A handle from sdfv_program_compile is
+ * accepted and interpreted: the cast is no compiled route. */
+typedef struct sdfv_ray {
+    float origin[3];
+    float t_min;
+    float dir[3]; /* any length but 0: normalised by the library */
+    float t_max;
+} sdfv_ray; /* 32 bytes */
+typedef struct sdfv_ray_hit {
+    int32_t status; /* 1 hit | 0 off the box or an empty interval | -1 out of steps | -2 left [t0, t1] */
+    int32_t steps;  /* evaluations of the program by the march */
+    float t;
+    float pos[3];
+    float normal[3];
+    sdfv_sample sample;
+} sdfv_ray_hit; /* 64 bytes */
+#define SDFV_CAST_NORMALS   1u
+#define SDFV_CAST_MATERIALS 2u
+typedef struct sdfv_program_cast_desc {
+    uint32_t size;
+    uint32_t reserved; /* 0 */
+    const sdfv_program *program;
+    const float *bb_min, *bb_max;
+    const sdfv_ray *rays;
+    sdfv_ray_hit *hits;
+    uint64_t n;
+    uint32_t flags; /* 0 or SDFV_CAST_* */
+    uint32_t max_steps;
+    float hit_eps;
+    float normal_eps;
+} sdfv_program_cast_desc;
+/* Argument errors (SDFV_ERR_INVALID_ARGUMENT) in this order: desc NULL, size, reserved, program NULL, half a box, a flat, reversed
+ * or non-finite box, rays or hits NULL with n > 0, alignment, flags, max_steps, hit_eps, normal_eps.  Then it needs a device
+ * (SDFV_ERR_NO_DEVICE without one, nothing computed). */
+int sdfv_program_raycast(const sdfv_program_cast_desc *desc, void *stream);
+/* The argument checks of sdfv_program_raycast on their own (no device needed): on SDFV_OK *checked (may be NULL) is the
+ * descriptor as the library reads it, the defaults of max_steps, hit_eps and normal_eps in place.  What the host mirror calls,
+ * so that both routes refuse the same descriptors with the same messages. */
+int sdfv_program_raycast_check(const sdfv_program_cast_desc *desc, sdfv_program_cast_desc *checked);
+
 /* ---- SDF programs compiled to kernels of their own, at run time ----
  * An interpreted program pays for the interpreter per evaluation (instruction fetch, dispatch, the stack's shifts).
  * sdfv_program_compile turns ONE program into gfx kernels in which every instruction is a compile-time constant: it generates a

@@ -34,6 +34,12 @@ int sdfv_program_as_surface(const sdfv_program *p, sdfv_surface *out);
  * n_threads: rows are dealt to that many threads (the viewer's worker pool); <= 0 = the CPUs this process may use. */
 int sdfv_program_raymarch_host(const sdfv_program_march_desc *desc, int n_threads);
 
+/* sdfv_program_raycast (sdfgrid.h) evaluated ON THE HOST: the same descriptor, the same checks and messages
+ * (sdfv_program_raycast_check; sdfv_last_error() has the text), the same per-ray source as the kernel -- rays and hits are HOST
+ * arrays here, and every byte of every record is what the device writes.  Needs no device.  Runs of 256 rays are dealt to the
+ * CPUs this process may use (the viewer's worker pool). */
+int sdfv_program_raycast_host(const sdfv_program_cast_desc *desc);
+
 /* ---- the program editor: parameters, set_parameter and changed (src/sdf/mod.rs:60-86) for a program ----
  * Program handles stay immutable.  An editor holds the instructions, a list of float parameters and the CURRENT SNAPSHOT, an
  * sdfv_program made by sdfv_program_create; every accepted edit makes a new snapshot through the same validator.  Replaced

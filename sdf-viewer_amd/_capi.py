@@ -100,6 +100,28 @@ class ProgramMarchDesc(C.Structure):
 assert C.sizeof(ProgramMarchDesc) == 88
 
 
+class Ray(C.Structure):
+    """sdfv_ray: one ray of sdfv_program_raycast's list."""
+    _fields_ = [("origin", C.c_float * 3), ("t_min", C.c_float), ("dir", C.c_float * 3), ("t_max", C.c_float)]
+
+
+class RayHit(C.Structure):
+    """sdfv_ray_hit: what sdfv_program_raycast writes per ray."""
+    _fields_ = [("status", C.c_int32), ("steps", C.c_int32), ("t", C.c_float), ("pos", C.c_float * 3), ("normal", C.c_float * 3),
+                ("sample", Sample)]
+
+
+class ProgramCastDesc(C.Structure):
+    """sdfv_program_cast_desc: the descriptor of sdfv_program_raycast / sdfv_program_raycast_host (size-prefixed)."""
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("program", C.c_void_p), ("bb_min", C.POINTER(C.c_float)),
+                ("bb_max", C.POINTER(C.c_float)), ("rays", C.c_void_p), ("hits", C.c_void_p), ("n", C.c_uint64),
+                ("flags", C.c_uint32), ("max_steps", C.c_uint32), ("hit_eps", C.c_float), ("normal_eps", C.c_float)]
+
+
+assert C.sizeof(Ray) == 32 and C.sizeof(RayHit) == 64 and C.sizeof(ProgramCastDesc) == 72
+CAST_NORMALS, CAST_MATERIALS = 1, 2  # SDFV_CAST_*
+
+
 class CompiledInfo(C.Structure):
     """sdfv_compiled_info (size-prefixed): what sdfv_program_compiled_info reports about a handle."""
     _fields_ = [("size", C.c_uint32), ("routes", C.c_uint32), ("arch", C.c_char * 32), ("compile_seconds", C.c_double),
@@ -223,6 +245,8 @@ PROTOTYPES = {
                                          C.c_void_p, C.c_uint32, C.c_void_p]),
     "sdfv_program_raymarch": (C.c_int, [C.POINTER(ProgramMarchDesc), C.c_void_p]),
     "sdfv_program_raymarch_check": (C.c_int, [C.POINTER(ProgramMarchDesc), C.POINTER(ProgramMarchDesc), C.POINTER(C.c_float)]),
+    "sdfv_program_raycast": (C.c_int, [C.POINTER(ProgramCastDesc), C.c_void_p]),
+    "sdfv_program_raycast_check": (C.c_int, [C.POINTER(ProgramCastDesc), C.POINTER(ProgramCastDesc)]),
     # ... compiled to kernels of their own
     "sdfv_program_compile": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.POINTER(C.c_void_p)]),
     "sdfv_program_compiled_info": (C.c_int, [C.c_void_p, C.POINTER(CompiledInfo)]),

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "api_internal.h"
+#include "program_cast_kernels.h"
 #include "program_handle.h"
 #include "program_kernels.h"
 #include "program_march_kernels.h"
@@ -252,6 +253,56 @@ int sdfv_program_raymarch(const sdfv_program_march_desc* desc, void* stream) {
         SDFV_HIP(sdfv::launch_program_march(a, compiled, (hipStream_t)stream));
     }
     return SDFV_OK;
+}
+
+int sdfv_program_raycast_check(const sdfv_program_cast_desc* desc, sdfv_program_cast_desc* checked) {
+    sdfv_program_cast_desc d;
+    if (int rc = read_sized_desc(desc, sizeof(sdfv_program_cast_desc), "sdfv_program_cast_desc", d)) return rc;
+    if (d.reserved != 0) return set_error(SDFV_ERR_INVALID_ARGUMENT, "sdfv_program_cast_desc: reserved must be 0");
+    if (!d.program) return set_error(SDFV_ERR_INVALID_ARGUMENT, "sdfv_program_cast_desc.program is NULL");
+    if ((d.bb_min == nullptr) != (d.bb_max == nullptr))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "bounding box: bb_min and bb_max are both given or both NULL (the program's box)");
+    for (int i = 0; d.bb_min && i < 3; ++i)
+        if (!std::isfinite(d.bb_min[i]) || !std::isfinite(d.bb_max[i]) || !(d.bb_max[i] > d.bb_min[i]))
+            return set_error(SDFV_ERR_INVALID_ARGUMENT, "degenerate bounding box on axis %d: [%g, %g]", i, d.bb_min[i], d.bb_max[i]);
+    if (int rc = check_point_buffers(d.rays, d.hits, d.n)) return rc;
+    if (int rc = check_word_aligned("rays and hits", d.rays, d.hits)) return rc;
+    if (d.flags & ~(SDFV_CAST_NORMALS | SDFV_CAST_MATERIALS)) return set_error(SDFV_ERR_INVALID_ARGUMENT, "unknown flags 0x%x", d.flags);
+    if (d.max_steps > 4096) return set_error(SDFV_ERR_INVALID_ARGUMENT, "max_steps %u is outside [1, 4096] (0 = 256)", d.max_steps);
+    if (!(d.hit_eps >= 0.0f) || !std::isfinite(d.hit_eps))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "hit_eps = %g: a distance > 0, or 0 for 1e-5", d.hit_eps);
+    if (!(d.normal_eps >= 0.0f) || !std::isfinite(d.normal_eps))
+        return set_error(SDFV_ERR_INVALID_ARGUMENT, "normal_eps = %g: a distance > 0, or 0 for 0.001", d.normal_eps);
+    if (d.max_steps == 0) d.max_steps = 256;
+    if (d.hit_eps == 0.0f) d.hit_eps = 1e-5f;
+    if (d.normal_eps == 0.0f) d.normal_eps = 0.001f;
+    if (checked) *checked = d;
+    return SDFV_OK;
+}
+
+int sdfv_program_raycast(const sdfv_program_cast_desc* desc, void* stream) {
+    sdfv_program_cast_desc d;
+    if (int rc = sdfv_program_raycast_check(desc, &d)) return rc;
+    if (int rc = need_device()) return rc;
+    if (d.n == 0) return SDFV_OK;
+    sdfv::ProgramCastArgs a;
+    memset(&a, 0, sizeof(a));
+    const float* bb = nullptr;
+    if (int rc = program_on_device(d.program, &a.c.ops, &a.c.n_ops, &bb)) return rc;
+    for (int i = 0; i < 3; ++i) {  // (copied: the caller's box is free again when the call returns)
+        a.c.bounds_min[i] = d.bb_min ? d.bb_min[i] : bb[i];
+        a.c.bounds_max[i] = d.bb_max ? d.bb_max[i] : bb[3 + i];
+    }
+    a.c.flags = d.flags;
+    a.c.max_steps = d.max_steps;
+    a.c.hit_eps = d.hit_eps;
+    a.c.normal_eps = d.normal_eps;
+    a.rays = d.rays;
+    a.hits = d.hits;
+    a.n = d.n;
+    a.rays16 = ((uintptr_t)d.rays & 15) == 0;
+    a.hits16 = ((uintptr_t)d.hits & 15) == 0;
+    SDFV_HIP_RETURN(sdfv::launch_program_cast(a, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -50,15 +50,24 @@ SDFV_MARCH_FN float oob_dist(const sdfv_render_params& rp, V3 p) {
     return fmaxf(ox, fmaxf(oy, oz));
 }
 
+// The slab test's arithmetic -- where the line eye + t * d0 enters and leaves the box [b.bounds_min, b.bounds_max]
+// (sdfv_render_params, or the cast's own block): six divisions, then
+// tnear = max(max(min x, min y), min z) and tfar = min(min(max x, max y), max z).  The ray cast of program_cast.h clips a
+// caller's [t_min, t_max] against the two.
+template <typename Box>
+SDFV_MARCH_FN void box_slab_interval(const Box& b, V3 eye, V3 d0, float& tnear, float& tfar) {
+    const float tx1 = (b.bounds_min[0] - eye.x) / d0.x, tx2 = (b.bounds_max[0] - eye.x) / d0.x;
+    const float ty1 = (b.bounds_min[1] - eye.y) / d0.y, ty2 = (b.bounds_max[1] - eye.y) / d0.y;
+    const float tz1 = (b.bounds_min[2] - eye.z) / d0.z, tz2 = (b.bounds_max[2] - eye.z) / d0.z;
+    tnear = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2));
+    tfar = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
+}
 // The bbox fragment of the ray eye + t * d0 (d0 normalised): slab test standing in for the rasterised cube
 // (scene/sdf/mod.rs:254-282).  Returns whether the pixel is covered by the box; tfrag = the fragment's distance from the eye --
 // the entry point when the camera is outside the box, the exit point when it is inside -- feeds fragment_ray.
 SDFV_MARCH_FN bool box_slab_test(const sdfv_render_params& rp, V3 eye, V3 d0, bool in_image, float& tfrag) {
-    const float tx1 = (rp.bounds_min[0] - eye.x) / d0.x, tx2 = (rp.bounds_max[0] - eye.x) / d0.x;
-    const float ty1 = (rp.bounds_min[1] - eye.y) / d0.y, ty2 = (rp.bounds_max[1] - eye.y) / d0.y;
-    const float tz1 = (rp.bounds_min[2] - eye.z) / d0.z, tz2 = (rp.bounds_max[2] - eye.z) / d0.z;
-    const float tnear = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2));
-    const float tfar = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
+    float tnear, tfar;
+    box_slab_interval(rp, eye, d0, tnear, tfar);
     tfrag = tnear > 0.0f ? tnear : tfar;
     return in_image && (tfar >= tnear && tfar > 0.0f);
 }

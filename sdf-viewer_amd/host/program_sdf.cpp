@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "../../include/sdfprogram.h"
+#include "../csrc/program_cast.h"
 #include "../csrc/program_eval.h"
 #include "../csrc/program_march.h"
 #include "worker_pool.hpp"
@@ -137,7 +138,61 @@ void ProgramSDF::raymarch(const sdfv_program_march_desc& d, float normal_h, bool
     pool.end();
 }
 
+void ProgramSDF::cast(const sdfv_program_cast_desc& d, int n_threads) const {
+    if (d.n == 0) return;
+    sdfv::pcast::Cast c;
+    c.ops = ops_;
+    c.n_ops = (uint32_t)n_ops_;
+    c.flags = d.flags;
+    for (int a = 0; a < 3; ++a) {
+        c.bounds_min[a] = d.bb_min ? d.bb_min[a] : bb_[a];
+        c.bounds_max[a] = d.bb_max ? d.bb_max[a] : bb_[3 + a];
+    }
+    c.max_steps = d.max_steps;
+    c.hit_eps = d.hit_eps;
+    c.normal_eps = d.normal_eps;
+    // the list is dealt out in runs of 256 rays: a run across the object costs many times a run of misses
+    constexpr uint64_t kRun = 256;
+    const uint64_t n_runs = (d.n + kRun - 1) / kRun;
+    const sdfv::prog::Interpreter eval{ops_, (uint32_t)n_ops_};
+    std::atomic<uint64_t> next{0};
+    const auto work = [&](unsigned) {
+        for (uint64_t r = next.fetch_add(1, std::memory_order_relaxed); r < n_runs; r = next.fetch_add(1, std::memory_order_relaxed)) {
+            const uint64_t end = (r + 1) * kRun < d.n ? (r + 1) * kRun : d.n;
+            for (uint64_t i = r * kRun; i < end; ++i) {
+                sdfv_ray ray;  // (the arrays need no more than 4-byte alignment)
+                sdfv_ray_hit hit;
+                memcpy(&ray, d.rays + i, sizeof(ray));
+                sdfv::pcast::cast_ray_program(c, eval, ray, true, hit);
+                memcpy(d.hits + i, &hit, sizeof(hit));
+            }
+        }
+    };
+    unsigned n = n_threads > 0 ? (unsigned)n_threads : WorkerPool::usable_cpus();
+    if ((uint64_t)n > n_runs) n = (unsigned)n_runs;
+    WorkerPool pool;
+    pool.begin(n);
+    try {
+        pool.run(n, work);
+    } catch (...) {
+        pool.end();
+        throw;
+    }
+    pool.end();
+}
+
 }  // namespace sdfviewer
+
+extern "C" int sdfv_program_raycast_host(const sdfv_program_cast_desc* desc) {
+    sdfv_program_cast_desc d;
+    if (int rc = sdfv_program_raycast_check(desc, &d)) return rc;
+    try {  // nothing crosses the C boundary
+        sdfviewer::ProgramSDF(d.program).cast(d, 0);
+    } catch (...) {
+        return SDFV_ERR_INVALID_ARGUMENT;
+    }
+    return SDFV_OK;
+}
 
 extern "C" int sdfv_program_raymarch_host(const sdfv_program_march_desc* desc, int n_threads) {
     sdfv_program_march_desc d;

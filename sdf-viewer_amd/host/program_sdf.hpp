@@ -26,6 +26,11 @@ class ProgramSDF final : public SDFSurface {
     // n_threads workers (<= 0: the CPUs this process may use).  srgb_round: SDFV_OPT_EXT_SRGB_QUANT.
     void raymarch(const sdfv_program_march_desc& checked, float normal_h, bool srgb_round, int n_threads) const;
 
+    // The ray cast on the host (include/sdfprogram.h, sdfv_program_raycast_host): `checked` as sdfv_program_raycast_check hands it
+    // out, rays and hits in HOST memory; csrc/program_cast.h per ray, runs of rays dealt to n_threads workers (<= 0: the CPUs this
+    // process may use).  Every byte of every record is the device's.
+    void cast(const sdfv_program_cast_desc& checked, int n_threads) const;
+
     // meshing on the device: sdfv_program_mesh_extract / sdfv_program_mesh_postproc through mesh_sdf() and Mesh::postproc()
     const sdfv_program* device_program() const override { return program_; }
 

@@ -21,6 +21,7 @@ Parameters (include/sdfprogram.h, "program editor"): name an operand while build
     ed.update_viewer(viewer)                           # re-samples the box by whole passes (sdfv_viewer_update_program)
     rgba = prog.render(camera, 1920, 1080)             # sphere-traced directly per pixel: no grid
     vertices, indices = prog.mesh(128, materials=True) # marching cubes + Mesh::postproc: [V, 12], [3 * triangles]
+    hits = prog.cast(rays)                             # [n, 8] rays -> [n, 16]: status, steps, t, pos, normal, sample per ray
 
 The builder only appends instructions; sdfv_program_create validates them (build() raises SdfvError with the message that
 names the offending instruction).
@@ -47,6 +48,25 @@ class ProgramParam(C.Structure):
     _fields_ = [("id", C.c_uint32), ("name", C.c_char_p), ("description", C.c_char_p), ("min", C.c_float), ("max", C.c_float),
                 ("step", C.c_float), ("value", C.c_float), ("n_targets", C.c_uint32), ("targets", ParamTarget * PARAM_MAX_TARGETS),
                 ("has_box", C.c_uint32), ("box", C.c_float * 6)]
+
+
+def ray_dtype():
+    """numpy dtype of sdfv_ray (32 bytes)."""
+    import numpy as np
+    return np.dtype([("origin", "<f4", (3,)), ("t_min", "<f4"), ("dir", "<f4", (3,)), ("t_max", "<f4")])
+
+
+def hit_dtype():
+    """numpy dtype of sdfv_ray_hit (64 bytes); sample = (distance, r, g, b, metallic, roughness, occlusion)."""
+    import numpy as np
+    return np.dtype([("status", "<i4"), ("steps", "<i4"), ("t", "<f4"), ("pos", "<f4", (3,)), ("normal", "<f4", (3,)),
+                     ("sample", "<f4", (7,))])
+
+
+def hits_view(a):
+    """[n, 16] float32 (what CompiledProgram.cast hands out, as numpy) -> the same bytes as a hit_dtype() array [n]."""
+    import numpy as np
+    return np.ascontiguousarray(a).view(hit_dtype()).reshape(-1)
 
 
 def translation(tx, ty, tz):
@@ -347,6 +367,53 @@ class CompiledProgram:
         check(fn(C.byref(d), int(threads)))
         out = (colour,) + ((aux,) if want_aux else ()) + ((depth,) if want_depth else ())
         return out[0] if len(out) == 1 else out
+
+    def cast_desc(self, rays_ptr, hits_ptr, n, normals=True, materials=True, max_steps=0, hit_eps=0.0, normal_eps=0.0, box=None):
+        """An sdfv_program_cast_desc over this program from raw addresses (and what keeps its box alive).  box: 6 floats
+        (min.xyz, max.xyz) or None for the program's."""
+        d = _capi.ProgramCastDesc()
+        d.size = C.sizeof(d)
+        d.program = self.h
+        keep = None
+        if box is not None:
+            keep = (_capi.f3(box[:3]), _capi.f3(box[3:]))
+            d.bb_min, d.bb_max = keep
+        d.rays, d.hits, d.n = rays_ptr, hits_ptr, int(n)
+        d.flags = (_capi.CAST_NORMALS if normals else 0) | (_capi.CAST_MATERIALS if materials else 0)
+        d.max_steps, d.hit_eps, d.normal_eps = int(max_steps), float(hit_eps), float(normal_eps)
+        return d, keep
+
+    def cast(self, rays, *, normals=True, materials=True, max_steps=0, hit_eps=0.0, normal_eps=0.0, box=None, stream=None,
+             out=None):
+        """sdfv_program_raycast: rays [n, 8] float32 CUDA tensor (origin.xyz, t_min, dir.xyz, t_max per ray) -> hits [n, 16]
+        float32 CUDA tensor, the 64-byte sdfv_ray_hit records (status and steps are int32 bit patterns: hits_view() of the
+        tensor's numpy copy names the fields).  max_steps / hit_eps / normal_eps: 0 = the library's 256 / 1e-5 / 0.001; box: the
+        6 floats to clip against (None: the program's); out: optional tensor that receives the records."""
+        import torch
+        from . import _dev_ptr, _out_tensor, _stream_ptr
+        if rays.dim() != 2 or rays.shape[1] != 8:
+            raise TypeError("rays must be an [n, 8] tensor")
+        n = rays.shape[0]
+        out = _out_tensor(out, (n, 16), torch.float32, rays.device, "out")
+        d, keep = self.cast_desc(_dev_ptr(rays, "rays") if n else None, out.data_ptr() if n else None, n, normals, materials,
+                                 max_steps, hit_eps, normal_eps, box)
+        check(lib.sdfv_program_raycast(C.byref(d), _stream_ptr(stream)))
+        return out
+
+    def cast_host(self, rays, *, normals=True, materials=True, max_steps=0, hit_eps=0.0, normal_eps=0.0, box=None):
+        """sdfv_program_raycast_host: the same cast on the host, by the per-ray source the kernel is built from; needs no device.
+        rays: [n, 8] float32 numpy array or a RAY_DTYPE structured array -> HIT_DTYPE structured array [n]."""
+        import numpy as np
+        from . import viewer
+        fn = viewer.lib.sdfv_program_raycast_host
+        fn.restype, fn.argtypes = C.c_int, [C.POINTER(_capi.ProgramCastDesc)]
+        r = np.ascontiguousarray(rays)
+        r = r.view(np.float32).reshape(-1, 8) if r.dtype == ray_dtype() else np.ascontiguousarray(r, np.float32).reshape(-1, 8)
+        hits = np.empty(len(r), hit_dtype())
+        d, keep = self.cast_desc(r.ctypes.data if len(r) else None, hits.ctypes.data if len(r) else None, len(r), normals, materials,
+                                 max_steps, hit_eps, normal_eps, box)
+        check(fn(C.byref(d)))
+        return hits
 
     def as_surface(self, device_route=True):
         """A viewer.Surface over this program (sdfv_program_as_surface); device_route=False clears sample_batch_device, so
